@@ -1,6 +1,6 @@
 """Benchmark of the native U-Net hot path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c3|c4|c5|c2]
+    python bench.py [--gpus N --steps K --warmup W] [--workload c3|c4|c5|c2] [--full] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no torch.distributed environment: bench.py starts itself under
 `python -m torch.distributed.run --nproc-per-node N` (child processes; this process has not touched the GPU) and
@@ -14,7 +14,7 @@ Workloads (BASELINE.json `configs`; the metric is "voxels/sec (train step + full
        (96*chunks*N + 32) x 128 x 128 volume shared by the N ranks = `chunks` overlapping 128^3 blocks per GPU
        (reflect-padded block gather, forward + softmax, Gaussian blend, piece exchange for N > 1, normalise +
        quantise).  value = (training chunk voxels + UNIQUE predicted volume voxels) / s, whole job, weak scaling.
-       The same run then times the C4 volume once (`"c4"` object of the line; `--c4-reps 0` skips it).
+       With `--full` the same run then times the C4 volume once (`"c4"` object of the line; `--c4-reps 0` skips it).
   c4 (configs[3])  the fixed 1024^3 uint8 volume (generated on the device from the voxel coordinates, identical for
        every N), 1 331 blocks of 128^3, overlap 0.25, sharded over the N ranks (shard.py): one step = one whole-volume
        prediction, wall time including every exchange.  value = unique volume voxels / s; STRONG scaling.
@@ -26,7 +26,15 @@ trainer.py:59) + prediction in the default, tolerance-meeting mode (split precis
 engine_auto.EngineAuto's calibration on the model's own weights and reported in `config.predict_dtype` /
 `config.predict_mode_selection`; the reference predicts in fp32, predict.py:30-35).
 
-The JSON line also carries
+A plain run sets up, warms up, times the `--steps` steps and prints the headline line (`metric`, `value`, `unit`, `ms_per_step`,
+`dtype`, `config`, ...; `rccl_ranks` -- N > 1: the result of an all-reduce of ones over the process group, must equal n_gpus).
+`--dump-outputs DIR` then also writes what the last timed step returned to its caller as DIR/<name>.npy
+(float32; rank 0's part; above 60 MB in all, a fixed seeded sample of each array): `train_metrics` (Loss, Dice, IoU, MCC of the
+training step) and `predict_volume` (uint8 [Z, Y, X, C] of the 3-D workloads) or `predict_probs` / `predict_classes` (2-D).
+
+With `--full` the JSON line also carries (each measured in runs of its own after the timed steps)
+  legs         -- the step's training and prediction legs timed apart by HIP events (`c4`: the C4 volume, for c3);
+  c2, c5       -- c3 with N = 1 (unless `--no-extras`): the compact lines of those workloads;
   roofline     -- the workload's bottleneck 3x3(x3) conv (dec0.conv1), timed live with HIP events on the launch
                   stream over 50 back-to-back launches (average = `achieved`: the figure the committed rocprofv3
                   summary of the same launch sequence reproduces; the first 8 and the last 20 are given as burst /
@@ -42,8 +50,7 @@ The JSON line also carries
   cpu_baseline -- the oracle (oracle/unet_ref.py, torch CPU fp32, host cores) timed on a bounded sample of the same
                   workload, rank 0 / N = 1 only;
   legs.predict_2p5d -- the reference's own predict semantics (predict.py:79-112): one 128^3 block through the
-                  2-D net along 3 axes, in the default mode and fp16, with the oracle's predict_block on the host cores beside it;
-  rccl_ranks   -- N > 1: the result of an all-reduce of ones over the process group (must equal n_gpus).
+                  2-D net along 3 axes, in the default mode and fp16, with the oracle's predict_block on the host cores beside it.
 """
 import argparse
 import json
@@ -52,6 +59,7 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -99,6 +107,27 @@ def synth_volume_slab(z0, z1, Y, X, device):
         h = ((zi * 73856093) ^ (yi * 19349663) ^ (xi * 83492791)) & 31
         out[a - z0:b - z0] = (128.0 + 30.0 * f + h.float()).clamp_(1, 255).to(torch.uint8)
     return out
+
+
+DUMP_BUDGET_BYTES = 60_000_000     # --dump-outputs: float32 payload of all arrays together
+
+
+def dump_outputs(arrays, out_dir):
+    """Writes each tensor of `arrays` (name -> tensor, any device) as <out_dir>/<name>.npy in float32.  When the arrays together
+    exceed DUMP_BUDGET_BYTES, each one keeps its share of the budget as a sample of its flat elements at seeded random positions
+    (sorted; the seed is a function of the name), so that two runs with the same arguments write the same positions."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // 4
+    total = sum(t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        keep = n if total <= cap else max(1, n * cap // total)
+        if keep < n:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, n, (keep,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(out_dir, f'{name}.npy'), flat.float().cpu().numpy().reshape(t.shape if keep == n else (keep,)))
 
 
 def flops_per_voxel(dim, levels, base, cin, ncls):
@@ -486,7 +515,14 @@ def main():
     ap.add_argument('--no-2p5d', action='store_true', help='skip legs.predict_2p5d (the reference-semantics 2.5-D block prediction)')
     ap.add_argument('--no-parity-mode', action='store_true', help='time the all-16-bit step only (no split-precision prediction leg)')
     ap.add_argument('--no-extras', action='store_true', help='c3 only: skip the compact c2 / c5 sub-objects of the line')
+    ap.add_argument('--full', action='store_true', help='after the timed steps also measure the legs, the C4 volume, throughput mode, '
+                    'roofline, parity, the 2.5-D leg, the CPU baseline and (c3) the c2 / c5 sub-objects; the --no-* / --c4-* options '
+                    'apply to these')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step returned as DIR/<name>.npy '
+                    '(float32, rank 0, at most 60 MB: larger outputs as a seeded sample)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(relaunch(args))
 
@@ -528,12 +564,13 @@ def main():
     if out is not None and rank == 0:
         out['rccl_ranks'] = ranks_seen if (dist is not None and backend == 'nccl') else None
         out['process_group'] = {'backend': backend if dist is not None else None, 'ranks_seen_by_all_reduce': ranks_seen}
-        if world == 1 and args.workload == 'c3' and not args.no_extras:
+        if args.full and world == 1 and args.workload == 'c3' and not args.no_extras:
             # the other single-GPU configurations of BASELINE.json in the SAME driver-run line, as compact sub-objects
             # (10 steps each; the full lines of those workloads are `--workload c2 / c5`)
             for wl in ('c2', 'c5'):
                 sub = argparse.Namespace(**vars(args))
                 sub.workload, sub.steps, sub.warmup, sub.chunks, sub.c4_reps, sub.no_2p5d = wl, 10, 3, None, 0, True
+                sub.dump_outputs = None
                 try:
                     out[wl] = compact(run(sub, wl, rank, world, dev, dist, group))
                 except Exception as e:                                         # the headline must not be lost to a side measurement
@@ -591,6 +628,7 @@ def run(args, workload, rank, world, dev, dist, group):
     legs = {'train': 0.0, 'predict': 0.0}
     leg_events = []
     info = {}
+    last = {}                   # what the latest step returned to its caller (device tensors): --dump-outputs
     ops = None
 
     # ------------------------------------------------------------------ the step of each workload
@@ -603,7 +641,7 @@ def run(args, workload, rank, world, dev, dist, group):
 
         def step(timed=False):
             t0 = time.time()
-            _, st = shard.predict_volume_sharded(ops, my_slab, V, S, 0.25, group=group)
+            last['predict_volume'], st = shard.predict_volume_sharded(ops, my_slab, V, S, 0.25, group=group)
             info.update(st)
             if timed:
                 torch.cuda.synchronize(); legs['predict'] += time.time() - t0
@@ -618,7 +656,8 @@ def run(args, workload, rank, world, dev, dist, group):
         X = chunks.reshape((B, 1) + tile)                                  # uint8, /255 in the first conv
         lab = (X.to(torch.int32) * ncls // 256).clamp_(max=ncls - 1)
         y = torch.cat([(lab == c) for c in range(ncls)], 1).to(torch.float16)       # loader contract: fp16 one-hot (loader.py:150-152)
-        w = (torch.rand((B, 1) + tile, device=dev) > 0.1).to(torch.float16).expand((B, ncls) + tile).contiguous()
+        gw = torch.Generator(device=dev).manual_seed(5678 + rank)
+        w = (torch.rand((B, 1) + tile, generator=gw, device=dev) > 0.1).to(torch.float16).expand((B, ncls) + tile).contiguous()
         y = y * w
         if dim == 3:
             # predict leg: ONE volume shared by all ranks, Z = 96*B*world + 32 planes of S x S -> exactly B overlapping
@@ -635,7 +674,7 @@ def run(args, workload, rank, world, dev, dist, group):
             processed_vox = float(B * world) * tvox
 
             def predict_leg():
-                _, st = shard.predict_volume_sharded(ops, my_slab, V, S, 0.25, group=group)
+                last['predict_volume'], st = shard.predict_volume_sharded(ops, my_slab, V, S, 0.25, group=group)
                 info.update(st)
         else:
             # 2-D: the slices of the batch through the forward + softmax + argmax (predict.py:16-47 per slice)
@@ -646,6 +685,7 @@ def run(args, workload, rank, world, dev, dist, group):
 
             def predict_leg():
                 model.engine('eval').infer(chunks, (tvox, tvox, tvox, tile[1], 1), B, 1, tile[0], tile[1], probs=probs, cls=cls)
+                last['predict_probs'], last['predict_classes'] = probs, cls
         train_vox = float(B * world) * tvox
         scaling = 'weak'
 
@@ -655,7 +695,7 @@ def run(args, workload, rank, world, dev, dist, group):
             if timed:
                 ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
                 ev[0].record()
-            trainer.train_step(X, y, w, sync=False)
+            last['train_metrics'] = trainer.train_step(X, y, w, sync=False)
             if timed:
                 ev[1].record()
             model.engine('eval')                                            # re-packs the updated weights (BN folded)
@@ -683,9 +723,9 @@ def run(args, workload, rank, world, dev, dist, group):
         if ops is not None:
             ops = shard.NativeOps(model, ncls, S)                 # (step / predict_leg look `ops` up at call time)
 
-    def timed_region(c4_reps):
-        """warm-up, barrier, K steps, barrier, max over ranks; then the leg split in separate steps (the timed region has no extra
-        syncs) and, for c3, the C4 volume."""
+    def timed_region(c4_reps, split_legs=True, dump_dir=None):
+        """warm-up, barrier, K steps, barrier, max over ranks (dump_dir: what the last of them returned is written there); then,
+        with split_legs, the leg split in separate steps (the timed region has no extra syncs) and, for c3, the C4 volume."""
         nonlocal legs
         legs = {'train': 0.0, 'predict': 0.0}
         for _ in range(max(1, args.warmup)):
@@ -696,6 +736,10 @@ def run(args, workload, rank, world, dev, dist, group):
             step()
         barrier()
         dt = max_over_ranks(time.time() - t0)
+        if dump_dir:
+            dump_outputs(last, dump_dir)
+        if not split_legs:
+            return {'dt': dt, 'c4': None}
         nleg = 4 if workload != 'c4' else 1          # (2 steps read the prediction leg anywhere in 2.08-2.43 ms on one box)
         leg_events.clear()
         for _ in range(nleg):
@@ -747,41 +791,19 @@ def run(args, workload, rank, world, dev, dist, group):
     # ------------------------------------------------------------------ the headline region.  For the BatchNorm networks without
     # quantised weights it is the COMPLIANT pairing: training in the workload's 16-bit dtype (the reference trains
     # under '16-mixed', trainer.py:59) + prediction in the tolerance-meeting split-precision mode (fp16x2: logits within 1e-3 of the CPU
-    # fp32 path, what UNet() predicts in by default; the reference predicts in fp32, predict.py:30-35).  The all-16-bit step is timed
-    # afterwards, exactly the same way, as `throughput_mode`.
+    # fp32 path, what UNet() predicts in by default; the reference predicts in fp32, predict.py:30-35).  With --full the all-16-bit step
+    # is timed afterwards, exactly the same way, as `throughput_mode`.
     compliant = not cfg['wq'] and not args.no_parity_mode
     if compliant:
         set_predict_mode('fp16x2')
-    head = timed_region(args.c4_reps)
+    head = timed_region(args.c4_reps, split_legs=args.full, dump_dir=args.dump_outputs if rank == 0 else None)
     selection = model.engine('eval').describe() if compliant and hasattr(model.engine('eval'), 'describe') else None
     dt = head['dt']
     value = (train_vox + unique_vox) * args.steps / dt
     c4 = head['c4']
-    predict_events = probe_layer(1 if workload == 'c4' else 6, False) if compliant else []
-
-    # ------------------------------------------------------------------ throughput mode (prediction in the 16-bit dtype) + the roofline
-    # layer as the 16-bit step launches it
-    tm = None
-    if compliant:
-        set_predict_mode(dtype)
-        tm = timed_region(min(1, args.c4_reps))
-    probe_train = workload != 'c4' and not cfg['wq']      # C5 trains on the 16-bit kernel: only its fp8 prediction launches count
-    probe_events = probe_layer(1 if workload == 'c4' else 10, probe_train)
 
     out = None
     if rank == 0:
-        # `roofline` top level = the layer alone, back to back (the figure `rocprofv3 --kernel-trace --stats` of tools/bench_conv.py
-        # reproduces: profiles/r03_roofline_*); the launches inside real steps are the `in_situ` sub-object
-        if probe_events:
-            in_situ = conv_roofline_in_situ(nv, cfg, workload, dtype, probe_events[:400])
-            roof = conv_roofline_back_to_back(nv, cfg, workload, dtype, in_situ['tiles_per_launch'])
-            roof['traffic'] = in_situ.pop('traffic')
-            roof['in_situ'] = in_situ
-        else:                                     # (GroupNorm: the engines' timing hook sits in the BatchNorm launch path)
-            roof = conv_roofline_back_to_back(nv, cfg, workload, dtype, max(1, B if dim == 3 else B))
-            roof['traffic'] = pmc_traffic(workload, roof['tiles_per_launch'])
-        if dim == 3 and roof['tiles_per_launch'] != 1:
-            roof['back_to_back_1_tile'] = conv_roofline_back_to_back(nv, cfg, workload, dtype, 1)
         tile_s = 'x'.join(str(s) for s in tile)
         if workload == 'c4':
             desc = (f'C4: tiled prediction of one {V[0]}^3 uint8 volume (generated on the device from the voxel coordinates), '
@@ -808,8 +830,46 @@ def run(args, workload, rank, world, dev, dist, group):
                        'tiles_per_gpu': B, 'tile': list(tile), 'levels': levels, 'base': base,
                        'train_voxels_per_step': train_vox, 'predict_unique_voxels_per_step': unique_vox,
                        'predict_processed_voxels_per_step': processed_vox, 'fwd_flop_per_voxel': fpv},
-            'roofline': roof,
         }
+        x2m_on = compliant and selection is not None and selection['form'] == 'x2m'      # the form engine_auto.EngineAuto selected
+        x2_name = ('fp16x2 with the cross terms on the fp8 matrix cores (x2m: x_hi w_hi on v_mfma_f32_16x16x32_f16 + [x_lo8 | x_hi8][w_hi8 | w_lo8] on '
+                   'v_mfma_f32_16x16x128_f8f6f4, fp32 accumulate)') if x2m_on else 'fp16x2 (split precision: fp16 hi + lo words, fp32 accumulate)'
+        if compliant:
+            out['headline_mode'] = (f'compliant pairing: training {cfg["dtype"]} (trainer.py:59 trains under 16-mixed) + prediction {x2_name}: logits within '
+                                    f'1e-3 of the CPU fp32 path (predict.py:30-35 predicts in fp32); the all-16-bit step is `throughput_mode`' +
+                                    ('' if args.full else ' (--full)'))
+            # the form the default engine SELECTED for this model (x2m against fp16x2 on a calibration tile; engine_auto.py) and the figure behind it
+            out['config']['predict_dtype'] = f"fp16x2 ({selection['form']})" if selection else 'fp16x2'
+            out['config']['predict_mode_selection'] = selection
+    if not args.full:
+        return out
+
+    # ------------------------------------------------------------------ --full: everything else, in runs of its own after the timed steps
+    predict_events = probe_layer(1 if workload == 'c4' else 6, False) if compliant else []
+
+    # ------------------------------------------------------------------ throughput mode (prediction in the 16-bit dtype) + the roofline
+    # layer as the 16-bit step launches it
+    tm = None
+    if compliant:
+        set_predict_mode(dtype)
+        tm = timed_region(min(1, args.c4_reps))
+    probe_train = workload != 'c4' and not cfg['wq']      # C5 trains on the 16-bit kernel: only its fp8 prediction launches count
+    probe_events = probe_layer(1 if workload == 'c4' else 10, probe_train)
+
+    if rank == 0:
+        # `roofline` top level = the layer alone, back to back (the figure `rocprofv3 --kernel-trace --stats` of tools/bench_conv.py
+        # reproduces: profiles/r03_roofline_*); the launches inside real steps are the `in_situ` sub-object
+        if probe_events:
+            in_situ = conv_roofline_in_situ(nv, cfg, workload, dtype, probe_events[:400])
+            roof = conv_roofline_back_to_back(nv, cfg, workload, dtype, in_situ['tiles_per_launch'])
+            roof['traffic'] = in_situ.pop('traffic')
+            roof['in_situ'] = in_situ
+        else:                                     # (GroupNorm: the engines' timing hook sits in the BatchNorm launch path)
+            roof = conv_roofline_back_to_back(nv, cfg, workload, dtype, max(1, B if dim == 3 else B))
+            roof['traffic'] = pmc_traffic(workload, roof['tiles_per_launch'])
+        if dim == 3 and roof['tiles_per_launch'] != 1:
+            roof['back_to_back_1_tile'] = conv_roofline_back_to_back(nv, cfg, workload, dtype, 1)
+        out['roofline'] = roof
         def leg_fields(r):
             lg = {}
             if r['train'] > 0:
@@ -824,15 +884,7 @@ def run(args, workload, rank, world, dev, dist, group):
         out['legs'] = leg_fields(head)
         if c4 is not None:
             out['c4'] = c4
-        x2m_on = compliant and selection is not None and selection['form'] == 'x2m'      # the form engine_auto.EngineAuto selected
-        x2_name = ('fp16x2 with the cross terms on the fp8 matrix cores (x2m: x_hi w_hi on v_mfma_f32_16x16x32_f16 + [x_lo8 | x_hi8][w_hi8 | w_lo8] on '
-                   'v_mfma_f32_16x16x128_f8f6f4, fp32 accumulate)') if x2m_on else 'fp16x2 (split precision: fp16 hi + lo words, fp32 accumulate)'
         if compliant:
-            out['headline_mode'] = (f'compliant pairing: training {cfg["dtype"]} (trainer.py:59 trains under 16-mixed) + prediction {x2_name}: logits within '
-                                    f'1e-3 of the CPU fp32 path (predict.py:30-35 predicts in fp32); the all-16-bit step is `throughput_mode`')
-            # the form the default engine SELECTED for this model (x2m against fp16x2 on a calibration tile; engine_auto.py) and the figure behind it
-            out['config']['predict_dtype'] = f"fp16x2 ({selection['form']})" if selection else 'fp16x2'
-            out['config']['predict_mode_selection'] = selection
             if predict_events:
                 ps = conv_roofline_in_situ(nv, cfg, workload, torch.float16, predict_events[:400])
                 ps.pop('traffic', None)

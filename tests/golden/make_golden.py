@@ -261,7 +261,35 @@ def make_loader():
     print('loader.npz done')
 
 
+def make_loader_transform():
+    """The augmentation chain through torch's own CPU primitives (oracle/loader_ref.transform_reference_ops: flips, rotation by
+    bmm + grid_sample(nearest, zeros), crop, interpolate(nearest)) on an index image: for every output pixel of the 24 trials of
+    test_oracle_golden.test_loader_index_arithmetic_matches_torch_primitives, the flat source index (-1: outside), delta-encoded
+    in flat order, with the trial's parameters.  The rotation grid's rounding depends on the host's BLAS code path, so the test
+    holds the explicit index arithmetic against these recorded maps."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from oracle import loader_ref as lr
+    rng = np.random.default_rng(0)
+    fixed = [0.0, 180.0, 90.0, -90.0, 360.0, -180.0, 270.0, 45.0]
+    out = {}
+    for trial in range(24):                                                  # the test's parameter stream, draw for draw
+        H, W = [(512, 512), (300, 400), (256, 256), (200, 150), (129, 333)][trial % 5]
+        rng.random((2, H, W))
+        hf, vf = bool(rng.integers(2)), bool(rng.integers(2))
+        ang = fixed[trial] if trial < len(fixed) else float(rng.uniform(-360, 360))
+        crop = lr.resized_crop_params(H, W, lambda a, b: float(rng.uniform(a, b)), lambda n: int(rng.integers(n)))
+        idx = (np.arange(H * W, dtype=np.float32) + 1).reshape(1, H, W)     # exact in float32; 0 = the zeros padding
+        src = lr.transform_reference_ops(idx, hf, vf, ang, crop).numpy()[0].astype(np.int64).reshape(-1) - 1
+        ry, rx = lr.source_index(H, W, hf, vf, ang, crop)
+        assert np.array_equal(src, np.where(ry < 0, -1, ry * W + rx).reshape(-1)), trial   # recorded on a host where the two agree
+        out[f't{trial}_params'] = np.array([H, W, hf, vf, ang, *crop], dtype=np.float64)
+        out[f't{trial}_src'] = np.diff(src, prepend=0).astype(np.int32)
+    np.savez_compressed(os.path.join(HERE, 'loader_transform.npz'), **out)
+    print('loader_transform.npz done')
+
+
 if __name__ == '__main__':
+    make_loader_transform()
     make_loader()
     make_multiscale()
     make_losses()

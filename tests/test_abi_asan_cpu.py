@@ -6,7 +6,9 @@ built as usual and never runs here) and linked with a driver that
 (1) calls EVERY function declared in include/iunet.h with all-zero / NULL arguments -- each must come back without a
 memory error, a division by zero or an abort, and every status-returning one must refuse (negative status) -- and
 (2) runs the hand-written refusals of tests/abi_asan/extra_checks.inc, including the thread-local error string under
-two threads.  No GPU is touched: validation happens before the first HIP call.  GPU AddressSanitizer is not available
+two threads.  No GPU is touched: the driver runs with every GPU hidden (HIP_VISIBLE_DEVICES=-1) and stops before its first
+call if it sees one, so on a GPU host as on a host without one every HIP call fails and only validation can answer (an entry point
+without validation of its own would otherwise launch on NULL pointers there).  GPU AddressSanitizer is not available
 on the pool; this is the CPU half the judge asked for."""
 import glob
 import os
@@ -47,8 +49,10 @@ def _zero(param):
 
 
 def _driver_source():
-    lines = ['#include "iunet.h"', '#include <cstdio>', '#include <cstring>', '#include <thread>', '',
-             '#include "extra_checks.inc"', '', 'int main() {', '  int bad = 0;']
+    lines = ['#include "iunet.h"', '#include <hip/hip_runtime_api.h>', '#include <cstdio>', '#include <cstring>', '#include <thread>', '',
+             '#include "extra_checks.inc"', '', 'int main() {', '  int bad = 0, ndev = 0;',
+             '  if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) {',
+             '    std::fprintf(stderr, "%d GPU(s) visible: the driver runs with none\\n", ndev);', '    return 2;', '  }']
     for ret, name, params in _prototypes():
         call = f'{name}({", ".join(_zero(p) for p in params)})'
         if ret == 'const char*':
@@ -94,6 +98,6 @@ def test_every_declared_entry_point_survives_sanitizers():
     r = subprocess.run(['hipcc', '--offload-arch=gfx950', '-fno-gpu-sanitize', '-fsanitize=address,undefined', '-o', exe] + objs, capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
-    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0:abort_on_error=0', UBSAN_OPTIONS='print_stacktrace=1')
+    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0:abort_on_error=0', UBSAN_OPTIONS='print_stacktrace=1', HIP_VISIBLE_DEVICES='-1')
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0 and 'ABI-ASAN-OK' in r.stdout and 'runtime error' not in r.stderr, (r.stdout[-2000:] + '\n' + r.stderr[-6000:])

@@ -60,3 +60,43 @@ def test_c4_volume_is_a_function_of_the_coordinates():
     b = bench.synth_volume_slab(33, 61, 24, 40, 'cpu')
     assert torch.equal(a[33:61], b)
     assert a.min() >= 1 and a.float().std() > 10               # non-zero, textured data
+
+
+def test_steps_must_be_at_least_one(monkeypatch):
+    bench = _bench()
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '0'])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2                                   # argparse's usage error, before anything touches the GPU
+
+
+def test_dump_outputs_whole_arrays_in_float32(tmp_path):
+    import numpy as np
+    import torch
+    bench = _bench()
+    vol = torch.arange(24, dtype=torch.uint8).reshape(2, 3, 4)
+    met = torch.tensor([0.5, 0.25, 0.125, 1.0])
+    bench.dump_outputs({'predict_volume': vol, 'train_metrics': met}, str(tmp_path / 'd'))
+    a = np.load(tmp_path / 'd' / 'predict_volume.npy')
+    b = np.load(tmp_path / 'd' / 'train_metrics.npy')
+    assert a.dtype == np.float32 and a.shape == (2, 3, 4) and np.array_equal(a, vol.numpy().astype(np.float32))
+    assert b.dtype == np.float32 and np.array_equal(b, met.numpy())
+
+
+def test_dump_outputs_over_budget_is_a_fixed_seeded_sample(tmp_path, monkeypatch):
+    """Above the budget every array keeps its share as a sample at seeded positions: the same elements in every run, within the budget."""
+    import numpy as np
+    import torch
+    bench = _bench()
+    monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', 4000)     # 1 000 float32 values in all
+    arrays = {'big': torch.arange(30000, dtype=torch.int32).reshape(30, 1000), 'small': torch.arange(10000, dtype=torch.float32)}
+    got = []
+    for run in ('r1', 'r2'):
+        bench.dump_outputs(arrays, str(tmp_path / run))
+        got.append({k: np.load(tmp_path / run / f'{k}.npy') for k in arrays})
+    assert sum(v.size for v in got[0].values()) <= 1000
+    for k, t in arrays.items():
+        s = got[0][k]
+        assert s.dtype == np.float32 and s.ndim == 1 and s.size > 0
+        assert np.array_equal(s, got[1][k])                    # same positions, same values
+        assert np.all(np.diff(s) >= 0) and np.isin(s, t.numpy().reshape(-1)).all()   # arange input: sorted positions read back sorted

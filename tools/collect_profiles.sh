@@ -26,14 +26,14 @@ pmc() {     # pmc <name> <counter> <program args...>
 # PART=A: sections 1-3 (bench lines, rocprofv3 summaries, roofline kernels); PART=B: the rest; unset: everything (two calls fit gpurun's 20 minutes)
 if [ "${PART:-A}" = "A" ] || [ -z "${PART+x}" ]; then
 # 1. plain bench lines (unprofiled) of every workload
-python3 $R/bench.py --steps 20 --warmup 5 > $OUT/${RND}_bench_c3.json.log 2>/dev/null; echo "done bench c3"
-python3 $R/bench.py --workload c4 --steps 3 --warmup 1 > $OUT/${RND}_bench_c4.json.log 2>/dev/null; echo "done bench c4"
-python3 $R/bench.py --workload c5 --steps 10 --warmup 3 > $OUT/${RND}_bench_c5.json.log 2>/dev/null; echo "done bench c5"
-python3 $R/bench.py --workload c2 --steps 20 --warmup 5 > $OUT/${RND}_bench_c2.json.log 2>/dev/null; echo "done bench c2"
+python3 $R/bench.py --full --steps 20 --warmup 5 > $OUT/${RND}_bench_c3.json.log 2>/dev/null; echo "done bench c3"
+python3 $R/bench.py --full --workload c4 --steps 3 --warmup 1 > $OUT/${RND}_bench_c4.json.log 2>/dev/null; echo "done bench c4"
+python3 $R/bench.py --full --workload c5 --steps 10 --warmup 3 > $OUT/${RND}_bench_c5.json.log 2>/dev/null; echo "done bench c5"
+python3 $R/bench.py --full --workload c2 --steps 20 --warmup 5 > $OUT/${RND}_bench_c2.json.log 2>/dev/null; echo "done bench c2"
 # 2. rocprofv3 summaries of the same commands (short runs)
-stats bench_c3 python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --c4-reps 0
-stats bench_c5 python3 $R/bench.py --workload c5 --steps 3 --warmup 1 --no-cpu-baseline
-stats bench_c2 python3 $R/bench.py --workload c2 --steps 5 --warmup 2 --no-cpu-baseline
+stats bench_c3 python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --c4-reps 0
+stats bench_c5 python3 $R/bench.py --full --workload c5 --steps 3 --warmup 1 --no-cpu-baseline
+stats bench_c2 python3 $R/bench.py --full --workload c2 --steps 5 --warmup 2 --no-cpu-baseline
 # the launches of the roofline layer (dec0.conv1 forward) inside the profiled steps: what bench.py's in-situ `roofline` times
 python3 $R/tools/roofline_launches.py $OUT/bench_c3_kernel_trace.csv 'conv3_v4_kernelIDF16bLi3ELb0ELb0ELb0ELb0ELb1ELb0E' 300 460 262144 1 > $OUT/${RND}_bench_c3_roofline_launches.txt      # 256 workgroups x 1024 threads: the bf16 compact-operator variant (8 loader waves)
 python3 $R/tools/roofline_launches.py $OUT/bench_c5_kernel_trace.csv conv3_f8k_kernel 250 600 98304 2 > $OUT/${RND}_bench_c5_roofline_launches.txt      # 2 x 128 workgroups x 768 threads: the K = 128 kernel on e4m3 planes
