@@ -476,6 +476,15 @@ int iunet_bn_relu_bwd(int dtype, const void* dz, long long dz_ss, const void* z,
                       long long y_ss, void* dy, long long dy_ss, const void* mean, const void* invstd, const void* gamma,
                       const void* scale, const void* shift, void* dgamma, void* dbeta, void* slab, void* coef, int C, int N,
                       long long vox, void* stream);
+/* U-Net++: the same backward with the upstream gradient a sum dz = srcs[0] + ... + srcs[K-1] (K = 1..8 NHWC8c tensors of the
+ * activation dtype, source k at srcs[k] with sample stride src_ss[k]) plus, when dpool is non-NULL, the max-pool route of dpool as in
+ * iunet_bn_relu_pool_bwd.  The sum is taken in fp32 in source order, rounded once to the activation dtype and never written; z is
+ * recomputed from y.  (D, H, W) is y's grid.  slab / coef as iunet_bn_relu_bwd; dy NULL (no dpool): sums and coefficients only.
+ * K = 1: the bits of iunet_bn_relu_bwd (z NULL) / iunet_bn_relu_pool_bwd. */
+int iunet_bn_relu_sum_bwd(int dtype, int nd, int K, const void* const* srcs, const long long* src_ss, const void* dpool,
+                          long long dp_ss, const void* y, long long y_ss, void* dy, long long dy_ss, const void* mean,
+                          const void* invstd, const void* gamma, const void* scale, const void* shift, void* dgamma, void* dbeta,
+                          void* slab, void* coef, int C, int N, int D, int H, int W, void* stream);
 /* The first pass of iunet_bn_relu_bwd folded into the data-gradient launch that produces dz.  iunet_conv3_dgrad_bnstats =
  * iunet_conv3_fwd (layout 2, epi 0) on the data-gradient operator, whose epilogue also reads yp (the raw output of the layer the
  * gradient flows into, z = relu(bn(yp))) and writes per-workgroup rows of (sum dz', sum dz' * xhat) to stats

@@ -1291,6 +1291,190 @@ __global__ void head_grad_scatter_kernel(const float* __restrict__ t, float* __r
   }
 }
 
+// ------------------------------------------------------------------ BatchNorm + ReLU backward with a summed upstream gradient (U-Net++)
+// In the nested network a stage output feeds every later node of its level and the transposed conv above it: its gradient is a sum
+// of up to 8 NHWC8c tensors (slot slices of the consumers' data gradients).  The sum is formed in fp32 in source order while the two
+// passes read, rounded once to T (the value a materialised dz tensor would hold), and never written.  The kernels below are
+// bn_bwd_reduce_kernel / bn_bwd_apply_kernel (z = NULL) and bn_pool_bwd_kernel with that sum in place of their single dz load, line
+// for line: with one source they give the same bits.
+struct SumSrcs {
+  static constexpr int MAX = 8;
+  const void* p[MAX];          // source k: sample n, element e at p[k] + n * ss[k] + e (in T elements)
+  long long ss[MAX];
+  int k;                       // 1 .. MAX
+};
+
+// acc[j] = sum_k src_k[n * ss_k + off + j] in fp32, k in order
+template <typename T>
+__device__ __forceinline__ void sum_srcs(const SumSrcs& s, int n, long long off, float (&acc)[8]) {
+  const V8T<T> g0 = *(const V8T<T>*)((const T*)s.p[0] + n * s.ss[0] + off);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = to_f32<T>(g0[j]);
+#pragma unroll
+  for (int k = 1; k < SumSrcs::MAX; ++k) {
+    if (k >= s.k) break;
+    const V8T<T> g = *(const V8T<T>*)((const T*)s.p[k] + n * s.ss[k] + off);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] += to_f32<T>(g[j]);
+  }
+}
+
+// pass 1 (bn_bwd_reduce_kernel): grid (chunks, planes, N); slab [(n*chunks + chunk)][C][2]
+template <typename T>
+__global__ __launch_bounds__(256) void bn_sum_bwd_reduce_kernel(SumSrcs src, const T* __restrict__ y, long long y_ss,
+                                                                const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                int C, long long vox, int per_block, float* __restrict__ slab) {
+  const int pl = blockIdx.y, n = blockIdx.z;
+  const long long v0 = (long long)blockIdx.x * per_block;
+  const long long v1 = min(v0 + per_block, vox);
+  float s1[8], s2[8], mu[8], is[8], sc[8], sh[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int c = pl * 8 + j;
+    s1[j] = 0.f; s2[j] = 0.f; mu[j] = mean[c]; is[j] = invstd[c];
+    sc[j] = scale[c]; sh[j] = shift[c];
+  }
+  const long long po = (long long)pl * vox * 8;
+#pragma unroll 4
+  for (long long v = v0 + threadIdx.x; v < v1; v += 256) {
+    float g[8];
+    sum_srcs<T>(src, n, po + v * 8, g);
+    const V8T<T> yy = *(const V8T<T>*)(y + n * y_ss + po + v * 8);
+    V8T<T> zz;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) zz[j] = from_f32<T>(fmaf(sc[j], to_f32<T>(yy[j]), sh[j]));
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float d = to_f32<T>(zz[j]) > 0.f ? to_f32<T>(from_f32<T>(g[j])) : 0.f;
+      s1[j] += d;
+      s2[j] += d * (to_f32<T>(yy[j]) - mu[j]) * is[j];
+    }
+  }
+  __shared__ float red[4 * 16];
+  const long long part = (long long)n * gridDim.x + blockIdx.x;
+  float vals[16];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { vals[2 * j] = s1[j]; vals[2 * j + 1] = s2[j]; }
+  block_reduce_store<16>(vals, red, slab + (part * C + pl * 8) * 2);
+}
+
+// pass 2 (bn_bwd_apply_kernel): dy = a (dz' - c1 - xhat c2); grid (vox / 512, planes, N), two items per thread
+template <typename T>
+__global__ __launch_bounds__(256) void bn_sum_bwd_apply_kernel(SumSrcs src, const T* __restrict__ y, long long y_ss,
+                                                               T* __restrict__ dy, long long dy_ss, const float* __restrict__ mean,
+                                                               const float* __restrict__ invstd, const float* __restrict__ coef,
+                                                               const float* __restrict__ scale, const float* __restrict__ shift,
+                                                               long long vox) {
+  const int pl = blockIdx.y, n = blockIdx.z;
+  const long long v0 = (long long)blockIdx.x * 512 + threadIdx.x;
+  float mu[8], is[8], ca[8], c1[8], c2[8], sc[8], sh[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int c = pl * 8 + j;
+    mu[j] = mean[c]; is[j] = invstd[c]; ca[j] = coef[c * 3]; c1[j] = coef[c * 3 + 1]; c2[j] = coef[c * 3 + 2];
+    sc[j] = scale[c]; sh[j] = shift[c];
+  }
+  const long long base = (long long)pl * vox * 8;
+  float g[2][8];
+  V8T<T> yy[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const long long v = v0 + u * 256;
+    if (v < vox) {
+      sum_srcs<T>(src, n, base + v * 8, g[u]);
+      yy[u] = *(const V8T<T>*)(y + n * y_ss + base + v * 8);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const long long v = v0 + u * 256;
+    if (v >= vox) continue;
+    V8T<T> o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float yv = to_f32<T>(yy[u][j]);
+      const float zv = to_f32<T>(from_f32<T>(fmaf(sc[j], yv, sh[j])));
+      const float d = zv > 0.f ? to_f32<T>(from_f32<T>(g[u][j])) : 0.f;
+      const float xh = (yv - mu[j]) * is[j];
+      o[j] = from_f32<T>(ca[j] * (d - c1[j] - xh * c2[j]));
+    }
+    *(V8T<T>*)(dy + n * dy_ss + base + v * 8) = o;
+  }
+}
+
+// both passes with the max-pool route of dpool added (bn_pool_bwd_kernel): dz = round_T(sum_k src_k + route(dpool)); one thread per
+// pooled voxel and channel plane
+template <typename T, int ND, int PASS>
+__global__ __launch_bounds__(256) void bn_sum_pool_bwd_kernel(SumSrcs src, const T* __restrict__ dpool, long long dp_ss,
+                                                              const T* __restrict__ y, long long y_ss, T* __restrict__ dy,
+                                                              long long dy_ss, const float* __restrict__ mean,
+                                                              const float* __restrict__ invstd, const float* __restrict__ coef,
+                                                              const float* __restrict__ scale, const float* __restrict__ shift,
+                                                              int C, int Do, int Ho, int Wo, int per_block, float* __restrict__ slab) {
+  constexpr int NW = ND == 3 ? 8 : 4;
+  const int pl = blockIdx.y, n = blockIdx.z;
+  const long long ovox = (long long)Do * Ho * Wo;
+  const int Di = ND == 3 ? Do * 2 : 1, Hi = Ho * 2, Wi = Wo * 2;
+  const long long ipl = (long long)pl * Di * Hi * Wi * 8;
+  float mu[8], is[8], sc[8], sh[8], ca[8], c1[8], c2[8], s1[8], s2[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int c = pl * 8 + j;
+    mu[j] = mean[c]; is[j] = invstd[c]; sc[j] = scale[c]; sh[j] = shift[c]; s1[j] = 0.f; s2[j] = 0.f;
+    if (PASS == 2) { ca[j] = coef[c * 3]; c1[j] = coef[c * 3 + 1]; c2[j] = coef[c * 3 + 2]; }
+  }
+  const long long r0 = (long long)blockIdx.x * per_block, r1 = min(r0 + per_block, ovox);
+  for (long long r = r0 + threadIdx.x; r < r1; r += 256) {
+    const int ox = (int)(r % Wo), oy = (int)((r / Wo) % Ho), oz = (int)(r / ((long long)Wo * Ho));
+    V8T<T> yy[NW];
+    float gs[NW][8];
+    long long off[NW];
+#pragma unroll
+    for (int s = 0; s < NW; ++s) {
+      const int a = ND == 3 ? (s >> 2) : 0, b = (s >> 1) & 1, c = s & 1;
+      const int zz = ND == 3 ? oz * 2 + a : 0;
+      off[s] = ipl + (((long long)zz * Hi + oy * 2 + b) * Wi + ox * 2 + c) * 8;
+      yy[s] = *(const V8T<T>*)(y + n * y_ss + off[s]);
+      sum_srcs<T>(src, n, off[s], gs[s]);
+    }
+    const V8T<T> gp = *(const V8T<T>*)(dpool + n * dp_ss + (long long)pl * ovox * 8 + r * 8);
+    int best[8];
+    float zv[NW][8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float m = 0.f;
+#pragma unroll
+      for (int s = 0; s < NW; ++s) {
+        zv[s][j] = to_f32<T>(from_f32<T>(fmaxf(fmaf(sc[j], to_f32<T>(yy[s][j]), sh[j]), 0.f)));
+        if (s == 0) { m = zv[0][j]; best[j] = 0; } else if (zv[s][j] > m) { m = zv[s][j]; best[j] = s; }   // first maximum
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < NW; ++s) {
+      V8T<T> o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float dz = to_f32<T>(from_f32<T>(gs[s][j] + (best[j] == s ? to_f32<T>(gp[j]) : 0.f)));
+        const float d = zv[s][j] > 0.f ? dz : 0.f;
+        const float xh = (to_f32<T>(yy[s][j]) - mu[j]) * is[j];
+        if (PASS == 1) { s1[j] += d; s2[j] += d * xh; }
+        else o[j] = from_f32<T>(ca[j] * (d - c1[j] - xh * c2[j]));
+      }
+      if (PASS == 2) *(V8T<T>*)(dy + n * dy_ss + off[s]) = o;
+    }
+  }
+  if (PASS == 1) {
+    __shared__ float red[4 * 16];
+    const long long part = (long long)n * gridDim.x + blockIdx.x;
+    float vals[16];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { vals[2 * j] = s1[j]; vals[2 * j + 1] = s2[j]; }
+    block_reduce_store<16>(vals, red, slab + (part * C + pl * 8) * 2);
+  }
+}
+
+
 }  // namespace
 
 #define DT_OK(dt) IUNET_REQUIRE((dt) == 0 || (dt) == 1, "dtype must be 0 (f16) or 1 (bf16), got %d", (dt))
@@ -1842,6 +2026,74 @@ int iunet_adamw_step_dev(void* p, const void* g, void* m, void* v, long long n, 
   hipLaunchKernelGGL(adamw_dev_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, s, (float*)p, (const float*)g, (float*)m, (float*)v,
                      n, lr, b1, b2, eps, wd, (const float*)state);
   hipLaunchKernelGGL(train_state_update_kernel, dim3(1), dim3(1), 0, s, (float*)state);
+  IUNET_CHECK_HIP(hipGetLastError());
+  return IUNET_OK;
+}
+
+// Backward of z = relu(bn(y)) whose upstream gradient is dz = sum_k srcs[k] (+ route(dpool) when dpool is non-NULL): see SumSrcs.
+// (D, H, W) is y's grid; with dpool the pooled grid is (D/2 in 3-D, H/2, W/2).  slab: iunet_bn_bwd_num_parts(N, D*H*W) * C * 2
+// floats, coef: 3 C floats.  dy NULL (without dpool): sums and coefficients only.
+int iunet_bn_relu_sum_bwd(int dtype, int nd, int K, const void* const* srcs, const long long* src_ss, const void* dpool, long long dp_ss,
+                          const void* y, long long y_ss, void* dy, long long dy_ss, const void* mean, const void* invstd,
+                          const void* gamma, const void* scale, const void* shift, void* dgamma, void* dbeta, void* slab, void* coef,
+                          int C, int N, int D, int H, int W, void* stream) {
+  DT_OK(dtype);
+  IUNET_REQUIRE(nd == 2 || nd == 3, "bn_relu_sum_bwd: nd must be 2 or 3");
+  IUNET_REQUIRE(K >= 1 && K <= SumSrcs::MAX, "bn_relu_sum_bwd: 1 .. %d sources, got %d", SumSrcs::MAX, K);
+  IUNET_REQUIRE(srcs && src_ss && y && slab && coef && scale && shift && mean && invstd && gamma && dgamma && dbeta,
+                "bn_relu_sum_bwd: null pointer");
+  IUNET_REQUIRE(dy || !dpool, "bn_relu_sum_bwd: the pooled form needs dy");
+  IUNET_REQUIRE(C > 0 && C % 8 == 0 && N > 0 && D > 0 && H > 0 && W > 0 && (nd == 3 || D == 1),
+                "bn_relu_sum_bwd: C %d, N %d, %d x %d x %d", C, N, D, H, W);
+  const long long vox = (long long)D * H * W;
+  // 16-byte loads and stores: every base and sample stride on an 8-element boundary, each sample's C planes inside its stride
+  auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  SumSrcs s{};
+  s.k = K;
+  for (int k = 0; k < K; ++k) {
+    IUNET_REQUIRE(srcs[k] && al(srcs[k]) && src_ss[k] % 8 == 0 && src_ss[k] >= C * vox,
+                  "bn_relu_sum_bwd: source %d: pointer %p, sample stride %lld (C * vox = %lld)", k, srcs[k], src_ss[k], C * vox);
+    s.p[k] = srcs[k];
+    s.ss[k] = src_ss[k];
+  }
+  IUNET_REQUIRE(al(y) && y_ss % 8 == 0 && y_ss >= C * vox && (!dy || (al(dy) && dy_ss % 8 == 0 && dy_ss >= C * vox)),
+                "bn_relu_sum_bwd: y / dy alignment or sample stride");
+  if (dpool) {
+    IUNET_REQUIRE(H % 2 == 0 && W % 2 == 0 && (nd == 2 || D % 2 == 0), "bn_relu_sum_bwd: odd grid %d x %d x %d under a max-pool", D, H, W);
+    const int Do = nd == 3 ? D / 2 : 1, Ho = H / 2, Wo = W / 2;
+    const long long ovox = (long long)Do * Ho * Wo;
+    IUNET_REQUIRE(al(dpool) && dp_ss % 8 == 0 && dp_ss >= C * ovox, "bn_relu_sum_bwd: dpool alignment or sample stride");
+    const int per_block = BN_POOL_PER_BLOCK / (nd == 3 ? 8 : 4);
+    const int chunks = (int)((ovox + per_block - 1) / per_block);
+    dim3 g1(chunks, C / 8, N), g2((unsigned)((ovox + 255) / 256), C / 8, N);
+#define BSP(TT, NDV, PASSV, GRID, PB) hipLaunchKernelGGL((bn_sum_pool_bwd_kernel<TT, NDV, PASSV>), GRID, dim3(256), 0, (hipStream_t)stream, \
+    s, (const TT*)dpool, dp_ss, (const TT*)y, y_ss, (TT*)dy, dy_ss, (const float*)mean, (const float*)invstd, \
+    (const float*)coef, (const float*)scale, (const float*)shift, C, Do, Ho, Wo, PB, (float*)slab)
+    if (dtype == 0) { if (nd == 3) BSP(f16, 3, 1, g1, per_block); else BSP(f16, 2, 1, g1, per_block); }
+    else { if (nd == 3) BSP(bf16, 3, 1, g1, per_block); else BSP(bf16, 2, 1, g1, per_block); }
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, (const float*)slab, chunks * N, C,
+                       (double)N * (double)vox, (const float*)gamma, (const float*)invstd, (float*)dgamma, (float*)dbeta, (float*)coef);
+    if (dtype == 0) { if (nd == 3) BSP(f16, 3, 2, g2, 256); else BSP(f16, 2, 2, g2, 256); }
+    else { if (nd == 3) BSP(bf16, 3, 2, g2, 256); else BSP(bf16, 2, 2, g2, 256); }
+#undef BSP
+    IUNET_CHECK_HIP(hipGetLastError());
+    return IUNET_OK;
+  }
+  const int per_block = BN_BWD_PER_BLOCK;
+  const int chunks = (int)((vox + per_block - 1) / per_block);
+  dim3 g1(chunks, C / 8, N);
+#define BSR(TT) hipLaunchKernelGGL(bn_sum_bwd_reduce_kernel<TT>, g1, dim3(256), 0, (hipStream_t)stream, s, (const TT*)y, y_ss, \
+    (const float*)mean, (const float*)invstd, (const float*)scale, (const float*)shift, C, vox, per_block, (float*)slab)
+  if (dtype == 0) BSR(f16); else BSR(bf16);
+#undef BSR
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, (const float*)slab, chunks * N, C,
+                     (double)N * (double)vox, (const float*)gamma, (const float*)invstd, (float*)dgamma, (float*)dbeta, (float*)coef);
+  if (dy == nullptr) { IUNET_CHECK_HIP(hipGetLastError()); return IUNET_OK; }
+  dim3 g2((unsigned)((vox + 511) / 512), C / 8, N);
+#define BSA(TT) hipLaunchKernelGGL(bn_sum_bwd_apply_kernel<TT>, g2, dim3(256), 0, (hipStream_t)stream, s, (const TT*)y, y_ss, \
+    (TT*)dy, dy_ss, (const float*)mean, (const float*)invstd, (const float*)coef, (const float*)scale, (const float*)shift, vox)
+  if (dtype == 0) BSA(f16); else BSA(bf16);
+#undef BSA
   IUNET_CHECK_HIP(hipGetLastError());
   return IUNET_OK;
 }

@@ -220,7 +220,10 @@ def find_max_batch_size(model, input_size=256, start=4, max_limit=512):
     analytically, so answer from free HBM instead (same return contract: a power-of-two batch)."""
     eng = model.engine('eval')
     free, _ = torch.cuda.mem_get_info(model.device)
-    per_slice = 2 * input_size * input_size * sum(5 * c // (4 ** l) for l, c in enumerate(eng.ch)) * 2
+    if hasattr(eng, 'bytes_per_slice'):        # U-Net++: its own workspace (level buffers of up to L slots)
+        per_slice = eng.bytes_per_slice(input_size)
+    else:
+        per_slice = 2 * input_size * input_size * sum(5 * c // (4 ** l) for l, c in enumerate(eng.ch)) * 2
     best = start
     while best * 2 <= max_limit and best * 2 * per_slice < 0.5 * free:
         best *= 2

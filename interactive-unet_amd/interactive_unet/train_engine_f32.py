@@ -384,7 +384,11 @@ class TrainEngineF32:
 
 
 def make_train_engine(model, **kw):
-    """The training engine of a module: 16-bit activations (TrainEngine) or, for act_dtype='fp32', the fp32 parity form."""
+    """The training engine of a module: 16-bit activations (TrainEngine) or, for act_dtype='fp32', the fp32 parity form; U-Net++
+    modules train on train_engine_nested.NestedTrainEngine."""
+    if getattr(model, 'architecture', 'U-Net') == 'U-Net++':
+        from .train_engine_nested import NestedTrainEngine
+        return NestedTrainEngine(model, **kw)
     if model.act_dtype == torch.float32:
         kw.pop('loss_scale', None)
         return TrainEngineF32(model, **kw)

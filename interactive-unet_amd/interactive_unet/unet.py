@@ -3,8 +3,8 @@
 `.loss_function`, `.device`, `load_from_checkpoint(checkpoint_path=)`; the network itself is
 the native canonical U-Net (engine.py) instead of segmentation_models_pytorch.
 
-Only architecture='U-Net' exists natively; `encoder_name` is accepted and ignored (the canonical
-net has its own plain conv encoder), `pretrained` is a no-op with a warning (no imagenet
+architecture='U-Net' and 'U-Net++' (the canonical nested form: engine_nested.py, train_engine_nested.py) exist natively;
+`encoder_name` is accepted and ignored (the canonical nets have their own plain conv encoder), `pretrained` is a no-op with a warning (no imagenet
 weights for a from-scratch encoder; no network access).  Extra keyword arguments (dim, levels,
 base, act_dtype, infer_dtype) select the 3-D / wider variants of BASELINE.json's configs.
 
@@ -35,8 +35,22 @@ _ACT = {'fp16': torch.float16, 'f16': torch.float16, 'bf16': torch.bfloat16, 'fp
 _ACT_NAME = {torch.float16: 'fp16', torch.bfloat16: 'bf16', torch.float32: 'fp32', X2: X2}
 
 
-def param_shapes(dim=2, levels=4, base=32, cin=1, ncls=2):
-    """Ordered {name: shape} of the canonical network (same names as the oracle's definition)."""
+NESTED = 'U-Net++'
+ARCHITECTURES = ('U-Net', NESTED)
+
+
+def nested_nodes(levels):
+    """The decoder nodes X^{i,j} (j >= 1, i + j <= L - 1) of the nested network in forward (topological) order: by column j,
+    then level i.  Node (i, j) reads X^{i,0..j-1} and up(X^{i+1,j-1}); its parameters are `dec{i}_{j}.*`."""
+    return [(i, j) for j in range(1, levels) for i in range(levels - j)]
+
+
+def param_shapes(dim=2, levels=4, base=32, cin=1, ncls=2, architecture='U-Net'):
+    """Ordered {name: shape} of the canonical network (same names as the oracle's definition).  architecture='U-Net++': the
+    nested form (Zhou et al. 2018) on the same stage -- the encoder `enc{i}`, then `dec{i}_{j}` in nested_nodes order, each with
+    its transposed conv ch[i+1] -> ch[i] and a stage (j + 1) ch[i] -> ch[i]."""
+    if architecture not in ARCHITECTURES:
+        raise NotImplementedError(f'architecture {architecture!r}: the native networks are {ARCHITECTURES}')
     ch = [base * 2 ** l for l in range(levels)]
     k3, k2, k1 = (3,) * dim, (2,) * dim, (1,) * dim
     shapes = {}
@@ -48,13 +62,38 @@ def param_shapes(dim=2, levels=4, base=32, cin=1, ncls=2):
                 shapes[f'{prefix}.bn{j}.{k}'] = (b,)
     for l in range(levels):
         stage(f'enc{l}', cin if l == 0 else ch[l - 1], ch[l])
-    for l in range(levels - 2, -1, -1):
-        shapes[f'dec{l}.up.weight'] = (ch[l + 1], ch[l]) + k2
-        shapes[f'dec{l}.up.bias'] = (ch[l],)
-        stage(f'dec{l}', 2 * ch[l], ch[l])
+    if architecture == NESTED:
+        for i, j in nested_nodes(levels):
+            shapes[f'dec{i}_{j}.up.weight'] = (ch[i + 1], ch[i]) + k2
+            shapes[f'dec{i}_{j}.up.bias'] = (ch[i],)
+            stage(f'dec{i}_{j}', (j + 1) * ch[i], ch[i])
+    else:
+        for l in range(levels - 2, -1, -1):
+            shapes[f'dec{l}.up.weight'] = (ch[l + 1], ch[l]) + k2
+            shapes[f'dec{l}.up.bias'] = (ch[l],)
+            stage(f'dec{l}', 2 * ch[l], ch[l])
     shapes['head.weight'] = (ncls, ch[0]) + k1
     shapes['head.bias'] = (ncls,)
     return shapes
+
+
+def _check_nested(levels, act_dtype, weight_dtype, norm, infer_dtype, infer_policy):
+    """The combinations the native U-Net++ supports: BatchNorm, 16-bit training (fp16 / bf16), prediction in fp32 (default) or
+    fp16 / bf16, 2 .. 9 levels (a stage output has at most 8 summed gradient sources)."""
+    what = ("U-Net++ supports norm='batch', act_dtype None / 'fp16' / 'bf16' (training), infer_dtype None / 'fp32' / 'fp16' / "
+            "'bf16' (prediction) and 2 .. 9 levels")
+    if norm != 'batch':
+        raise NotImplementedError(f'U-Net++ with norm={norm!r} (GroupNorm): {what}')
+    if weight_dtype is not None:
+        raise NotImplementedError(f'U-Net++ with weight_dtype={weight_dtype!r} (fp8 weights): {what}')
+    if act_dtype is not None and _ACT.get(act_dtype) not in (torch.float16, torch.bfloat16):
+        raise NotImplementedError(f'U-Net++ with act_dtype={act_dtype!r} (the fp32 training form / split precision): {what}')
+    if infer_dtype is not None and _ACT.get(infer_dtype) not in (torch.float32, torch.float16, torch.bfloat16):
+        raise NotImplementedError(f'U-Net++ with infer_dtype={infer_dtype!r} (split precision): {what}')
+    if infer_policy is not None:
+        raise NotImplementedError(f'U-Net++ with infer_policy={infer_policy!r} (split-precision forms): {what}')
+    if not (2 <= levels <= 9):
+        raise NotImplementedError(f'U-Net++ with {levels} levels: {what}')
 
 
 def _is_buffer(name):
@@ -94,9 +133,11 @@ class UNet(nn.Module):
                  dim=2, levels=4, base=32, act_dtype=None, weight_dtype=None, norm='batch', groups=8, infer_dtype=None,
                  act_quant=None, infer_policy=None):
         super().__init__()
-        if architecture != 'U-Net':
-            raise NotImplementedError(f"architecture {architecture!r}: only 'U-Net' has a native MI355X "
+        if architecture not in ARCHITECTURES:
+            raise NotImplementedError(f"architecture {architecture!r}: only 'U-Net' and 'U-Net++' have a native MI355X "
                                       f"implementation (the reference builds the others through smp, unet.py:33-54)")
+        if architecture == NESTED:
+            _check_nested(levels, act_dtype, weight_dtype, norm, infer_dtype, infer_policy)
         if pretrained:
             warnings.warn('pretrained=True ignored: the native U-Net encoder is trained from scratch')
         self.hparams = dict(lr=lr, num_channels=num_channels, num_classes=num_classes,
@@ -113,9 +154,12 @@ class UNet(nn.Module):
         self.num_channels, self.num_classes = num_channels, num_classes
         # act_dtype None = the reference's pair: 16-bit training (trainer.py:59) + tolerance-meeting prediction (predict.py:30-35);
         # fp8-weight networks predict in their own mode
+        self.architecture = architecture
         self.act_dtype = torch.float16 if act_dtype is None else _ACT[act_dtype]
         if infer_dtype is not None:
             self.infer_dtype = _ACT[infer_dtype]
+        elif architecture == NESTED:
+            self.infer_dtype = torch.float32   # the nested net predicts in the fp32 form (within 1e-3 of the CPU fp32 logits)
         elif act_dtype is None and weight_dtype is None:
             self.infer_dtype = X2              # (GroupNorm networks too: engine_auto runs them in the full fp16x2 form)
         else:
@@ -133,7 +177,7 @@ class UNet(nn.Module):
             raise ValueError("norm must be 'batch' or 'group'")
         self.norm, self.groups = norm, groups
         self._names = []
-        for name, shp in param_shapes(dim, levels, base, num_channels, num_classes).items():
+        for name, shp in param_shapes(dim, levels, base, num_channels, num_classes, architecture).items():
             t = torch.empty(shp, dtype=torch.float32)
             key = name.replace('.', '__')
             if _is_buffer(name):
@@ -197,6 +241,14 @@ class UNet(nn.Module):
             raise RuntimeError('the native U-Net runs on the GPU only: move the module with .to("cuda") '
                                '(there is no CPU fallback)')
         eng = self._engines.get(dev)
+        if eng is None and self.architecture == NESTED:
+            from .engine_nested import NestedEngine, NestedEngineF32
+            if self.infer_dtype == torch.float32:
+                eng = NestedEngineF32(self.dim, self.levels, self.base, self.num_channels, self.num_classes, dev)
+            else:
+                eng = NestedEngine(self.dim, self.levels, self.base, self.num_channels, self.num_classes, self.infer_dtype, dev)
+            self._engines = {dev: eng}
+            self._packed_sig = None
         if eng is None:
             if self.infer_dtype in (torch.float32, X2):
                 if self.weight_dtype is not None:
