@@ -308,6 +308,10 @@ int iunet_net_create(int dim, int levels, int base, int cin, int ncls, int mode,
  * folds: a stage conv writes its raw output, iunet_x2_gn_relu_fwd normalises it with per-(sample, group) statistics taken in double; the
  * bn{j}.weight / .bias tensors of the flat vector are the affine pair, the running statistics are unused) */
 int iunet_net_create_ex(int dim, int levels, int base, int cin, int ncls, int mode, float act_scale, int norm, int groups, iunet_net** out);
+/* U-Net++ forward (unet.param_shapes(..., architecture='U-Net++'): the encoder enc{i}, then the nodes dec{i}_{j} in unet.nested_nodes
+ * order, then the head; BatchNorm folded): modes 0 / 1 (16-bit) only -- modes 2 / 3 are refused, as the Python constructor refuses them;
+ * 2..9 levels.  Every other iunet_net_* entry point takes the handle unchanged (engine_nested.NestedEngine sequences the same launches). */
+int iunet_net_create_nested(int dim, int levels, int base, int cin, int ncls, int mode, iunet_net** out);
 void iunet_net_destroy(iunet_net* net);
 /* the flat fp32 parameter vector: trainable tensors and BatchNorm running statistics in the canonical order (the state_dict keys of
  * interactive_unet/unet.py: enc{l}.conv{j}.weight [Cout][Cin][3^d], enc{l}.bn{j}.{weight,bias,running_mean,running_var},
@@ -685,6 +689,12 @@ int iunet_train_create(int dim, int levels, int base, int cin, int ncls, int dty
  * statistics per (sample, group), the same at training and inference: the running-statistics pointers of iunet_train_bind are accepted and
  * left alone; train_engine.TrainEngine on a UNet(norm='group') sequences the same launches) */
 int iunet_train_create_ex(int dim, int levels, int base, int cin, int ncls, int dtype, int loss_kind, int norm, int groups, iunet_train** out);
+/* U-Net++ (unet.param_shapes(..., architecture='U-Net++')): BatchNorm, 2..9 levels, dtype 0 fp16 / 1 bf16.  iunet_train_param lists the
+ * trainable tensors in that order, iunet_train_num_bn counts the BatchNorms enc0.bn1, .., enc{L-1}.bn2, then dec{i}_{j}.bn1 / .bn2 in node
+ * order; every other iunet_train_* entry point takes the handle unchanged (train_engine_nested.NestedTrainEngine sequences the same
+ * launches).  The hooks of iunet_train_forward_backward_hooks: stage 0 when every dec{i}_{j} and the head's gradients are final, stage 1
+ * when the bottom encoder level's are. */
+int iunet_train_create_nested(int dim, int levels, int base, int cin, int ncls, int dtype, int loss_kind, iunet_train** out);
 void iunet_train_destroy(iunet_train* t);
 long long iunet_train_num_params(const iunet_train* t);
 int iunet_train_num_tensors(const iunet_train* t);

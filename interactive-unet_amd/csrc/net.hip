@@ -113,6 +113,9 @@ struct iunet_net {
   long long nparams = 0;
   std::vector<ConvOp> conv;           // enc0.conv1, enc0.conv2, ..., dec{L-2}.conv1, ... in stage order
   std::vector<UpOp> up;               // dec{L-2}.up ... dec0.up
+  // U-Net++ (iunet_net_create_nested, modes 0 / 1): conv / up hold the nodes dec{i}_{j} after the encoder, in unet.nested_nodes order
+  bool nested = false;
+  std::vector<std::pair<int, int>> nodes;
   long long head_w = 0, head_b = 0;
   long long packed_bytes = 0, scratch_off = 0;
   const float* flat = nullptr;        // set by iunet_net_load
@@ -135,6 +138,19 @@ WsLayout ws_layout(const iunet_net* n, int N, int D, int H, int W) {
   auto take = [&](long long elems) { const long long o = off; off = align256(off + elems * 2); return o; };
   L.a.resize(lv); L.b.resize(lv); L.cat.resize(lv, -1); L.pin.resize(lv, -1);
   L.am.resize(lv, -1); L.catm.resize(lv, -1); L.pinm.resize(lv, -1);
+  if (n->nested) {
+    // engine_nested._level_bufs: cat[l] = the level buffer [X^{l,0} | X^{l,1} | ..] (L - l slots), a[l] = conv1's output, pin[l], b[0] = the head's input
+    for (int l = 0; l < lv; ++l) {
+      const long long v = (long long)(n->dim == 3 ? D >> l : 1) * (H >> l) * (W >> l);
+      L.cat[l] = take((long long)N * (lv - l) * n->ch[l] * v);
+      L.a[l] = take((long long)N * n->ch[l] * v);
+      L.b[l] = -1;
+      if (l > 0) L.pin[l] = take((long long)N * n->ch[l - 1] * v);
+    }
+    L.b[0] = take((long long)N * n->ch[0] * (n->dim == 3 ? D : 1) * H * W);
+    L.bytes = off;
+    return L;
+  }
   if (n->mode == 3) {
     for (int l = 0; l < lv; ++l) {
       const long long v = (long long)(n->dim == 3 ? D >> l : 1) * (H >> l) * (W >> l);
@@ -169,6 +185,81 @@ WsLayout ws_layout(const iunet_net* n, int N, int D, int H, int W) {
   return L;
 }
 
+// one 16-bit stage conv on the layout engine.Engine._conv3 picks (the U-Net path of iunet_net_forward)
+int conv16(const iunet_net* n, const ConvOp& op, const void* xp, long long x_ss, void* yp, long long y_ss, int N, int d, int h, int w, void* stream) {
+  const float* aux = (const float*)(n->packed + op.aux);
+  int lay = 1;
+  if (op.pk[3] >= 0 && iunet_conv3_compact_ok(n->dim, N, d, h, w, op.ci, op.co, 0, 0)) lay = 3;
+  else {
+    lay = iunet_conv3_pick_layout(n->dim, N, d, h, w, op.ci, op.co);
+    if (lay == 0 && op.pk[0] < 0) lay = 1;
+  }
+  return iunet_conv3_fwd(n->mode, n->dim, xp, x_ss, yp, y_ss, n->packed + op.pk[lay == 2 ? 1 : lay], aux + op.co, nullptr, N, d, h, w, op.ci, op.co, 2, lay,
+                         stream);
+}
+
+// the U-Net++ forward of engine_nested.NestedEngine.infer (modes 0 / 1): the encoder writes X^{l,0} into slot 0 of its level buffer
+// and max-pools it, node (i, j)'s transposed conv writes up(X^{i+1,j-1}) into slot j, conv1 reads slots 0..j, conv2 overwrites slot j
+// (the last node: b[0], the head's input)
+int nested_forward(const iunet_net* n, const WsLayout& L, const void* x, int in_dtype, const long long* in_strides, int N, int D, int H, int W,
+                   unsigned char* WS, void* logits, void* probs, void* cls, const long long* out_strides, float divisor, int accumulate, void* stream) {
+  const int lv = n->levels, dim = n->dim, mode = n->mode;
+  unsigned char* K = n->packed;
+  auto dims = [&](int l, int& d, int& h, int& w) { d = dim == 3 ? D >> l : 1; h = H >> l; w = W >> l; };
+  auto vox = [&](int l) { int d, h, w; dims(l, d, h, w); return (long long)d * h * w; };
+  int rc = 0;
+  for (int l = 0; l < lv; ++l) {
+    int d, h, w;
+    dims(l, d, h, w);
+    const long long v = vox(l), x0_ss = (long long)(lv - l) * n->ch[l] * v;
+    const int c = n->ch[l];
+    const ConvOp& c1 = n->conv[2 * l];
+    const ConvOp& c2 = n->conv[2 * l + 1];
+    if (l == 0) {
+      const float* aux = (const float*)(K + c1.aux);
+      rc = iunet_first_conv_fwd(mode, dim, x, in_dtype, in_strides, WS + L.a[0], (long long)c * v, K + c1.pk[1], aux + c, nullptr, N, d, h, w, n->cin, c, 1, stream);
+    } else {
+      rc = conv16(n, c1, WS + L.pin[l], (long long)n->ch[l - 1] * v, WS + L.a[l], (long long)c * v, N, d, h, w, stream);
+    }
+    if (rc) return rc;
+    rc = conv16(n, c2, WS + L.a[l], (long long)c * v, WS + L.cat[l], x0_ss, N, d, h, w, stream);
+    if (rc) return rc;
+    if (l < lv - 1) {
+      int dn, hn, wn;
+      dims(l + 1, dn, hn, wn);
+      rc = iunet_maxpool_fwd(mode, dim, WS + L.cat[l], x0_ss, WS + L.pin[l + 1], (long long)c * vox(l + 1), c, N, dn, hn, wn, stream);
+      if (rc) return rc;
+    }
+  }
+  for (size_t k = 0; k < n->nodes.size(); ++k) {
+    const int i = n->nodes[k].first, j = n->nodes[k].second;
+    int d, h, w, di, hi, wi;
+    dims(i, d, h, w);
+    dims(i + 1, di, hi, wi);
+    const long long v = vox(i), vi = vox(i + 1);
+    const int c = n->ch[i], cn = n->ch[i + 1];
+    const long long cat_ss = (long long)(lv - i) * c * v;
+    unsigned char* up = WS + L.cat[i] + (long long)j * c * v * 2;
+    const UpOp& u = n->up[k];
+    rc = iunet_convT_fwd(mode, dim, WS + L.cat[i + 1] + (long long)(j - 1) * cn * vi * 2, (long long)(lv - i - 1) * cn * vi, up, cat_ss, K + u.pk,
+                         n->flat + u.b, N, di, hi, wi, cn, c, stream);
+    if (rc) return rc;
+    const ConvOp& c1 = n->conv[2 * (lv + k)];
+    const ConvOp& c2 = n->conv[2 * (lv + k) + 1];
+    rc = conv16(n, c1, WS + L.cat[i], cat_ss, WS + L.a[i], (long long)c * v, N, d, h, w, stream);
+    if (rc) return rc;
+    const bool last = k + 1 == n->nodes.size();
+    rc = conv16(n, c2, WS + L.a[i], (long long)c * v, last ? WS + L.b[0] : up, last ? (long long)c * v : cat_ss, N, d, h, w, stream);
+    if (rc) return rc;
+  }
+  if (!logits && !probs && !cls) return IUNET_OK;
+  const long long v0 = vox(0);
+  const long long dflt[5] = {n->ncls * v0, v0, (long long)H * W, W, 1};
+  const int c0 = n->ch[0];
+  return iunet_head_fwd(mode, WS + L.b[0], (long long)c0 * v0, c0, n->flat + n->head_w, n->flat + n->head_b, n->ncls, logits, probs, cls,
+                        out_strides ? out_strides : dflt, divisor, accumulate, N, D, H, W, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -181,12 +272,22 @@ int iunet_net_create(int dim, int levels, int base, int cin, int ncls, int mode,
 }
 /* norm: 0 BatchNorm (eval-mode statistics folded into the operators), 1 GroupNorm(groups) + ReLU after every stage conv (north star
  * "GroupNorm/BN"; mode 2, the split-precision form GroupNorm networks predict in: engine_x2.EngineX2(norm='group')) */
+static int net_create(int dim, int levels, int base, int cin, int ncls, int mode, float act_scale, int norm, int groups, bool nested, iunet_net** out);
 int iunet_net_create_ex(int dim, int levels, int base, int cin, int ncls, int mode, float act_scale, int norm, int groups, iunet_net** out) {
+  return net_create(dim, levels, base, cin, ncls, mode, act_scale, norm, groups, false, out);
+}
+/* U-Net++ forward (engine_nested.NestedEngine, folded BatchNorm): modes 0 / 1 (16-bit) only, 2..9 levels */
+int iunet_net_create_nested(int dim, int levels, int base, int cin, int ncls, int mode, iunet_net** out) {
+  IUNET_REQUIRE(mode == 0 || mode == 1, "net_create_nested: mode must be 0 (fp16) or 1 (bf16), got %d", mode);
+  return net_create(dim, levels, base, cin, ncls, mode, 0.f, 0, 8, true, out);
+}
+static int net_create(int dim, int levels, int base, int cin, int ncls, int mode, float act_scale, int norm, int groups, bool nested, iunet_net** out) {
   IUNET_REQUIRE(out != nullptr, "net_create: null handle pointer");
   IUNET_REQUIRE(norm == 0 || norm == 1, "net_create: norm must be 0 (batch) or 1 (group), got %d", norm);
   IUNET_REQUIRE(norm == 0 || (mode == 2 && groups > 0 && base % groups == 0), "net_create: GroupNorm runs in mode 2 (fp16x2) with groups dividing base (mode %d, %d groups)", mode, groups);
   IUNET_REQUIRE(dim == 2 || dim == 3, "net_create: dim must be 2 or 3 (got %d)", dim);
-  IUNET_REQUIRE(levels >= 2 && levels <= 6, "net_create: levels must be 2..6 (got %d)", levels);
+  if (nested) IUNET_REQUIRE(levels >= 2 && levels <= 9, "net_create_nested: levels must be 2..9 (got %d)", levels);
+  else IUNET_REQUIRE(levels >= 2 && levels <= 6, "net_create: levels must be 2..6 (got %d)", levels);
   IUNET_REQUIRE(base > 0 && base % 32 == 0, "net_create: base channels must be a positive multiple of 32 (got %d)", base);
   IUNET_REQUIRE(cin >= 1 && cin <= 4, "net_create: 1..4 input channels (got %d)", cin);
   IUNET_REQUIRE(ncls >= 2 && ncls <= 10, "net_create: 2..10 classes (app.py:162; got %d)", ncls);
@@ -229,7 +330,21 @@ int iunet_net_create_ex(int dim, int levels, int base, int cin, int ncls, int mo
     }
   };
   for (int l = 0; l < levels; ++l) stage("enc" + std::to_string(l), l == 0 ? cin : n->ch[l - 1], n->ch[l]);
-  for (int l = levels - 2; l >= 0; --l) {
+  n->nested = nested;
+  for (int j = 1; j < levels && nested; ++j)            // unet.nested_nodes: by column j, then level i
+    for (int i = 0; i + j < levels; ++i) {
+      n->nodes.push_back({i, j});
+      UpOp u;
+      u.ci = n->ch[i + 1]; u.co = n->ch[i];
+      const std::string p = "dec" + std::to_string(i) + "_" + std::to_string(j);
+      u.w = add(p + ".up.weight", (long long)u.ci * u.co * n->npos);
+      u.b = add(p + ".up.bias", u.co);
+      u.pk = pk_take((long long)u.ci * u.co * n->npos * 2);
+      u.aux = pk_take(2ll * u.co * 4);
+      n->up.push_back(u);
+      stage(p, (j + 1) * n->ch[i], n->ch[i]);
+    }
+  for (int l = levels - 2; l >= 0 && !nested; --l) {
     UpOp u;
     u.ci = n->ch[l + 1]; u.co = n->ch[l];
     const std::string p = "dec" + std::to_string(l);
@@ -352,6 +467,7 @@ int iunet_net_forward(iunet_net* n, const void* x, int in_dtype, const long long
   unsigned char* WS = (unsigned char*)workspace;
   unsigned char* K = n->packed;
   const int lv = n->levels, dim = n->dim, mode = n->mode;
+  if (n->nested) return nested_forward(n, L, x, in_dtype, in_strides, N, D, H, W, WS, logits, probs, cls, out_strides, divisor, accumulate, stream);
   if (mode == 3) {
     // ---- x2m: a / cat / pin = (hi planes, lo8 planes), b = (hi planes, lo planes); engine_x2.EngineX2._infer_mixed sequences the same launches
     const float A = n->act_scale;

@@ -94,6 +94,8 @@ int iunet_gn_relu_bwd(int, const void*, long long, const void*, long long, void*
 int iunet_gn_relu_pool_bwd(int, int, const void*, long long, const void*, long long, const void*, long long, void*, long long, const void*, int,
                            const void*, const void*, const void*, const void*, void*, void*, void*, void*, int, int, int, int, int, void*);
 int iunet_first_conv_wgrad(int, int, const void*, int, const long long*, const void*, long long, void*, void*, int, int, int, int, int, int, void*);
+int iunet_bn_relu_sum_bwd(int, int, int, const void* const*, const long long*, const void*, long long, const void*, long long, void*, long long,
+                          const void*, const void*, const void*, const void*, const void*, void*, void*, void*, void*, int, int, int, int, int, void*);
 }
 
 namespace {
@@ -122,7 +124,8 @@ struct TUp { int ci, co, l; long long w, b, fwd, dgr; };
 
 struct TWs {
   std::vector<long long> y, z, dz, scale, shift, mean, invstd;      // per conv (z / dz: -1 for the skip convs)
-  std::vector<long long> cat, dcat, bslab, pin, dpin;               // per level
+  std::vector<long long> cat, dcat, bslab, pin, dpin;               // per level (U-Net++: cat = the level buffer [X^{l,0} | X^{l,1} | ..])
+  std::vector<long long> up, ndcat, dT;                             // U-Net++, per node: the stash of up(.), conv1's and the transposed conv's data gradients
   long long dy, stats, wslab, bnslab, bncoef, lslab, hslab, htmp, out4, coef, bytes;
 };
 
@@ -138,6 +141,11 @@ struct iunet_train {
   long long nparams = 0;
   std::vector<TConv> conv;                       // enc0.conv1, enc0.conv2, ..., dec{L-2}.conv1, ... (stage order)
   std::vector<TUp> up;                           // dec{L-2}.up ... dec0.up
+  // U-Net++ (iunet_train_create_nested): the decoder stages are the nodes dec{i}_{j} in unet.nested_nodes order (by column j, then
+  // level i), conv / up hold them in that order after the encoder; node_at[i * levels + j] = position of node (i, j) in `nodes`
+  bool nested = false;
+  std::vector<std::pair<int, int>> nodes;
+  std::vector<int> node_at;
   long long head_w = 0, head_b = 0;
   long long packed_bytes = 0, table_off = 0;
   int ndesc = 0;
@@ -173,7 +181,10 @@ int pack_pick(const TPack& p, int nd, int N, int D, int H, int W, bool act, bool
   return lay;
 }
 
+TWs ws_layout_nested(const iunet_train* n, int N, int D, int H, int W);
+
 TWs ws_layout(const iunet_train* n, int N, int D, int H, int W) {
+  if (n->nested) return ws_layout_nested(n, N, D, H, W);
   TWs L;
   const int lv = n->levels, dim = n->dim;
   long long off = 0;
@@ -236,6 +247,79 @@ TWs ws_layout(const iunet_train* n, int N, int D, int H, int W) {
   return L;
 }
 
+// the workspace of train_engine_nested.NestedTrainEngine.workspace: per conv y (+ z / dz of conv1 and of the last node's conv2, the
+// head's input), one level buffer of L - l slots per level, and per node the stash of up(.) and the two data gradients
+TWs ws_layout_nested(const iunet_train* n, int N, int D, int H, int W) {
+  TWs L;
+  const int lv = n->levels, dim = n->dim;
+  long long off = 0;
+  auto act = [&](long long elems) { const long long o = off; off = align256(off + elems * 2); return o; };
+  auto f32 = [&](long long nfl) { const long long o = off; off = align256(off + nfl * 4); return o; };
+  auto dims = [&](int l, int& d, int& h, int& w) { d = dim == 3 ? D >> l : 1; h = H >> l; w = W >> l; };
+  auto vox = [&](int l) { int d, h, w; dims(l, d, h, w); return (long long)d * h * w; };
+  const size_t nc = n->conv.size();
+  L.y.assign(nc, -1); L.z.assign(nc, -1); L.dz.assign(nc, -1);
+  L.scale.assign(nc, -1); L.shift.assign(nc, -1); L.mean.assign(nc, -1); L.invstd.assign(nc, -1);
+  long long max_stats = 0, max_wslab = 0, max_bn = 0, max_dy = 0;
+  for (size_t k = 0; k < nc; ++k) {
+    const TConv& c = n->conv[k];
+    int d, h, w;
+    dims(c.l, d, h, w);
+    const long long v = vox(c.l);
+    L.y[k] = act((long long)N * c.co * v);
+    if (k % 2 == 0 || k == nc - 1) { L.z[k] = act((long long)N * c.co * v); L.dz[k] = act((long long)N * c.co * v); }
+    L.scale[k] = f32(c.co); L.shift[k] = f32(c.co); L.mean[k] = f32(c.co); L.invstd[k] = f32(c.co);
+    if (c.first) {
+      max_stats = std::max(max_stats, (long long)iunet_conv3_num_tiles(dim, N, d, h, w) * c.co * 2);
+      max_wslab = std::max(max_wslab, (long long)iunet_first_conv_wgrad_blocks(dim, N, d, h, w) * c.co * 112);
+    } else {
+      const long long p0 = iunet_conv3_stats_parts(dim, N, d, h, w, c.co, 0), p2 = iunet_conv3_stats_parts(dim, N, d, h, w, c.co, 2);
+      max_stats = std::max(max_stats, std::max(p0, p2) * c.co * 2);
+      max_wslab = std::max(max_wslab, iunet_conv3_wgrad_slab_floats(dim, N, d, h, w, c.ci, c.co));
+    }
+    max_bn = std::max(max_bn, (long long)iunet_bn_bwd_num_parts(N, v) * c.co * 2);
+    max_dy = std::max(max_dy, (long long)n->ch[c.l] * v);
+  }
+  L.cat.assign(lv, -1); L.pin.assign(lv, -1); L.dpin.assign(lv, -1);
+  for (int l = 0; l < lv; ++l) {
+    const long long v = vox(l);
+    L.cat[l] = act((long long)N * (lv - l) * n->ch[l] * v);
+    if (l > 0) { L.pin[l] = act((long long)N * n->ch[l - 1] * v); L.dpin[l] = act((long long)N * n->ch[l - 1] * v); }
+  }
+  const size_t nn = n->nodes.size();
+  L.up.assign(nn, -1); L.ndcat.assign(nn, -1); L.dT.assign(nn, -1); L.bslab.assign(nn, -1);
+  for (size_t k = 0; k < nn; ++k) {
+    const int i = n->nodes[k].first, j = n->nodes[k].second;
+    const long long v = vox(i), vi = vox(i + 1);
+    L.up[k] = act((long long)N * n->ch[i] * v);
+    L.ndcat[k] = act((long long)N * (j + 1) * n->ch[i] * v);
+    L.dT[k] = act((long long)N * n->ch[i + 1] * vi);
+    int d, h, w;
+    dims(i + 1, d, h, w);
+    const long long nb = iunet_convT_wgrad_blocks(dim, N, d, h, w, n->ch[i + 1], n->ch[i]);
+    max_wslab = std::max(max_wslab, nb * n->ch[i + 1] * n->ch[i] * n->npos);
+    L.bslab[k] = f32(nb * n->ch[i]);
+  }
+  const long long v0 = vox(0);
+  L.dy = act((long long)N * max_dy);
+  L.stats = f32(max_stats); L.wslab = f32(max_wslab); L.bnslab = f32(max_bn);
+  L.bncoef = f32(3ll * n->ch[lv - 1]);
+  L.lslab = f32((long long)iunet_head_loss_num_parts(N, v0) * n->ncls * 8);
+  L.hslab = f32((long long)iunet_head_loss_bwd_num_parts(N, v0, n->ncls, n->ch[0]) * n->ncls * (n->ch[0] + 1));
+  L.htmp = f32((long long)n->ncls * (n->ch[0] + 1));
+  L.out4 = f32(4);
+  L.coef = f32((long long)n->ncls * 3);
+  L.bytes = off;
+  return L;
+}
+
+// a channel slot of ch channels (of elems 16-bit elements per sample) copied between two tensors of different sample strides: N rows
+int copy_slot(void* dst, long long dst_ss, const void* src, long long src_ss, long long elems, int N, void* stream) {
+  IUNET_CHECK_HIP(hipMemcpy2DAsync(dst, (size_t)dst_ss * 2, src, (size_t)src_ss * 2, (size_t)elems * 2, (size_t)N, hipMemcpyDeviceToDevice,
+                                   (hipStream_t)stream));
+  return IUNET_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -248,11 +332,21 @@ int iunet_train_create(int dim, int levels, int base, int cin, int ncls, int dty
 }
 /* norm: 0 BatchNorm, 1 GroupNorm(groups) after every stage conv (north star "GroupNorm/BN"; statistics per (sample, group), the same at
  * training and inference -- the running-statistics pointers of iunet_train_bind are accepted and left alone) */
+static int train_create(int dim, int levels, int base, int cin, int ncls, int dtype, int loss_kind, int norm, int groups, bool nested, iunet_train** out);
 int iunet_train_create_ex(int dim, int levels, int base, int cin, int ncls, int dtype, int loss_kind, int norm, int groups, iunet_train** out) {
+  return train_create(dim, levels, base, cin, ncls, dtype, loss_kind, norm, groups, false, out);
+}
+/* U-Net++ (unet.param_shapes(..., architecture='U-Net++')): BatchNorm, 2..9 levels, dtype 0 fp16 / 1 bf16 -- the step of
+ * interactive_unet/train_engine_nested.py, the same launches in the same order */
+int iunet_train_create_nested(int dim, int levels, int base, int cin, int ncls, int dtype, int loss_kind, iunet_train** out) {
+  return train_create(dim, levels, base, cin, ncls, dtype, loss_kind, 0, 8, true, out);
+}
+static int train_create(int dim, int levels, int base, int cin, int ncls, int dtype, int loss_kind, int norm, int groups, bool nested, iunet_train** out) {
   IUNET_REQUIRE(out != nullptr, "train_create: null handle pointer");
   IUNET_REQUIRE(norm == 0 || (norm == 1 && groups > 0 && base % groups == 0), "train_create: norm must be 0 (batch) or 1 (group, groups dividing base): %d, %d groups", norm, groups);
   IUNET_REQUIRE(dim == 2 || dim == 3, "train_create: dim must be 2 or 3 (got %d)", dim);
-  IUNET_REQUIRE(levels >= 2 && levels <= 6, "train_create: levels must be 2..6 (got %d)", levels);
+  if (nested) IUNET_REQUIRE(levels >= 2 && levels <= 9, "train_create_nested: levels must be 2..9 (got %d)", levels);
+  else IUNET_REQUIRE(levels >= 2 && levels <= 6, "train_create: levels must be 2..6 (got %d)", levels);
   IUNET_REQUIRE(base > 0 && base % 32 == 0, "train_create: base channels must be a positive multiple of 32 (got %d)", base);
   IUNET_REQUIRE(base == 32 || base == 64, "train_create: the fused head + loss kernels take 32 or 64 head input channels (base %d)", base);
   IUNET_REQUIRE(cin >= 1 && cin <= 4, "train_create: 1..4 input channels (got %d)", cin);
@@ -302,7 +396,28 @@ int iunet_train_create_ex(int dim, int levels, int base, int cin, int ncls, int 
     }
   };
   for (int l = 0; l < levels; ++l) stage("enc" + std::to_string(l), l == 0 ? cin : n->ch[l - 1], n->ch[l], l);
-  for (int l = levels - 2; l >= 0; --l) {
+  auto up_op = [&](const std::string& p, int l) {
+    TUp u;
+    u.ci = n->ch[l + 1]; u.co = n->ch[l]; u.l = l;
+    u.w = add(p + ".up.weight", (long long)u.ci * u.co * n->npos);
+    u.b = add(p + ".up.bias", u.co);
+    const long long ne = (long long)u.ci * u.co * n->npos;
+    u.fwd = pk; pk = align256(pk + ne * 2);
+    u.dgr = pk; pk = align256(pk + ne * 2);
+    n->ndesc += 2;
+    n->up.push_back(u);
+  };
+  n->nested = nested;
+  n->node_at.assign((size_t)levels * levels, -1);
+  for (int j = 1; j < levels && nested; ++j)            // unet.nested_nodes: by column j, then level i
+    for (int i = 0; i + j < levels; ++i) {
+      n->node_at[i * levels + j] = (int)n->nodes.size();
+      n->nodes.push_back({i, j});
+      const std::string p = "dec" + std::to_string(i) + "_" + std::to_string(j);
+      up_op(p, i);
+      stage(p, (j + 1) * n->ch[i], n->ch[i], i);
+    }
+  for (int l = levels - 2; l >= 0 && !nested; --l) {
     TUp u;
     u.ci = n->ch[l + 1]; u.co = n->ch[l]; u.l = l;
     const std::string p = "dec" + std::to_string(l);
@@ -485,7 +600,52 @@ int iunet_train_forward_backward_hooks(iunet_train* n, const void* x, int in_dty
   // materialised activation (train_engine.TrainEngine._conv2_input)
   auto conv2_fused = [&](int l) { return n->fuse_act && (dim == 3 || n->ch[l] <= 64); };
 
-  for (int l = 0; l < lv; ++l) {
+  if (n->nested) {
+    // ---- U-Net++ forward (train_engine_nested.NestedTrainEngine.forward_train): the encoder writes X^{l,0} into slot 0 of its level
+    // buffer; node (i, j)'s transposed conv writes up(X^{i+1,j-1}) into slot j, conv1 reads slots 0..j, up(.) is stashed, conv2's
+    // activation overwrites slot j (the last node's: the head's input)
+    for (int l = 0; l < lv; ++l) {
+      const long long v = vox(l);
+      const int c = n->ch[l], ci = l == 0 ? n->cin : n->ch[l - 1];
+      const int k1 = 2 * l, k2 = 2 * l + 1;
+      const bool fused = conv2_fused(l);
+      void* z1p = fused ? nullptr : (void*)(WS + L.z[k1]);
+      const void* x2 = fused ? (const void*)(WS + L.y[k1]) : (const void*)(WS + L.z[k1]);
+      rc = l == 0 ? conv_fwd(k1, nullptr, 0, z1p, (long long)c * v, -1, nullptr, 0)
+                  : conv_fwd(k1, WS + L.pin[l], (long long)ci * v, z1p, (long long)c * v, -1, nullptr, 0);
+      if (rc) return rc;
+      const long long z0_ss = (long long)(lv - l) * c * v;
+      if (l < lv - 1) rc = conv_fwd(k2, x2, (long long)c * v, WS + L.cat[l], z0_ss, fused ? k1 : -1, WS + L.pin[l + 1], (long long)c * vox(l + 1));
+      else rc = conv_fwd(k2, x2, (long long)c * v, WS + L.cat[l], z0_ss, fused ? k1 : -1, nullptr, 0);
+      if (rc) return rc;
+    }
+    for (size_t k = 0; k < n->nodes.size(); ++k) {
+      const int i = n->nodes[k].first, j = n->nodes[k].second;
+      int di, hi, wi;
+      dims(i + 1, di, hi, wi);
+      const long long v = vox(i), vi = vox(i + 1);
+      const int c = n->ch[i], cn = n->ch[i + 1];
+      const int k1 = 2 * (lv + (int)k), k2 = k1 + 1;
+      const TUp& u = n->up[k];
+      const long long cat_ss = (long long)(lv - i) * c * v, src_ss = (long long)(lv - i - 1) * cn * vi;
+      unsigned char* up = WS + L.cat[i] + (long long)j * c * v * 2;
+      rc = iunet_convT_fwd(dt, dim, WS + L.cat[i + 1] + (long long)(j - 1) * cn * vi * 2, src_ss, up, cat_ss, K + u.fwd, P + u.b, N, di, hi, wi, cn, c,
+                           stream);
+      if (rc) return rc;
+      const bool fused = conv2_fused(i);
+      void* z1p = fused ? nullptr : (void*)(WS + L.z[k1]);
+      const void* x2 = fused ? (const void*)(WS + L.y[k1]) : (const void*)(WS + L.z[k1]);
+      rc = conv_fwd(k1, WS + L.cat[i], cat_ss, z1p, (long long)c * v, -1, nullptr, 0);
+      if (rc) return rc;
+      rc = copy_slot(WS + L.up[k], (long long)c * v, up, cat_ss, (long long)c * v, N, stream);          // stash up(.)
+      if (rc) return rc;
+      const bool last = k + 1 == n->nodes.size();
+      void* z2 = last ? (n->head_act ? nullptr : (void*)(WS + L.z[k2])) : (void*)up;
+      rc = conv_fwd(k2, x2, (long long)c * v, z2, last ? (long long)c * v : cat_ss, fused ? k1 : -1, nullptr, 0);
+      if (rc) return rc;
+    }
+  }
+  for (int l = 0; l < lv && !n->nested; ++l) {
     const long long v = vox(l);
     const int c = n->ch[l], ci = l == 0 ? n->cin : n->ch[l - 1];
     const int k1 = idx(false, l, 1), k2 = idx(false, l, 2);
@@ -499,7 +659,7 @@ int iunet_train_forward_backward_hooks(iunet_train* n, const void* x, int in_dty
     else rc = conv_fwd(k2, x2, (long long)c * v, WS + L.z[k2], (long long)c * v, fused ? k1 : -1, nullptr, 0);
     if (rc) return rc;
   }
-  for (int l = lv - 2; l >= 0; --l) {
+  for (int l = lv - 2; l >= 0 && !n->nested; --l) {
     int di, hi, wi;
     dims(l + 1, di, hi, wi);
     const long long v = vox(l), vi = vox(l + 1);
@@ -523,7 +683,7 @@ int iunet_train_forward_backward_hooks(iunet_train* n, const void* x, int in_dty
 
   // ---- head + softmax + loss (unet.py:88-102, metrics.py)
   const long long v0 = vox(0);
-  const int c0 = n->ch[0], kl = idx(true, 0, 2);
+  const int c0 = n->ch[0], kl = n->nested ? (int)n->conv.size() - 1 : idx(true, 0, 2);
   if (n->gn_head)
     rc = iunet_head_loss_fwd_act_ps(dt, WS + L.y[kl], (long long)c0 * v0, c0, P + n->head_w, P + n->head_b, n->ncls, target, weight, tdtype, n->kind,
                                     F(L.lslab), F(L.out4), F(L.coef), F(L.scale[kl]), F(L.shift[kl]), 1, N, v0, stream);
@@ -633,6 +793,86 @@ int iunet_train_forward_backward_hooks(iunet_train* n, const void* x, int in_dty
     }
     return rc;
   };
+  if (n->nested) {
+    // ---- U-Net++ backward (NestedTrainEngine.backward): the nodes in reverse topological order, then the encoder bottom-up.  The
+    // gradient of X^{i,m} is the sum of slot m of the conv1 data gradient of nodes (i, m+1), (i, m+2), .., the transposed conv's data
+    // gradient of node (i-1, m+1) and, for the encoder, the max-pool route: with more than one consumer iunet_bn_relu_sum_bwd forms
+    // it inside the BatchNorm + ReLU backward, with one the U-Net path runs as it is
+    auto node_conv2_bwd = [&](int s, int i, int m, const void* dpool, long long dpool_ss) -> int {
+      const long long v = vox(i);
+      const int c = n->ch[i], k1 = 2 * s, k2 = k1 + 1;
+      const bool fused = conv2_fused(i);
+      const void* x2 = fused ? (const void*)(WS + L.y[k1]) : (const void*)(WS + L.z[k1]);
+      const void* dzp = nullptr;
+      long long dz_ss = 0;
+      if (k2 != dy_ready) {
+        const void* sp[8];
+        long long ss[8];
+        int K_ = 0;
+        for (int jj = m + 1; jj < lv - i; ++jj) {
+          const int q = n->node_at[i * lv + jj];
+          sp[K_] = WS + L.ndcat[q] + (long long)m * c * v * 2; ss[K_++] = (long long)(jj + 1) * c * v;
+        }
+        if (i >= 1) { sp[K_] = WS + L.dT[n->node_at[(i - 1) * lv + m + 1]]; ss[K_++] = (long long)c * v; }
+        if (K_ + (dpool != nullptr) == 1) {
+          dzp = sp[0]; dz_ss = ss[0];
+        } else {
+          const TConv& cc = n->conv[k2];
+          int d, h, w;
+          dims(i, d, h, w);
+          rc = iunet_bn_relu_sum_bwd(dt, dim, K_, sp, ss, dpool, dpool_ss, WS + L.y[k2], (long long)c * v, WS + L.dy, (long long)c * v, F(L.mean[k2]),
+                                     F(L.invstd[k2]), P + cc.gamma, F(L.scale[k2]), F(L.shift[k2]), G + cc.gamma, G + cc.beta, F(L.bnslab), F(L.bncoef),
+                                     c, N, d, h, w, stream);
+          if (rc) return rc;
+          dy_ready = k2;
+        }
+      }
+      return conv_bwd(k2, dzp, dz_ss, x2, (long long)c * v, WS + L.dz[k1], (long long)c * v, fused ? k1 : -1, nullptr, 0, k1);
+    };
+    for (int k = (int)n->nodes.size() - 1; k >= 0; --k) {
+      const int i = n->nodes[k].first, j = n->nodes[k].second, s = lv + k;
+      int di, hi, wi;
+      dims(i + 1, di, hi, wi);
+      const long long v = vox(i), vi = vox(i + 1);
+      const int c = n->ch[i], cn = n->ch[i + 1], k1 = 2 * s;
+      if (k + 1 == (int)n->nodes.size() && dy_ready != kl) {
+        const bool fused = conv2_fused(i);
+        const void* x2 = fused ? (const void*)(WS + L.y[k1]) : (const void*)(WS + L.z[k1]);
+        rc = conv_bwd(kl, WS + L.dz[kl], (long long)c * v, x2, (long long)c * v, WS + L.dz[k1], (long long)c * v, fused ? k1 : -1, nullptr, 0, k1);
+      } else {
+        rc = node_conv2_bwd(s, i, j, nullptr, 0);
+      }
+      if (rc) return rc;
+      const long long cat_ss = (long long)(lv - i) * c * v, dcat_ss = (long long)(j + 1) * c * v;
+      rc = copy_slot(WS + L.cat[i] + (long long)j * c * v * 2, cat_ss, WS + L.up[k], (long long)c * v, (long long)c * v, N, stream);      // restore up(.)
+      if (rc) return rc;
+      rc = conv_bwd(k1, WS + L.dz[k1], (long long)c * v, WS + L.cat[i], cat_ss, WS + L.ndcat[k], dcat_ss, -1, nullptr, 0, -1);
+      if (rc) return rc;
+      const TUp& u = n->up[k];
+      const void* src = WS + L.cat[i + 1] + (long long)(j - 1) * cn * vi * 2;
+      void* dup = WS + L.ndcat[k] + (long long)j * c * v * 2;
+      rc = iunet_convT_wgrad(dt, dim, src, (long long)(lv - i - 1) * cn * vi, dup, dcat_ss, F(L.wslab), F(L.bslab[k]), G + u.w, G + u.b, N, di, hi, wi, cn,
+                             c, stream);
+      if (rc) return rc;
+      rc = iunet_convT_dgrad(dt, dim, dup, dcat_ss, WS + L.dT[k], (long long)cn * vi, K + u.dgr, N, di, hi, wi, cn, c, stream);
+      if (rc) return rc;
+    }
+    if (hook) hook(hook_ctx, 0);                // every node's + the head's gradients enqueued
+    for (int l = lv - 1; l >= 0; --l) {
+      const long long v = vox(l);
+      const int c = n->ch[l], k1 = 2 * l;
+      rc = l < lv - 1 ? node_conv2_bwd(l, l, 0, WS + L.dpin[l + 1], (long long)c * vox(l + 1)) : node_conv2_bwd(l, l, 0, nullptr, 0);
+      if (rc) return rc;
+      if (l == 0) rc = conv_bwd(k1, WS + L.dz[k1], (long long)c * v, nullptr, 0, nullptr, 0, -1, nullptr, 0, -1);
+      else {
+        const int cp = n->ch[l - 1];
+        rc = conv_bwd(k1, WS + L.dz[k1], (long long)c * v, WS + L.pin[l], (long long)cp * v, WS + L.dpin[l], (long long)cp * v, -1, nullptr, 0, -1);
+      }
+      if (rc) return rc;
+      if (hook && l == lv - 1) hook(hook_ctx, 1);      // the bottom encoder level's gradients enqueued
+    }
+    return IUNET_OK;
+  }
   // decoder, level 0 upwards
   for (int l = 0; l < lv - 1; ++l) {
     int di, hi, wi;

@@ -8,8 +8,9 @@ Graph.  X^{i,0} is the encoder (enc{i}); for j >= 1 and i + j <= L - 1, X^{i,j} 
 Layout.  One buffer per level i with L - i channel-blocked slots of ch[i] channels, [X^{i,0} | X^{i,1} | ..] per sample: the
 transposed conv of node (i, j) writes up(X^{i+1,j-1}) into slot j, conv1 reads slots 0..j as one (j + 1) ch[i]-channel input (the
 concat is free: consecutive channel planes), and conv2's output overwrites slot j -- up(.) has no reader after conv1.  X^{0,L-1}
-goes to a buffer of its own, the head's input.  Both forwards are sequenced from Python (the C++-sequenced forward, net_graph, knows
-the U-Net topology only).
+goes to a buffer of its own, the head's input.  The 16-bit forward runs as one C call from its second forward on the same weights
+(net_graph.NetGraph over iunet_net_create_nested: the same launches sequenced in C++, bit-identical); the fp32 form is sequenced from
+Python.
 """
 import ctypes
 
@@ -52,7 +53,7 @@ class _Nested:
         return (j + 1) * self.ch[i], self.ch[i]
 
     def _graph(self):
-        return None          # the C++-sequenced forward is the U-Net graph's
+        return None          # (the fp32 form has no handle mode)
 
     def bytes_per_slice(self, input_size):
         """Workspace bytes of one 2-D slice of input_size^2 (predict.find_max_batch_size)."""
@@ -75,13 +76,30 @@ class NestedEngine(_Nested, Engine):
             raise NotImplementedError("NestedEngine runs fp16 / bf16 activations (NestedEngineF32: the fp32 form)")
         Engine.__init__(self, dim, levels, base, cin, ncls, act_dtype, device)
         self._nested_init()
+        self.use_graph = True      # False: every forward sequenced from Python (tests compare the two)
         self._es = 2
+
+    def _graph(self):
+        """The C++-sequenced nested forward (net_graph.NetGraph over iunet_net_create_nested) on this engine's current parameters, from the
+        SECOND forward on them (engine.Engine._graph's rule), or None (IUNET_PY_GRAPH=1, use_graph False, nothing loaded yet)."""
+        from . import net_graph
+        self._g_fwd += 1
+        if self._g_fwd < 2 or not net_graph.ENABLED or not self.use_graph or self._gparams is None:
+            return None
+        if self._g is None:
+            self._g = net_graph.NetGraph(self.dim, self.levels, self.base, self.cin, self.ncls, self.dt, self.device, nested=True)
+        if self._g_dirty:
+            self._g.set_params(self._gparams)
+            self._g_dirty = False
+            self._ws_cache.clear()         # the handle has its own workspace
+        return self._g
 
     def load_eval(self, params):
         """Fold eval-mode BatchNorm into every stage conv and pack all operators (one launch over a descriptor table, rebuilt when a
         source tensor moves), as Engine.load_eval does for the U-Net."""
         if not hasattr(self, '_stage'):
             self._stage, self._eval_sig, self._eval_table = {}, None, None
+        self._gparams, self._g_dirty, self._g_fwd = params, True, 0
         names = []
         for prefix in self.stage_names():
             for j in (1, 2):
@@ -133,6 +151,10 @@ class NestedEngine(_Nested, Engine):
         """engine.Engine.infer's contract on the nested graph (features_only: the head's input X^{0,L-1}, NHWC8c, contiguous)."""
         if self.packed is None:
             raise RuntimeError('NestedEngine.load_eval() has not been called')
+        g = self._graph()
+        if g is not None and not features_only and self.probe is None:
+            self.check_shape(D, H, W)
+            return g.infer(x, x_strides, N, D, H, W, logits, probs, cls, out_strides, divisor, accumulate)
         ws = self.workspace(N, D, H, W)
         dims, L, ch, s = ws['dims'], self.levels, self.ch, nv.stream()
         P = lambda t: ctypes.c_void_p(t.data_ptr())

@@ -383,6 +383,13 @@ class TrainEngine:
             self._stage_conv_fwd(ws, f'dec{l}.conv2', x2, ch[l] * v, ch[l], ch[l], l, z2, ch[l] * v, N, x_act=act)
         return ws
 
+    def train_loss_forward(self, ws, y, w, N, vox):
+        """loss_forward on the head's input of a training forward: the last conv's raw output with its BatchNorm + ReLU applied by the head
+        kernel (head_act), or the materialised activation."""
+        if self.head_act or self.gn_head:
+            return self.loss_forward(ws, ws['y.dec0.conv2'], y, w, N, vox, act='dec0.conv2')
+        return self.loss_forward(ws, ws['z.dec0.conv2'], y, w, N, vox)
+
     def loss_forward(self, ws, feat, y, w, N, vox, act=None):
         """head + softmax + loss sums + loss/metrics/coefs (device scalars in ws['out4']).  act: name of the layer whose raw
         output `feat` is (its BatchNorm + ReLU is then applied by the head kernel while loading)."""
@@ -633,10 +640,7 @@ class TrainEngine:
         else:
             self._refresh()
             ws = self.forward_train(X, xs, N, D, H, W)
-            if self.head_act or self.gn_head:
-                tdt, w = self.loss_forward(ws, ws['y.dec0.conv2'], y, w, N, vox, act='dec0.conv2')
-            else:
-                tdt, w = self.loss_forward(ws, ws['z.dec0.conv2'], y, w, N, vox)
+            tdt, w = self.train_loss_forward(ws, y, w, N, vox)
             self.backward(ws, X, xs, y, w, tdt, N)
             self.optimizer_step()
             out4 = ws['out4']
@@ -699,10 +703,7 @@ class TrainEngine:
         self._refresh()
         X, y, w, N, D, H, W, vox, xs = self._prep(X, y, w)
         ws = self.forward_train(X, xs, N, D, H, W)
-        if self.head_act or self.gn_head:
-            tdt, w = self.loss_forward(ws, ws['y.dec0.conv2'], y, w, N, vox, act='dec0.conv2')
-        else:
-            tdt, w = self.loss_forward(ws, ws['z.dec0.conv2'], y, w, N, vox)
+        tdt, w = self.train_loss_forward(ws, y, w, N, vox)
         return ws['out4'], (ws, X, xs, y, w, tdt, N)
 
     def step_backward(self, state):
@@ -775,7 +776,10 @@ class TrainHandle:
         self.lib = nv.lib()
         self.h = ctypes.c_void_p()
         m = te.model
-        nv.call('iunet_train_create_ex', te.dim, te.levels, m.base, te.cin, te.ncls, te.dt, te.kind, 1 if te.gn else 0, int(te.groups), ctypes.byref(self.h))
+        if getattr(te, 'nested', False):            # U-Net++ (train_engine_nested.NestedTrainEngine): BatchNorm only
+            nv.call('iunet_train_create_nested', te.dim, te.levels, m.base, te.cin, te.ncls, te.dt, te.kind, ctypes.byref(self.h))
+        else:
+            nv.call('iunet_train_create_ex', te.dim, te.levels, m.base, te.cin, te.ncls, te.dt, te.kind, 1 if te.gn else 0, int(te.groups), ctypes.byref(self.h))
         n = self.lib.iunet_train_num_params(self.h)
         if n != te.flat.numel():
             raise RuntimeError(f'iunet_train: {n} parameters, the engine holds {te.flat.numel()}')

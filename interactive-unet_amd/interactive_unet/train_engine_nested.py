@@ -11,6 +11,10 @@ X^{i,j} because every reader of X^{i,j} -- the later nodes of level i and node (
 before.  X^{i,j}'s gradient is the sum of slot j of every later node's conv1 data gradient on its level, the data gradient of the
 transposed conv above it and, for the encoder, the max-pool route of the next level's input gradient: with more than one such
 consumer, iunet_bn_relu_sum_bwd forms that sum inside the BatchNorm + ReLU backward; with one, the U-Net path runs as it is.
+
+From the second step the whole step is one C call (TrainEngine._handle: TrainHandle over iunet_train_create_nested, csrc/train_net.hip
+sequences these launches in C++, bit-identical).  Data parallel: the flat vector is the encoder, then every node, then the head, so the
+nodes + head are the tail bucket (all-reduced once the node loop of the backward is done) and enc{L-1} the bottom bucket.
 """
 import ctypes
 
@@ -22,18 +26,26 @@ from .unet import nested_nodes
 
 
 class NestedTrainEngine(TrainEngine):
+    nested = True           # (TrainHandle: iunet_train_create_nested)
+
     def __init__(self, model, lr=None, loss_kind='mcc_ce', betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
                  loss_scale=None, process_group=None):
         if getattr(model, 'norm', 'batch') != 'batch':
             raise NotImplementedError('U-Net++ training supports BatchNorm only')
         if model.act_dtype not in (torch.float16, torch.bfloat16):
             raise NotImplementedError("U-Net++ training runs with 16-bit activations (act_dtype 'fp16' / 'bf16')")
-        if process_group is not None:
-            raise NotImplementedError('U-Net++ training runs on one GPU (no data-parallel process group)')
         self.nodes = nested_nodes(model.levels)
         self.last = f'dec0_{model.levels - 1}'          # X^{0,L-1}: the head's input
-        super().__init__(model, lr=lr, loss_kind=loss_kind, betas=betas, eps=eps, weight_decay=weight_decay, loss_scale=loss_scale)
-        self.use_handle = False
+        super().__init__(model, lr=lr, loss_kind=loss_kind, betas=betas, eps=eps, weight_decay=weight_decay, loss_scale=loss_scale,
+                         process_group=process_group)
+
+    def _flatten(self):
+        super()._flatten()
+        # the data-parallel buckets: every node + the head (the tail from dec0_1, the first node), the bottom encoder level before it
+        self._dec_start = self.offsets['dec0_1.up.weight'][0]
+        bottom = [self.offsets[n] for n in self.names if n.startswith(f'enc{self.levels - 1}.')]
+        lo = min(o for o, _ in bottom)
+        self._bottom_start = lo if lo + sum(s for _, s in bottom) == self._dec_start else None
 
     # ------------------------------------------------------------------ graph
     def stage_names(self):
@@ -45,9 +57,6 @@ class NestedTrainEngine(TrainEngine):
             return (self.cin if l == 0 else self.ch[l - 1]), self.ch[l], l
         i, j = (int(t) for t in prefix[3:].split('_'))
         return (j + 1) * self.ch[i], self.ch[i], i
-
-    def _handle(self):
-        return None          # no C-sequenced handle: the step is sequenced from Python
 
     def _alloc_packed(self):
         self.pk = {}
@@ -289,6 +298,9 @@ class NestedTrainEngine(TrainEngine):
             _, wd = self.pk[node + '.up']
             nv.call('iunet_convT_dgrad', self.dt, self.dim, dup, dcat_ss, self._P(ws['dT.' + node]), ch[i + 1] * vi,
                     nv.ptr(wd), N, di[0], di[1], di[2], ch[i + 1], ch[i], s)
+        # data parallel: every node's and the head's gradients are final -- their all-reduce runs while the encoder backward computes
+        if self.pg is not None:
+            self.buckets.start_tail()
         for l in range(L - 1, -1, -1):
             v = _vox(dims[l])
             pool_bwd = None
@@ -309,29 +321,13 @@ class NestedTrainEngine(TrainEngine):
             else:
                 self._stage_conv_bwd(ws, f'enc{l}.conv1', dz1, ch[l] * v, None, ch[l] * v, self._P(ws[f'pin{l}']), ch[l - 1] * v,
                                      ch[l - 1], ch[l], l, self._P(ws[f'dpin{l}']), ch[l - 1] * v, N)
+            if l == L - 1 and self.pg is not None and self._bottom_start is not None:
+                self.buckets.start(self._bottom_start, self._dec_start)
 
-    # ------------------------------------------------------------------ public steps
-    def train_step(self, X, y, w=None, sync=True):
-        self.sync_weights()
-        X, y, w, N, D, H, W, vox, xs = self._prep(X, y, w)
-        ws = self.forward_train(X, xs, N, D, H, W)
+    # ------------------------------------------------------------------ public steps (TrainEngine.train_step / step_forward)
+    def train_loss_forward(self, ws, y, w, N, vox):
         feat, act = self._head_input(ws)
-        tdt, w = self.loss_forward(ws, feat, y, w, N, vox, act=act)
-        self.backward(ws, X, xs, y, w, tdt, N)
-        self.optimizer_step()
-        out4 = ws['out4']
-        if sync:
-            o = out4.tolist()
-            return {'Loss': o[0], 'Dice': o[1], 'IoU': o[2], 'MCC': o[3]}
-        return out4
-
-    def step_forward(self, X, y, w=None):
-        self.sync_weights()
-        X, y, w, N, D, H, W, vox, xs = self._prep(X, y, w)
-        ws = self.forward_train(X, xs, N, D, H, W)
-        feat, act = self._head_input(ws)
-        tdt, w = self.loss_forward(ws, feat, y, w, N, vox, act=act)
-        return ws['out4'], (ws, X, xs, y, w, tdt, N)
+        return self.loss_forward(ws, feat, y, w, N, vox, act=act)
 
     def _eval_engine(self):
         """The folded-BatchNorm nested forward in the training dtype (its features feed the fused head + loss kernel)."""
@@ -341,12 +337,8 @@ class NestedTrainEngine(TrainEngine):
         if getattr(self, '_eval_eng', None) is None:
             from .engine_nested import NestedEngine
             self._eval_eng = NestedEngine(self.dim, self.levels, m.base, self.cin, self.ncls, self.T, self.dev)
-        sig = (m._signature(), getattr(self, '_steps', 0))
+        sig = (m._signature(), getattr(self, '_steps_seen', 0))
         if sig != getattr(self, '_eval_sig', None):
             self._eval_eng.load_eval(m.named_tensors())
             self._eval_sig = sig
         return self._eval_eng
-
-    def optimizer_step(self):
-        super().optimizer_step()
-        self._steps = getattr(self, '_steps', 0) + 1
