@@ -719,6 +719,41 @@ int iunet_train_step(iunet_train* t, const void* x, int in_dtype, const long lon
                      int tdtype, int N, int D, int H, int W, void* workspace, float lr, float b1, float b2, float eps, float wd, void* out4,
                      void* stream);
 
+/* ---- LinkNet decoder blocks (csrc/linknet.hip; unet.param_shapes(..., architecture='LinkNet')) -----------------------------------
+ * Block l: a1 = relu(bn1(conv1x1(D^{l+1}))), a2 = relu(bn2(convT k4 s2 p1(a1))), D^l = relu(bn3(conv1x1(a2))) + X^l.  Every product is
+ * an implicit GEMM on v_mfma_f32_16x16x32_{f16,bf16} over NHWC8c tensors with sample strides; channel counts are multiples of 16.
+ * kind 0: 1x1 conv (D, H, W = its grid); kind 1: ConvTranspose k4 s2 p1 (D, H, W = the INPUT grid, output 2x; two taps per axis chosen by
+ * the output voxel's parity, K = 2^d Cin); kind 2: its data gradient, the k4 s2 p1 strided conv over dy on the 2x grid (D, H, W = the
+ * OUTPUT grid, K = 4^d Cin).  Cin / Cout are always the channels of x / y of the call. */
+/* operator packing, w fp32: kind 0 = 1x1 forward (w [Cout][Cin]), 1 = 1x1 data gradient (w [Cout][Cin]; the packed operator maps Cout ->
+ * Cin channels), 2 = convT forward (w [Cin][Cout][4^d]), 3 = convT data gradient (w [Cin][Cout][4^d]; maps Cout -> Cin).  A non-NULL gamma
+ * folds an eval-mode BatchNorm into kinds 0 / 2 (w * gamma / sqrt(var + eps)) and writes bias_out = beta - mean * that scale.  dtype 0 f16,
+ * 1 bf16, 2 f32 (the operator of iunet_lk_f32_conv_fwd).  dst: iunet_lk_pack_elems elements (-1: bad arguments). */
+long long iunet_lk_pack_elems(int nd, int kind, int Cout, int Cin);
+int iunet_lk_pack(int dtype, int nd, int kind, const void* w, const void* gamma, const void* beta, const void* mean, const void* var,
+                  float eps, void* dst, void* bias_out, int Cout, int Cin, void* stream);
+/* y = conv(x') with x' = relu(in_scale[c] * x + in_shift[c]) rounded to the activation dtype where in_scale is given (the bits
+ * iunet_bn_relu_fwd stores; kinds 0 and 1), else x.  epi 0: the raw output, and with stats non-NULL the BatchNorm partial sums of its fp32
+ * values, [iunet_lk_stats_parts][Cout][2] rows for iunet_bn_finalize; epi 1 (folded BatchNorm): relu(acc + bias) (+ skip, same shape as y,
+ * added in fp32, one rounding). */
+int iunet_lk_stats_parts(int nd, int kind, int N, int D, int H, int W, int Cout);
+int iunet_lk_conv_fwd(int dtype, int nd, int kind, const void* x, long long x_ss, void* y, long long y_ss, const void* wpk,
+                      const void* in_scale, const void* in_shift, const void* bias, const void* skip, long long skip_ss, void* stats, int epi,
+                      int N, int D, int H, int W, int Cin, int Cout, void* stream);
+/* weight gradient (kinds 0 / 1; x the forward's input with the same optional activation, dy its output gradient): dW = alpha * the sum over
+ * the batch, fp32, written in the parameter's layout ([Cout][Cin] / [Cin][Cout][4^d]); slab: iunet_lk_wgrad_slab_floats floats of scratch,
+ * reduced in a fixed order. */
+long long iunet_lk_wgrad_slab_floats(int nd, int kind, int N, int D, int H, int W, int Cin, int Cout);
+int iunet_lk_wgrad(int dtype, int nd, int kind, const void* x, long long x_ss, const void* dy, long long dy_ss, const void* x_scale,
+                   const void* x_shift, void* slab, void* dW, float alpha, int N, int D, int H, int W, int Cin, int Cout, void* stream);
+/* training forward of a block's output: out = relu(scale * y + shift) + skip, the sum in fp32, one rounding */
+int iunet_lk_bn_relu_add(int dtype, const void* y, long long y_ss, const void* skip, long long skip_ss, void* out, long long out_ss,
+                         const void* scale, const void* shift, int C, int N, long long vox, void* stream);
+/* fp32 form on the f32-input MFMA (planar fp32 [N][C][vox], sample strides in elements): kind 0 (1x1) or 1 (convT k4 s2 p1) with the
+ * operator of iunet_lk_pack dtype 2 (BatchNorm folded), y = relu(acc + bias) (+ skip where given, kind 0) */
+int iunet_lk_f32_conv_fwd(int nd, int kind, const void* x, long long x_ss, void* y, long long y_ss, const void* wpk, const void* bias,
+                          const void* skip, long long skip_ss, int N, int D, int H, int W, int Cin, int Cout, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -385,7 +385,10 @@ class TrainEngineF32:
 
 def make_train_engine(model, **kw):
     """The training engine of a module: 16-bit activations (TrainEngine) or, for act_dtype='fp32', the fp32 parity form; U-Net++
-    modules train on train_engine_nested.NestedTrainEngine."""
+    modules train on train_engine_nested.NestedTrainEngine, LinkNet modules on train_engine_linknet.LinkNetTrainEngine."""
+    if getattr(model, 'architecture', 'U-Net') == 'LinkNet':
+        from .train_engine_linknet import LinkNetTrainEngine
+        return LinkNetTrainEngine(model, **kw)
     if getattr(model, 'architecture', 'U-Net') == 'U-Net++':
         from .train_engine_nested import NestedTrainEngine
         return NestedTrainEngine(model, **kw)

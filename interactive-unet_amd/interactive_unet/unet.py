@@ -3,7 +3,8 @@
 `.loss_function`, `.device`, `load_from_checkpoint(checkpoint_path=)`; the network itself is
 the native canonical U-Net (engine.py) instead of segmentation_models_pytorch.
 
-architecture='U-Net' and 'U-Net++' (the canonical nested form: engine_nested.py, train_engine_nested.py) exist natively;
+architecture='U-Net', 'U-Net++' (the canonical nested form: engine_nested.py, train_engine_nested.py) and 'LinkNet' (engine_linknet.py,
+train_engine_linknet.py) exist natively;
 `encoder_name` is accepted and ignored (the canonical nets have their own plain conv encoder), `pretrained` is a no-op with a warning (no imagenet
 weights for a from-scratch encoder; no network access).  Extra keyword arguments (dim, levels,
 base, act_dtype, infer_dtype) select the 3-D / wider variants of BASELINE.json's configs.
@@ -36,7 +37,8 @@ _ACT_NAME = {torch.float16: 'fp16', torch.bfloat16: 'bf16', torch.float32: 'fp32
 
 
 NESTED = 'U-Net++'
-ARCHITECTURES = ('U-Net', NESTED)
+LINKNET = 'LinkNet'
+ARCHITECTURES = ('U-Net', NESTED, LINKNET)
 
 
 def nested_nodes(levels):
@@ -48,7 +50,9 @@ def nested_nodes(levels):
 def param_shapes(dim=2, levels=4, base=32, cin=1, ncls=2, architecture='U-Net'):
     """Ordered {name: shape} of the canonical network (same names as the oracle's definition).  architecture='U-Net++': the
     nested form (Zhou et al. 2018) on the same stage -- the encoder `enc{i}`, then `dec{i}_{j}` in nested_nodes order, each with
-    its transposed conv ch[i+1] -> ch[i] and a stage (j + 1) ch[i] -> ch[i]."""
+    its transposed conv ch[i+1] -> ch[i] and a stage (j + 1) ch[i] -> ch[i].  architecture='LinkNet': the encoder, then for l = L-2 .. 0
+    the block dec{l} (conv1 1x1 ch[l+1] -> m, ConvTranspose k4 s2 p1 m -> m, conv2 1x1 m -> ch[l], m = ch[l+1] / 4, a BatchNorm after
+    each, no conv bias), then the head."""
     if architecture not in ARCHITECTURES:
         raise NotImplementedError(f'architecture {architecture!r}: the native networks are {ARCHITECTURES}')
     ch = [base * 2 ** l for l in range(levels)]
@@ -62,7 +66,15 @@ def param_shapes(dim=2, levels=4, base=32, cin=1, ncls=2, architecture='U-Net'):
                 shapes[f'{prefix}.bn{j}.{k}'] = (b,)
     for l in range(levels):
         stage(f'enc{l}', cin if l == 0 else ch[l - 1], ch[l])
-    if architecture == NESTED:
+    if architecture == LINKNET:
+        k4 = (4,) * dim
+        for l in range(levels - 2, -1, -1):
+            m = ch[l + 1] // 4
+            for key, shp, bn in (('conv1', (m, ch[l + 1]) + k1, 'bn1'), ('up', (m, m) + k4, 'bn2'), ('conv2', (ch[l], m) + k1, 'bn3')):
+                shapes[f'dec{l}.{key}.weight'] = shp
+                for k in ('weight', 'bias', 'running_mean', 'running_var'):
+                    shapes[f'dec{l}.{bn}.{k}'] = (shp[0] if key != 'up' else m,)
+    elif architecture == NESTED:
         for i, j in nested_nodes(levels):
             shapes[f'dec{i}_{j}.up.weight'] = (ch[i + 1], ch[i]) + k2
             shapes[f'dec{i}_{j}.up.bias'] = (ch[i],)
@@ -94,6 +106,25 @@ def _check_nested(levels, act_dtype, weight_dtype, norm, infer_dtype, infer_poli
         raise NotImplementedError(f'U-Net++ with infer_policy={infer_policy!r} (split-precision forms): {what}')
     if not (2 <= levels <= 9):
         raise NotImplementedError(f'U-Net++ with {levels} levels: {what}')
+
+
+def _check_linknet(levels, base, cin, ncls, act_dtype, weight_dtype, norm, infer_dtype, infer_policy):
+    """The combinations the native LinkNet supports: BatchNorm, 16-bit training (fp16 / bf16), prediction in fp32 (default) or fp16 /
+    bf16, 2 .. 6 levels, base a multiple of 32, 1 .. 4 input channels, 2 .. 10 classes."""
+    what = ("LinkNet supports norm='batch', act_dtype None / 'fp16' / 'bf16' (training), infer_dtype None / 'fp32' / 'fp16' / "
+            "'bf16' (prediction), 2 .. 6 levels, base a multiple of 32, 1 .. 4 input channels and 2 .. 10 classes")
+    if norm != 'batch':
+        raise NotImplementedError(f'LinkNet with norm={norm!r} (GroupNorm): {what}')
+    if weight_dtype is not None:
+        raise NotImplementedError(f'LinkNet with weight_dtype={weight_dtype!r} (fp8 weights): {what}')
+    if act_dtype is not None and _ACT.get(act_dtype) not in (torch.float16, torch.bfloat16):
+        raise NotImplementedError(f'LinkNet with act_dtype={act_dtype!r} (the fp32 training form / split precision): {what}')
+    if infer_dtype is not None and _ACT.get(infer_dtype) not in (torch.float32, torch.float16, torch.bfloat16):
+        raise NotImplementedError(f'LinkNet with infer_dtype={infer_dtype!r} (split precision): {what}')
+    if infer_policy is not None:
+        raise NotImplementedError(f'LinkNet with infer_policy={infer_policy!r} (split-precision forms): {what}')
+    if not (2 <= levels <= 6) or base % 32 or not (1 <= cin <= 4) or not (2 <= ncls <= 10):
+        raise NotImplementedError(f'LinkNet with {levels} levels, base {base}, {cin} input channels, {ncls} classes: {what}')
 
 
 def _is_buffer(name):
@@ -134,10 +165,12 @@ class UNet(nn.Module):
                  act_quant=None, infer_policy=None):
         super().__init__()
         if architecture not in ARCHITECTURES:
-            raise NotImplementedError(f"architecture {architecture!r}: only 'U-Net' and 'U-Net++' have a native MI355X "
+            raise NotImplementedError(f"architecture {architecture!r}: only 'U-Net', 'U-Net++' and 'LinkNet' have a native MI355X "
                                       f"implementation (the reference builds the others through smp, unet.py:33-54)")
         if architecture == NESTED:
             _check_nested(levels, act_dtype, weight_dtype, norm, infer_dtype, infer_policy)
+        if architecture == LINKNET:
+            _check_linknet(levels, base, num_channels, num_classes, act_dtype, weight_dtype, norm, infer_dtype, infer_policy)
         if pretrained:
             warnings.warn('pretrained=True ignored: the native U-Net encoder is trained from scratch')
         self.hparams = dict(lr=lr, num_channels=num_channels, num_classes=num_classes,
@@ -158,8 +191,8 @@ class UNet(nn.Module):
         self.act_dtype = torch.float16 if act_dtype is None else _ACT[act_dtype]
         if infer_dtype is not None:
             self.infer_dtype = _ACT[infer_dtype]
-        elif architecture == NESTED:
-            self.infer_dtype = torch.float32   # the nested net predicts in the fp32 form (within 1e-3 of the CPU fp32 logits)
+        elif architecture in (NESTED, LINKNET):
+            self.infer_dtype = torch.float32   # these nets predict in the fp32 form (within 1e-3 of the CPU fp32 logits)
         elif act_dtype is None and weight_dtype is None:
             self.infer_dtype = X2              # (GroupNorm networks too: engine_auto runs them in the full fp16x2 form)
         else:
@@ -202,7 +235,7 @@ class UNet(nn.Module):
                     t.copy_(torch.randn(shp, generator=g) * math.sqrt(2.0 / fan_in))      # He-normal
                 elif name.endswith('up.weight'):
                     t.copy_(torch.randn(shp, generator=g) * math.sqrt(1.0 / shp[0]))
-                elif name.endswith('running_var') or name.endswith('bn1.weight') or name.endswith('bn2.weight'):
+                elif name.endswith('running_var') or name.endswith('bn1.weight') or name.endswith('bn2.weight') or name.endswith('bn3.weight'):
                     t.fill_(1.0)
                 else:
                     t.zero_()
@@ -241,6 +274,14 @@ class UNet(nn.Module):
             raise RuntimeError('the native U-Net runs on the GPU only: move the module with .to("cuda") '
                                '(there is no CPU fallback)')
         eng = self._engines.get(dev)
+        if eng is None and self.architecture == LINKNET:
+            from .engine_linknet import LinkNetEngine, LinkNetEngineF32
+            if self.infer_dtype == torch.float32:
+                eng = LinkNetEngineF32(self.dim, self.levels, self.base, self.num_channels, self.num_classes, dev)
+            else:
+                eng = LinkNetEngine(self.dim, self.levels, self.base, self.num_channels, self.num_classes, self.infer_dtype, dev)
+            self._engines = {dev: eng}
+            self._packed_sig = None
         if eng is None and self.architecture == NESTED:
             from .engine_nested import NestedEngine, NestedEngineF32
             if self.infer_dtype == torch.float32:
