@@ -754,6 +754,66 @@ int iunet_lk_bn_relu_add(int dtype, const void* y, long long y_ss, const void* s
 int iunet_lk_f32_conv_fwd(int nd, int kind, const void* x, long long x_ss, void* y, long long y_ss, const void* wpk, const void* bias,
                           const void* skip, long long skip_ss, int N, int D, int H, int W, int Cin, int Cout, void* stream);
 
+/* ---- DeepLabV3 decoder (csrc/deeplab.hip; unet.param_shapes(..., architecture='DeepLabV3')) -------------------------------------------
+ * Gathered implicit GEMMs over NHWC8c tensors with sample strides.  A conv is a list of taps: rate 0 = a 1x1 conv, rate r > 0 = a 3^d conv
+ * with dilation r and padding r, of which only the taps whose offset (k - 1) r is inside the grid on every axis are kept (the others read
+ * zero padding only).  Operators are packed with every tap, [rows][ksz^d * Cin] (tap-major, channel-minor). */
+/* number of kept taps of a rate-r conv on a D x H x W grid (-1: bad arguments) */
+int iunet_dl_num_taps(int nd, int rate, int D, int H, int W);
+/* w [Cout][Cin_tot][ksz^d] fp32, channels ci_off .. ci_off + Cin.  mode 0: the forward operator, dst[co][k_off + kidx Cin + ci] (a non-NULL
+ * gamma folds an eval-mode BatchNorm, bias_out = beta - mean * scale); mode 1: the data-gradient operator, dst[ci][k_off + kidx Cout + co]
+ * with the flipped kernel.  ld: the row length of dst.  dtype 0 f16, 1 bf16, 2 f32. */
+int iunet_dl_pack(int dtype, int nd, int mode, int ksz, const void* w, const void* gamma, const void* beta, const void* mean, const void* var,
+                  float eps, void* dst, void* bias_out, int Cout, int Cin, int Cin_tot, int ci_off, int k_off, int ld, void* stream);
+int iunet_dl_stats_parts(int N, int D, int H, int W, int Cout);
+/* y = sum over nbr branches (rates[b], input channels cbase[b] .. + Cin, operator columns colbase[b] + kidx Cin) of the gathered product,
+ * optionally through relu(in_scale x + in_shift) in the loads, + psb[n][co] * psb_scale (a per-sample bias, NULL: none).  epi 0: raw,
+ * with stats rows ([iunet_dl_stats_parts][Cout][2]) where given; epi 1: relu(acc + bias). */
+int iunet_dl_conv_fwd(int dtype, int nd, const void* x, long long x_ss, void* y, long long y_ss, const void* wpk, int Kw, int nbr,
+                      const int* rates, const int* cbase, const int* colbase, const void* in_scale, const void* in_shift, const void* bias,
+                      const void* psb, float psb_scale, void* stats, int epi, int N, int D, int H, int W, int Cin, int Cout, void* stream);
+/* weight gradient of one conv (x: channels cbase .. + Cin of the input, through its activation where given), staged in LDS: dW[co][ci_off +
+ * ci][kidx] = alpha * the sum over the batch, fp32, pruned taps zero; slab: iunet_dl_wgrad_slab_floats floats. */
+long long iunet_dl_wgrad_slab_floats(int nd, int rate, int N, int D, int H, int W, int Cin, int Cout);
+int iunet_dl_wgrad(int dtype, int nd, int rate, const void* x, long long x_ss, int cbase, const void* dy, long long dy_ss, const void* x_scale,
+                   const void* x_shift, void* slab, void* dW, int Cin_tot, int ci_off, float alpha, int N, int D, int H, int W, int Cin, int Cout,
+                   void* stream);
+/* fp32 form (planar fp32, operator of iunet_dl_pack dtype 2 with the BatchNorm folded): y = relu(acc + psb[n][co] + bias[co]) */
+int iunet_dl_f32_conv_fwd(int nd, int rate, const void* x, long long x_ss, void* y, long long y_ss, const void* wpk, int Kw, const void* bias,
+                          const void* psb, int N, int D, int H, int W, int Cin, int Cout, void* stream);
+/* out[n][c] = scale * the sum over the grid of x[n][c]; dtype 0 f16 / 1 bf16 (NHWC8c) or 2 (planar fp32) */
+int iunet_dl_chansum(int dtype, const void* x, long long x_ss, void* out, float scale, int C, int N, long long vox, void* stream);
+/* pooling branch: ypool = Wpool mean (stats rows [N][C][2] for iunet_bn_finalize where given); bp = relu(scale ypool + shift) (scale NULL:
+ * eval, folded from the running statistics); psb[n][c] = sum_j Wproj[c][4C + j] bp[n][j] (x the projection's eval BatchNorm scale where
+ * pgamma is given).  Wproj: [C][5C]. */
+int iunet_dl_pool_gemv(const void* mean, const void* wpool, void* ypool, void* stats, int N, int Cb, int C, void* stream);
+int iunet_dl_pool_psb(const void* ypool, const void* scale, const void* shift, const void* gamma, const void* beta, const void* rmean,
+                      const void* rvar, float eps, void* bp, const void* wproj, const void* pgamma, const void* pvar, void* psb, int N, int C,
+                      void* stream);
+/* its backward from dpsb[n][c] (the projection's raw-output gradient summed over the grid): dWproj[:, 4C:5C], the BatchNorm's dgamma /
+ * dbeta (batch statistics), dWpool and dxmean[n][ci]; scratch: 2 N C floats */
+int iunet_dl_pool_bwd(const void* dpsb, const void* bp, const void* ypool, const void* mean, const void* invstd, const void* gamma,
+                      const void* wproj, const void* wpool, const void* xmean, void* dwproj, void* dgamma, void* dbeta, void* dwpool,
+                      void* dxmean, void* scratch, int N, int Cb, int C, void* stream);
+/* mode 0: out = T(T(relu(scale y + shift)) * mask / (1 - p)); mode 1: out = T(y * mask / (1 - p)).  mask uint8 [N][C][vox] or NULL (all kept) */
+int iunet_dl_dropout(int dtype, int mode, const void* y, long long y_ss, void* out, long long out_ss, const void* scale, const void* shift,
+                     const void* mask, float p, int C, int N, long long vox, void* stream);
+/* coarse fp32 logits [N][ncls][Dc][Hc][Wc] upsampled x s (bilinear / trilinear, align_corners=True), then iunet_head_fwd's output contract */
+int iunet_dl_up_head(int nd, const void* lc, int ncls, int Dc, int Hc, int Wc, int s, void* logits, void* probs, void* cls,
+                     const long long* out_strides, float divisor, int accumulate, int N, void* stream);
+/* training: the upsampled logits' softmax + loss sums + loss / metrics / coefficients (iunet_head_loss_fwd's out4 / coef); the backward
+ * writes the fine dlogits (dfine, N ncls vox floats), then the interpolation's adjoint as a gather into dcoarse (tmp: N ncls Df Hf Wc floats);
+ * lscale: the device loss scale */
+int iunet_dl_up_loss_num_parts(int N, long long vox);
+int iunet_dl_up_loss_fwd(int nd, const void* lc, int ncls, int Dc, int Hc, int Wc, int s, const void* target, const void* weight, int tdtype,
+                         int kind, void* slab, void* out4, void* coef, int N, void* stream);
+int iunet_dl_up_loss_bwd(int nd, const void* lc, int ncls, int Dc, int Hc, int Wc, int s, const void* target, const void* weight, int tdtype,
+                         const void* coef, const void* lscale, void* dfine, void* tmp, void* dcoarse, int N, void* stream);
+/* head backward from coarse fp32 dlogits [N][ncls][vox]: dx = W^T dl (NHWC8c), dW [ncls][C], db; slab: iunet_dl_head_bwd_parts (C/8 + 1) 80 floats */
+int iunet_dl_head_bwd_parts(int N, long long vox);
+int iunet_dl_head_bwd(int dtype, const void* x, long long x_ss, int C, const void* w, const void* dl, int ncls, void* dx, long long dx_ss, void* slab,
+                      void* dw, void* db, int N, long long vox, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

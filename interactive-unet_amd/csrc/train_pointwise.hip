@@ -3,32 +3,11 @@
 // backward, max-pool backward, slab reductions, AdamW.  All reductions go through
 // per-block partial slabs summed in a fixed order (deterministic, no float atomics).
 #include "common.h"
+#include "loss_terms.h"
 
 namespace {
 
 template <typename T> using V8T = typename Vec8<T>::type;
-
-__device__ __forceinline__ float block_sum_256(float v, float* red /* [4] */) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
-// Block reduction of NV per-thread values with ONE barrier: wave shuffles, then 4 wave
-// partials through LDS (lds: [4][NV] floats), thread i < NV writes out[i].  Fixed order.
-template <int NV>
-__device__ __forceinline__ void block_reduce_store(const float (&vals)[NV], float* lds, float* out) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const float v = wave_sum(vals[i]);
-    if (lane == 0) lds[wave * NV + i] = v;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < NV; i += 256) out[i] = lds[i] + lds[NV + i] + lds[2 * NV + i] + lds[3 * NV + i];
-}
 
 // ------------------------------------------------------------------ BN statistics -> scale/shift
 // slab [nparts][C][2] (sum, sumsq of the raw conv output).  One block per channel.
@@ -515,10 +494,6 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ 
 
 // ------------------------------------------------------------------ fused head + softmax + loss
 // targets / weights: [N][ncls][vox] contiguous, f16 (tdtype 1) or f32 (tdtype 0).
-__device__ __forceinline__ float load_t(const void* p, long long off, int dt) {
-  return dt == 0 ? ((const float*)p)[off] : (float)((const f16*)p)[off];
-}
-
 struct HeadLossParams {
   const void* x; long long x_ss; int planes;
   const float* w; const float* bias;
@@ -574,24 +549,7 @@ __global__ __launch_bounds__(256) void head_loss_fwd_kernel(HeadLossParams p) {
         for (int c = 0; c < NCLS; ++c) l[c] = fmaf(a, p.w[c * p.planes * 8 + pl * 8 + j], l[c]);
       }
     }
-    float mx = l[0];
-#pragma unroll
-    for (int c = 1; c < NCLS; ++c) mx = fmaxf(mx, l[c]);
-    float e[NCLS], s = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCLS; ++c) { e[c] = __expf(l[c] - mx); s += e[c]; }
-    const float inv = 1.f / s;
-#pragma unroll
-    for (int c = 0; c < NCLS; ++c) {
-      const float pr = e[c] * inv;
-      const long long to = ((long long)n * NCLS + c) * p.vox + v;
-      const float y = load_t(p.target, to, p.tdtype);
-      const float w = p.weight ? load_t(p.weight, to, p.tdtype) : 1.f;
-      const float ry = rintf(y), rp = rintf(pr);
-      acc[c][0] += w; acc[c][1] += w * y; acc[c][2] += w * pr; acc[c][3] += w * y * pr;
-      acc[c][4] += w * y * __logf(pr + 1e-12f);
-      acc[c][5] += w * ry; acc[c][6] += w * rp; acc[c][7] += w * ry * rp;
-    }
+    loss_sums<NCLS>(l, p.target, p.weight, p.tdtype, n, p.vox, v, acc);
   }
   __shared__ float red[4 * NCLS * 8];
   const long long part = (long long)n * gridDim.x + blockIdx.x;

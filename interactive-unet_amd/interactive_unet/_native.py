@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get('IUNET_LIB') or os.path.join(os.path.dirname(_HERE), '
 _lib = None
 
 c_void_p, c_int, c_ll, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
+_IP = ctypes.POINTER(c_int)
 
 # name -> argtypes (all functions return int status except where noted)
 _SIGS = {
@@ -250,13 +251,31 @@ _SIGS = {
     'iunet_lk_bn_relu_add': [c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_int, c_int, c_ll, c_void_p],
     'iunet_lk_f32_conv_fwd': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_ll,
                               c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    # ---- DeepLabV3 decoder (csrc/deeplab.hip)
+    'iunet_dl_pack': [c_int, c_int, c_int, c_int] + [c_void_p] * 5 + [c_float, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p],
+    'iunet_dl_stats_parts': [c_int] * 5,
+    'iunet_dl_conv_fwd': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_int, c_int, _IP, _IP, _IP, c_void_p, c_void_p, c_void_p,
+                          c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    'iunet_dl_wgrad': [c_int, c_int, c_int, c_void_p, c_ll, c_int, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                       c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    'iunet_dl_f32_conv_fwd': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p,
+                              c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    'iunet_dl_chansum': [c_int, c_void_p, c_ll, c_void_p, c_float, c_int, c_int, c_ll, c_void_p],
+    'iunet_dl_pool_gemv': [c_void_p] * 4 + [c_int] * 3 + [c_void_p],
+    'iunet_dl_pool_psb': [c_void_p] * 7 + [c_float] + [c_void_p] * 5 + [c_int, c_int, c_void_p],
+    'iunet_dl_pool_bwd': [c_void_p] * 15 + [c_int] * 3 + [c_void_p],
+    'iunet_dl_dropout': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_ll, c_void_p],
+    'iunet_dl_up_head': [c_int, c_void_p] + [c_int] * 5 + [c_void_p] * 3 + [ctypes.POINTER(c_ll), c_float, c_int, c_int, c_void_p],
+    'iunet_dl_up_loss_fwd': [c_int, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    'iunet_dl_up_loss_bwd': [c_int, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_void_p],
+    'iunet_dl_head_bwd': [c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_int, c_void_p, c_ll] + [c_void_p] * 3 + [c_int, c_ll, c_void_p],
 }
 # functions that return a size / count instead of a status
 _INT_RETURN = ['iunet_pack_desc_bytes', 'iunet_augment_desc_bytes', 'iunet_x2_prep_desc_bytes']
-_INT_RETURN_ARGS = {'iunet_zoom_nearest_len': [c_int, ctypes.c_double], 'iunet_x2_convT_kc': [c_int], 'iunet_x2m_head_fusable': [c_int, c_int], 'iunet_x2m_pool_fusable': [c_int, c_int], 'iunet_x2m_first_stage_fusable': [c_int] * 6, 'iunet_x2_pack_mode': [c_int], 'iunet_f8_pack_order': [c_int, c_int]}
+_INT_RETURN_ARGS = {'iunet_dl_num_taps': [c_int] * 5, 'iunet_dl_up_loss_num_parts': [c_int, c_ll], 'iunet_dl_head_bwd_parts': [c_int, c_ll], 'iunet_zoom_nearest_len': [c_int, ctypes.c_double], 'iunet_x2_convT_kc': [c_int], 'iunet_x2m_head_fusable': [c_int, c_int], 'iunet_x2m_pool_fusable': [c_int, c_int], 'iunet_x2m_first_stage_fusable': [c_int] * 6, 'iunet_x2_pack_mode': [c_int], 'iunet_f8_pack_order': [c_int, c_int]}
 _LL_RETURN = {'iunet_gn_precise_slab_bytes': [c_int, c_int, c_ll], 'iunet_net_eval_scratch_bytes': [c_void_p, c_int, c_int, c_int, c_int], 'iunet_x2m_w8_bytes': [c_int] * 2, 'iunet_x2m_w8_bytes_nd': [c_int] * 3, 'iunet_train_num_params': [c_void_p], 'iunet_train_packed_bytes': [c_void_p], 'iunet_train_workspace_bytes': [c_void_p, c_int, c_int, c_int, c_int], 'iunet_conv3_wgrad_slab_floats': [c_int] * 7, 'iunet_f32_pack_conv_elems': [c_int] * 3, 'iunet_f8_pack_conv3_bytes': [c_int] * 3, 'iunet_conv3_f8_workspace_elems': [c_int] * 7, 'iunet_pack_conv3_elems': [c_int] * 4,
               'iunet_pack_first_conv_elems': [c_int] * 3, 'iunet_slice_scatter_workspace_bytes': [c_int],
-              'iunet_lk_pack_elems': [c_int] * 4, 'iunet_lk_wgrad_slab_floats': [c_int] * 8,
+              'iunet_lk_pack_elems': [c_int] * 4, 'iunet_lk_wgrad_slab_floats': [c_int] * 8, 'iunet_dl_wgrad_slab_floats': [c_int] * 8,
               'iunet_net_num_params': [c_void_p], 'iunet_net_packed_bytes': [c_void_p], 'iunet_net_workspace_bytes': [c_void_p] + [c_int] * 4}
 
 

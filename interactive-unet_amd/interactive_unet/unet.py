@@ -3,8 +3,8 @@
 `.loss_function`, `.device`, `load_from_checkpoint(checkpoint_path=)`; the network itself is
 the native canonical U-Net (engine.py) instead of segmentation_models_pytorch.
 
-architecture='U-Net', 'U-Net++' (the canonical nested form: engine_nested.py, train_engine_nested.py) and 'LinkNet' (engine_linknet.py,
-train_engine_linknet.py) exist natively;
+architecture='U-Net', 'U-Net++' (the canonical nested form: engine_nested.py, train_engine_nested.py), 'LinkNet' (engine_linknet.py,
+train_engine_linknet.py) and 'DeepLabV3' (engine_deeplab.py, train_engine_deeplab.py) exist natively;
 `encoder_name` is accepted and ignored (the canonical nets have their own plain conv encoder), `pretrained` is a no-op with a warning (no imagenet
 weights for a from-scratch encoder; no network access).  Extra keyword arguments (dim, levels,
 base, act_dtype, infer_dtype) select the 3-D / wider variants of BASELINE.json's configs.
@@ -38,7 +38,8 @@ _ACT_NAME = {torch.float16: 'fp16', torch.bfloat16: 'bf16', torch.float32: 'fp32
 
 NESTED = 'U-Net++'
 LINKNET = 'LinkNet'
-ARCHITECTURES = ('U-Net', NESTED, LINKNET)
+DEEPLAB = 'DeepLabV3'
+ARCHITECTURES = ('U-Net', NESTED, LINKNET, DEEPLAB)
 
 
 def nested_nodes(levels):
@@ -47,12 +48,14 @@ def nested_nodes(levels):
     return [(i, j) for j in range(1, levels) for i in range(levels - j)]
 
 
-def param_shapes(dim=2, levels=4, base=32, cin=1, ncls=2, architecture='U-Net'):
+def param_shapes(dim=2, levels=4, base=32, cin=1, ncls=2, architecture='U-Net', decoder_channels=256):
     """Ordered {name: shape} of the canonical network (same names as the oracle's definition).  architecture='U-Net++': the
     nested form (Zhou et al. 2018) on the same stage -- the encoder `enc{i}`, then `dec{i}_{j}` in nested_nodes order, each with
     its transposed conv ch[i+1] -> ch[i] and a stage (j + 1) ch[i] -> ch[i].  architecture='LinkNet': the encoder, then for l = L-2 .. 0
     the block dec{l} (conv1 1x1 ch[l+1] -> m, ConvTranspose k4 s2 p1 m -> m, conv2 1x1 m -> ch[l], m = ch[l+1] / 4, a BatchNorm after
-    each, no conv bias), then the head."""
+    each, no conv bias), then the head.  architecture='DeepLabV3': the encoder, then the ASPP on ch[L-1] (aspp.b0 1x1, aspp.b1..b3 dilated
+    3^d, aspp.pool 1x1 after the global mean, aspp.project 1x1 over the 5 C concat; C = decoder_channels), dec.conv 3^d C -> C, each conv
+    without bias and with a BatchNorm `<prefix>.bn`, then the head C -> ncls."""
     if architecture not in ARCHITECTURES:
         raise NotImplementedError(f'architecture {architecture!r}: the native networks are {ARCHITECTURES}')
     ch = [base * 2 ** l for l in range(levels)]
@@ -66,6 +69,16 @@ def param_shapes(dim=2, levels=4, base=32, cin=1, ncls=2, architecture='U-Net'):
                 shapes[f'{prefix}.bn{j}.{k}'] = (b,)
     for l in range(levels):
         stage(f'enc{l}', cin if l == 0 else ch[l - 1], ch[l])
+    if architecture == DEEPLAB:
+        C, Cb = decoder_channels, ch[-1]
+        for prefix, shp in (('aspp.b0', (C, Cb) + k1), ('aspp.b1', (C, Cb) + k3), ('aspp.b2', (C, Cb) + k3), ('aspp.b3', (C, Cb) + k3),
+                            ('aspp.pool', (C, Cb) + k1), ('aspp.project', (C, 5 * C) + k1), ('dec', (C, C) + k3)):
+            shapes[f'{prefix}.conv.weight'] = shp
+            for k in ('weight', 'bias', 'running_mean', 'running_var'):
+                shapes[f'{prefix}.bn.{k}'] = (C,)
+        shapes['head.weight'] = (ncls, C) + k1
+        shapes['head.bias'] = (ncls,)
+        return shapes
     if architecture == LINKNET:
         k4 = (4,) * dim
         for l in range(levels - 2, -1, -1):
@@ -127,6 +140,35 @@ def _check_linknet(levels, base, cin, ncls, act_dtype, weight_dtype, norm, infer
         raise NotImplementedError(f'LinkNet with {levels} levels, base {base}, {cin} input channels, {ncls} classes: {what}')
 
 
+def _check_deeplab(levels, base, cin, ncls, act_dtype, weight_dtype, norm, infer_dtype, infer_policy, decoder_channels, rates):
+    """The combinations the native DeepLabV3 supports: BatchNorm, 16-bit training (fp16 / bf16), prediction in fp32 (default) or fp16 /
+    bf16, 2 .. 6 levels, base a multiple of 32, 1 .. 4 input channels, 2 .. 10 classes, decoder_channels a multiple of 32 in 32 .. 512 and
+    three positive integer atrous rates."""
+    what = ("DeepLabV3 supports norm='batch', act_dtype None / 'fp16' / 'bf16' (training), infer_dtype None / 'fp32' / 'fp16' / "
+            "'bf16' (prediction), 2 .. 6 levels, base a multiple of 32, 1 .. 4 input channels, 2 .. 10 classes, decoder_channels a "
+            "multiple of 32 in 32 .. 512 and three positive integer decoder_atrous_rates")
+    if norm != 'batch':
+        raise NotImplementedError(f'DeepLabV3 with norm={norm!r} (GroupNorm): {what}')
+    if weight_dtype is not None:
+        raise NotImplementedError(f'DeepLabV3 with weight_dtype={weight_dtype!r} (fp8 weights): {what}')
+    if act_dtype is not None and _ACT.get(act_dtype) not in (torch.float16, torch.bfloat16):
+        raise NotImplementedError(f'DeepLabV3 with act_dtype={act_dtype!r} (the fp32 training form / split precision): {what}')
+    if infer_dtype is not None and _ACT.get(infer_dtype) not in (torch.float32, torch.float16, torch.bfloat16):
+        raise NotImplementedError(f'DeepLabV3 with infer_dtype={infer_dtype!r} (split precision): {what}')
+    if infer_policy is not None:
+        raise NotImplementedError(f'DeepLabV3 with infer_policy={infer_policy!r} (split-precision forms): {what}')
+    if not (2 <= levels <= 6) or base % 32 or not (1 <= cin <= 4) or not (2 <= ncls <= 10):
+        raise NotImplementedError(f'DeepLabV3 with {levels} levels, base {base}, {cin} input channels, {ncls} classes: {what}')
+    if not isinstance(decoder_channels, int) or decoder_channels % 32 or not (32 <= decoder_channels <= 512):
+        raise NotImplementedError(f'DeepLabV3 with decoder_channels={decoder_channels!r}: {what}')
+    try:
+        ok = len(rates) == 3 and all(isinstance(r, int) and not isinstance(r, bool) and r > 0 for r in rates)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise NotImplementedError(f'DeepLabV3 with decoder_atrous_rates={rates!r}: {what}')
+
+
 def _is_buffer(name):
     return name.endswith('running_mean') or name.endswith('running_var')
 
@@ -162,15 +204,20 @@ class UNet(nn.Module):
     def __init__(self, lr=0.0001, num_channels=1, num_classes=2, loss_function=metrics.mcc_ce_loss,
                  architecture='U-Net', encoder_name='mit_b0', pretrained=True,
                  dim=2, levels=4, base=32, act_dtype=None, weight_dtype=None, norm='batch', groups=8, infer_dtype=None,
-                 act_quant=None, infer_policy=None):
+                 act_quant=None, infer_policy=None, decoder_channels=256, decoder_atrous_rates=(12, 24, 36), decoder_aspp_dropout=0.5):
         super().__init__()
         if architecture not in ARCHITECTURES:
-            raise NotImplementedError(f"architecture {architecture!r}: only 'U-Net', 'U-Net++' and 'LinkNet' have a native MI355X "
+            raise NotImplementedError(f"architecture {architecture!r}: only 'U-Net', 'U-Net++', 'LinkNet' and 'DeepLabV3' have a native MI355X "
                                       f"implementation (the reference builds the others through smp, unet.py:33-54)")
         if architecture == NESTED:
             _check_nested(levels, act_dtype, weight_dtype, norm, infer_dtype, infer_policy)
         if architecture == LINKNET:
             _check_linknet(levels, base, num_channels, num_classes, act_dtype, weight_dtype, norm, infer_dtype, infer_policy)
+        if architecture == DEEPLAB:
+            _check_deeplab(levels, base, num_channels, num_classes, act_dtype, weight_dtype, norm, infer_dtype, infer_policy,
+                           decoder_channels, decoder_atrous_rates)
+            if not (0.0 <= float(decoder_aspp_dropout) < 1.0):
+                raise ValueError(f'decoder_aspp_dropout must be in [0, 1), got {decoder_aspp_dropout!r}')
         if pretrained:
             warnings.warn('pretrained=True ignored: the native U-Net encoder is trained from scratch')
         self.hparams = dict(lr=lr, num_channels=num_channels, num_classes=num_classes,
@@ -181,6 +228,12 @@ class UNet(nn.Module):
                             weight_dtype=weight_dtype, norm=norm, groups=groups,
                             infer_dtype=None if infer_dtype is None else _ACT_NAME[_ACT[infer_dtype]], act_quant=act_quant,
                             infer_policy=infer_policy)
+        self.decoder_channels, self.decoder_atrous_rates, self.decoder_aspp_dropout = None, None, None
+        if architecture == DEEPLAB:         # (only DeepLabV3 modules carry these: the other checkpoints stay as they were)
+            self.decoder_channels, self.decoder_atrous_rates = decoder_channels, tuple(int(r) for r in decoder_atrous_rates)
+            self.decoder_aspp_dropout = float(decoder_aspp_dropout)
+            self.hparams.update(decoder_channels=decoder_channels, decoder_atrous_rates=list(self.decoder_atrous_rates),
+                                decoder_aspp_dropout=self.decoder_aspp_dropout)
         self.lr = lr
         self.loss_function = loss_function
         self.dim, self.levels, self.base = dim, levels, base
@@ -191,7 +244,7 @@ class UNet(nn.Module):
         self.act_dtype = torch.float16 if act_dtype is None else _ACT[act_dtype]
         if infer_dtype is not None:
             self.infer_dtype = _ACT[infer_dtype]
-        elif architecture in (NESTED, LINKNET):
+        elif architecture in (NESTED, LINKNET, DEEPLAB):
             self.infer_dtype = torch.float32   # these nets predict in the fp32 form (within 1e-3 of the CPU fp32 logits)
         elif act_dtype is None and weight_dtype is None:
             self.infer_dtype = X2              # (GroupNorm networks too: engine_auto runs them in the full fp16x2 form)
@@ -210,7 +263,8 @@ class UNet(nn.Module):
             raise ValueError("norm must be 'batch' or 'group'")
         self.norm, self.groups = norm, groups
         self._names = []
-        for name, shp in param_shapes(dim, levels, base, num_channels, num_classes, architecture).items():
+        for name, shp in param_shapes(dim, levels, base, num_channels, num_classes, architecture,
+                                      decoder_channels if architecture == DEEPLAB else 256).items():
             t = torch.empty(shp, dtype=torch.float32)
             key = name.replace('.', '__')
             if _is_buffer(name):
@@ -230,12 +284,13 @@ class UNet(nn.Module):
             for name in self._names:
                 t = self.tensor(name)
                 shp = t.shape
-                if name.endswith('conv1.weight') or name.endswith('conv2.weight') or name == 'head.weight':
+                if name.endswith('conv1.weight') or name.endswith('conv2.weight') or name == 'head.weight' or name.endswith('.conv.weight'):
                     fan_in = shp[1] * math.prod(shp[2:])
                     t.copy_(torch.randn(shp, generator=g) * math.sqrt(2.0 / fan_in))      # He-normal
                 elif name.endswith('up.weight'):
                     t.copy_(torch.randn(shp, generator=g) * math.sqrt(1.0 / shp[0]))
-                elif name.endswith('running_var') or name.endswith('bn1.weight') or name.endswith('bn2.weight') or name.endswith('bn3.weight'):
+                elif name.endswith('running_var') or name.endswith('bn1.weight') or name.endswith('bn2.weight') or name.endswith('bn3.weight') \
+                        or name.endswith('.bn.weight'):
                     t.fill_(1.0)
                 else:
                     t.zero_()
@@ -274,6 +329,16 @@ class UNet(nn.Module):
             raise RuntimeError('the native U-Net runs on the GPU only: move the module with .to("cuda") '
                                '(there is no CPU fallback)')
         eng = self._engines.get(dev)
+        if eng is None and self.architecture == DEEPLAB:
+            from .engine_deeplab import DeepLabV3Engine, DeepLabV3EngineF32
+            args = (self.dim, self.levels, self.base, self.num_channels, self.num_classes)
+            kw = dict(decoder_channels=self.decoder_channels, rates=self.decoder_atrous_rates, device=dev)
+            if self.infer_dtype == torch.float32:
+                eng = DeepLabV3EngineF32(*args, **kw)
+            else:
+                eng = DeepLabV3Engine(*args, act_dtype=self.infer_dtype, **kw)
+            self._engines = {dev: eng}
+            self._packed_sig = None
         if eng is None and self.architecture == LINKNET:
             from .engine_linknet import LinkNetEngine, LinkNetEngineF32
             if self.infer_dtype == torch.float32:
