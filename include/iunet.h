@@ -814,6 +814,33 @@ int iunet_dl_head_bwd_parts(int N, long long vox);
 int iunet_dl_head_bwd(int dtype, const void* x, long long x_ss, int C, const void* w, const void* dl, int ncls, void* dx, long long dx_ss, void* slab,
                       void* dw, void* db, int N, long long vox, void* stream);
 
+/* ---- Segformer decoder (csrc/segformer.hip): Z = sum_l M_l R_l(X^l) + beta on the target grid T, M_l = W_f,l W_l, beta = sum_l W_f,l b_l.
+ * R_l resizes source l's grid to T (linear, align_corners=False); sources: x[i] (NHWC8c 16-bit, or planar fp32 for dtype 2), sample stride
+ * x_ss[i], cin[i] channels (multiples of 32), grid dims[3 i .. 3 i + 2]; optional per-source relu(sc x + sh) prologue (sc / sh tables or NULL).
+ * Operators are [Cout][K], K = sum cin, columns in source order. */
+/* operators from fp32 parameters: fuse weight wf [C][L C] (block j reads level L-1-j), mlp weights w[l] [C][ch[l]], biases b[l] [C].
+ * dst[c][k] = s_c (M)[c][k], dstT[k][c] = (M)[c][k] (or NULL), bias[c] = beta_c (gamma NULL, s_c = 1) or s_c (beta_c - mean_c) + beta_bn_c
+ * (the eval BatchNorm fold, s_c = gamma_c / sqrt(var_c + eps)); dtype 0 f16, 1 bf16, 2 f32 */
+int iunet_sf_pack(int dtype, int L, int C, const int* ch, const void* wf, const void* const* w, const void* const* b, const void* gamma,
+                  const void* beta, const void* mean, const void* var, float eps, void* dst, void* dstT, void* bias, void* stream);
+/* the resampling gather GEMM: epi 0 y = acc + bias (raw Z) with [iunet_sf_stats_parts][Cout][2] statistics rows where stats is given;
+ * epi 1 y = relu(acc + bias).  y on T: NHWC8c (dtype 0 / 1) or planar fp32 (dtype 2); Cout a multiple of 16 up to 512 */
+int iunet_sf_stats_parts(int N, int D, int H, int W);
+int iunet_sf_gemm(int dtype, int nd, int nsrc, const void* const* x, const long long* x_ss, const int* cin, const int* dims, const void* const* sc,
+                  const void* const* sh, const void* wpk, const void* bias, void* y, long long y_ss, void* stats, int epi, int N, int D, int H,
+                  int W, int Cout, void* stream);
+/* G[Cout][K] = sum over (n, t in T) of dz[n][co][t] R(x)[n][k][t], fp32; slab: iunet_sf_wgrad_slab_floats floats */
+long long iunet_sf_wgrad_slab_floats(int N, int D, int H, int W, int K, int Cout);
+int iunet_sf_wgrad(int dtype, int nd, int nsrc, const void* const* x, const long long* x_ss, const int* cin, const int* dims, const void* const* sc,
+                   const void* const* sh, const void* dz, long long dz_ss, void* slab, void* G, int N, int D, int H, int W, int Cout, void* stream);
+/* dx = R^T(u): u on T (Dt Ht Wt), dx on the source grid (Ds Hs Ws), C channels, NHWC8c; fp32 sum, one rounding (dx is overwritten) */
+int iunet_sf_adjoint(int dtype, int nd, const void* u, long long u_ss, int Dt, int Ht, int Wt, void* dx, long long dx_ss, int Ds, int Hs, int Ws,
+                     int C, int N, void* stream);
+/* parameter gradients from G [C][K] and rs [N][C] (r = sum_n rs): dw[l] = W_f,l^T G_l, db[l] = W_f,l^T r, dwf[c][(L-1-l) C + j] =
+ * (G_l W_l^T)[c][j] + r_c b_l[j]; all fp32, overwritten */
+int iunet_sf_param_grads(int L, int C, const int* ch, const void* wf, const void* const* w, const void* const* b, const void* G, const void* rs,
+                         int N, void* const* dw, void* const* db, void* dwf, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,699 @@
+// Segformer decoder (Xie et al. 2021, smp's SegformerDecoder on this project's encoder), on the target grid T = the input grid / 4:
+//   P_l = W_l X^l + b_l (per voxel), R_l = resize of level l's grid to T (linear, align_corners=False), concat deepest first,
+//   Z = W_f concat (1x1, no bias), F = relu(bn(Z)), logits_T = head(F), logits = x4 (align_corners=True), softmax.
+//
+// Every step up to Z is linear and interpolation weights sum to 1 (also where the borders clamp), so with W_f,l the block of the fuse
+// operator that reads level l:
+//   Z = sum_l M_l R_l(X^l) + beta,   M_l = W_f,l W_l,   beta = sum_l W_f,l b_l.
+// The forward is ONE GEMM [C] x [K = sum ch[l]] whose B operand is gathered resampled straight out of the encoder tensors: no C-channel
+// tensor finer than T and no L C-channel concat ever exists.  The backward follows from the same identity (dZ from fuse.bn's backward,
+// r = sum over (n, t) of dZ):
+//   G_l = dZ R_l(X^l)^T (sf_wgrad_kernel), dW_l = W_f,l^T G_l, dW_f,l = G_l W_l^T + r b_l^T, db_l = W_f,l^T r (sf_param_grad_kernel),
+//   dX^l = R_l^T(M_l^T dZ) (M^T dZ by iunet_dl_conv_fwd at rate 0 with the transposed operator, R^T by sf_adjoint_kernel).
+//
+// Resampling.  PyTorch's linear interpolation with align_corners=False and an output size: per axis src = max(0, (t + 0.5) in / out - 0.5),
+// i0 = floor(src), i1 = i0 + (i0 < in - 1), weights (1 - lambda, lambda), lambda = src - i0.  The sources are the encoder's NHWC8c tensors
+// (16-bit) or planar fp32 tensors, each with its own grid: the kernels take any source grid, so the ratios -2 .. +3 of the network and
+// odd grids are one code path.  The taps are summed in fp32 in a fixed order and rounded once to the MFMA input type.  An optional
+// per-source relu(scale x + shift) prologue applies a BatchNorm + ReLU to each tap with iunet_bn_relu_fwd's bits before weighting it.
+//
+// All reductions are fixed-order (per-workgroup rows / slabs, then ordered sums): no float atomics, two identical calls are bit-identical.
+#include <type_traits>
+
+#include "common.h"
+#include "../../include/iunet.h"
+
+namespace {
+
+template <typename T> using V8T = typename Vec8<T>::type;
+typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+template <typename T> struct Vec4;
+template <> struct Vec4<f16> { typedef f16x4_t type; };
+template <> struct Vec4<bf16> { typedef bf16x4_t type; };
+
+constexpr int SF_MAXS = 6;           // sources (levels) per launch
+constexpr int SF_COLS = 64;          // output voxels per workgroup of the forward GEMM
+constexpr int SF_MAXC = 512;         // output channels (all of them in one workgroup: the gathered tile is built once)
+constexpr int SF_LD16 = 40;          // LDS row stride (elements) of a [rows][32] 16-bit operand image
+constexpr int SF_LD32 = 36;          // ... of a [rows][32] fp32 image
+
+struct SfSrc {
+  const void* x; long long x_ss;     // NHWC8c (16-bit) or planar [C][vox] (fp32), sample stride in elements
+  const float* sc; const float* sh;  // optional relu(sc x + sh) prologue
+  int C, koff;                       // channels, first operator column
+  int D, H, W;                       // the source's grid
+};
+
+struct SfSrcs {
+  int n;
+  SfSrc s[SF_MAXS];
+};
+
+struct SfAx {
+  int i0, i1;
+  float l1;
+};
+
+// PyTorch's upsample_linear source index (align_corners=False, output size given)
+__device__ __forceinline__ SfAx sf_axis(int t, int nout, int nin) {
+  const float scale = (float)nin / (float)nout;
+  float src = scale * ((float)t + 0.5f) - 0.5f;
+  src = src < 0.f ? 0.f : src;
+  SfAx a;
+  a.i0 = min((int)src, nin - 1);
+  a.i1 = a.i0 + (a.i0 < nin - 1 ? 1 : 0);
+  a.l1 = src - (float)a.i0;
+  return a;
+}
+
+template <typename T>
+__device__ __forceinline__ float sf_pro(float v, const SfSrc& s, int c) {
+  v = fmaxf(fmaf(s.sc[c], v, s.sh[c]), 0.f);
+  if constexpr (!std::is_same<T, float>::value) v = to_f32<T>(from_f32<T>(v));
+  return v;
+}
+
+// The 8 channels c0 .. c0 + 7 of source s resampled at the T voxel whose per-axis taps are ad / ah / aw (fp32 sum, fixed tap order)
+template <typename T, int ND, bool ACT>
+__device__ __forceinline__ void sf_sample(const SfSrc& s, int n, int c0, const SfAx& ad, const SfAx& ah, const SfAx& aw, float out[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) out[j] = 0.f;
+  const long long vs = (long long)s.D * s.H * s.W;
+#pragma unroll
+  for (int td = 0; td < (ND == 3 ? 2 : 1); ++td) {
+    const int id = ND == 3 ? (td ? ad.i1 : ad.i0) : 0;
+    const float wd = ND == 3 ? (td ? ad.l1 : 1.f - ad.l1) : 1.f;
+#pragma unroll
+    for (int th = 0; th < 2; ++th) {
+      const int ih = th ? ah.i1 : ah.i0;
+      const float wh = wd * (th ? ah.l1 : 1.f - ah.l1);
+#pragma unroll
+      for (int tw = 0; tw < 2; ++tw) {
+        const int iw = tw ? aw.i1 : aw.i0;
+        const float wgt = wh * (tw ? aw.l1 : 1.f - aw.l1);
+        const long long vox = ((long long)id * s.H + ih) * s.W + iw;
+        if constexpr (std::is_same<T, float>::value) {
+          const float* xs = (const float*)s.x + (long long)n * s.x_ss + (long long)c0 * vs + vox;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            float v = xs[(long long)j * vs];
+            if constexpr (ACT) v = sf_pro<T>(v, s, c0 + j);
+            out[j] = fmaf(wgt, v, out[j]);
+          }
+        } else {
+          const V8T<T> b = *(const V8T<T>*)((const T*)s.x + (long long)n * s.x_ss + ((long long)(c0 >> 3) * vs + vox) * 8);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            float v = to_f32<T>(b[j]);
+            if constexpr (ACT) v = sf_pro<T>(v, s, c0 + j);
+            out[j] = fmaf(wgt, v, out[j]);
+          }
+        }
+      }
+    }
+  }
+}
+
+struct SfGemm {
+  SfSrcs src;
+  const void* wpk; int K;            // operator [Cout][K], K = sum of the sources' channels
+  const float* bias;                 // [Cout]: beta (epi 0) or the folded eval bias (epi 1)
+  void* y; long long y_ss;           // Z (epi 0) / F (epi 1) on T: NHWC8c T or planar fp32
+  float* stats;                      // [gridDim.x][Cout][2] or null (epi 0)
+  int D, H, W;                       // T
+  int Cout, epi;
+  long long cols;
+};
+
+// One workgroup = 64 T voxels x all Cout rows.  Per chunk of 32 operator columns (one source's channels) its 256 threads gather the
+// resampled B tile [64 voxels][32] (one 8-channel group of one voxel each) and copy the operator chunk [Cout][32] into LDS; wave w then
+// runs row tiles w, w + 4, ... against the 4 column tiles, both operands read from LDS.
+template <typename T, int ND, bool ACT>
+__global__ __launch_bounds__(256) void sf_gemm_kernel(SfGemm p) {
+  constexpr bool F32 = std::is_same<T, float>::value;
+  constexpr int LD = F32 ? SF_LD32 : SF_LD16;
+  extern __shared__ __attribute__((aligned(16))) unsigned char sf_smem[];
+  T* sB = (T*)sf_smem;                                 // [64][LD]
+  T* sA = sB + SF_COLS * LD;                           // [Cout][LD]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, l15 = lane & 15;
+  const long long vT = (long long)p.D * p.H * p.W;
+  const int ntile = p.Cout / 16;
+  // this thread's gather slot: voxel gc, channel group gg of the chunk
+  const int gc = threadIdx.x & 63, gg = threadIdx.x >> 6;
+  const long long gcol = (long long)blockIdx.x * SF_COLS + gc;
+  const bool gok = gcol < p.cols;
+  const long long gcc = gok ? gcol : 0;
+  const int gn = (int)(gcc / vT);
+  const long long gr = gcc - (long long)gn * vT;
+  const int gw = (int)(gr % p.W), gh = (int)((gr / p.W) % p.H), gd = (int)(gr / ((long long)p.W * p.H));
+  f32x4 acc[8][4];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[i][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int si = 0; si < p.src.n; ++si) {
+    const SfSrc& s = p.src.s[si];
+    SfAx ad, ah, aw;
+    ad = ND == 3 ? sf_axis(gd, p.D, s.D) : SfAx{0, 0, 0.f};
+    ah = sf_axis(gh, p.H, s.H);
+    aw = sf_axis(gw, p.W, s.W);
+    for (int c0 = 0; c0 < s.C; c0 += 32) {
+      float v[8];
+      if (gok) {
+        sf_sample<T, ND, ACT>(s, gn, c0 + gg * 8, ad, ah, aw, v);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = 0.f;
+      }
+      __syncthreads();                                 // the previous chunk's operands are consumed
+      if constexpr (F32) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sB[gc * LD + gg * 8 + j] = v[j];
+        const float* wk = (const float*)p.wpk + s.koff + c0;
+        for (int e = threadIdx.x; e < p.Cout * 8; e += 256) {
+          const int row = e >> 3, kk = (e & 7) * 4;
+          *(f32x4*)(sA + row * LD + kk) = *(const f32x4*)(wk + (long long)row * p.K + kk);
+        }
+      } else {
+        V8T<T> b;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) b[j] = from_f32<T>(v[j]);
+        *(V8T<T>*)(sB + gc * LD + gg * 8) = b;
+        const T* wk = (const T*)p.wpk + s.koff + c0;
+        for (int e = threadIdx.x; e < p.Cout * 4; e += 256) {
+          const int row = e >> 2, kk = (e & 3) * 8;
+          *(V8T<T>*)(sA + row * LD + kk) = *(const V8T<T>*)(wk + (long long)row * p.K + kk);
+        }
+      }
+      __syncthreads();
+      if constexpr (F32) {
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+          float bv[4];
+#pragma unroll
+          for (int t = 0; t < 4; ++t) bv[t] = sB[(t * 16 + l15) * LD + ks * 4 + q];
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            const int a = wave + 4 * i;
+            if (a < ntile) {
+              const float av = sA[(a * 16 + l15) * LD + ks * 4 + q];
+#pragma unroll
+              for (int t = 0; t < 4; ++t) acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[t], acc[i][t], 0, 0, 0);
+            }
+          }
+        }
+      } else {
+        V8T<T> bv[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) bv[t] = *(const V8T<T>*)(sB + (t * 16 + l15) * LD + q * 8);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int a = wave + 4 * i;
+          if (a < ntile) {
+            const V8T<T> av = *(const V8T<T>*)(sA + (a * 16 + l15) * LD + q * 8);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[i][t] = mfma16<T>(av, bv[t], acc[i][t]);
+          }
+        }
+      }
+    }
+  }
+  // epilogue: lane holds rows a*16 + q*4 + rr at column tile t, voxel l15
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int a = wave + 4 * i;
+    if (a >= ntile) continue;
+    const int co = a * 16 + q * 4;
+    float ssum[4] = {0.f, 0.f, 0.f, 0.f}, ssq[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const long long col = (long long)blockIdx.x * SF_COLS + t * 16 + l15;
+      if (col >= p.cols) continue;
+      const int n = (int)(col / vT);
+      const long long r = col - (long long)n * vT;
+      float o[4];
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const float v = acc[i][t][rr] + p.bias[co + rr];
+        if (p.epi == 0) {
+          o[rr] = v;
+          ssum[rr] += v;
+          ssq[rr] += v * v;
+        } else {
+          o[rr] = fmaxf(v, 0.f);
+        }
+      }
+      if constexpr (F32) {
+        float* ys = (float*)p.y + (long long)n * p.y_ss + r;
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) ys[(long long)(co + rr) * vT] = o[rr];
+      } else {
+        typename Vec4<T>::type ov;
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) ov[rr] = from_f32<T>(o[rr]);
+        *(typename Vec4<T>::type*)((T*)p.y + (long long)n * p.y_ss + ((long long)(co >> 3) * vT + r) * 8 + (co & 7)) = ov;
+      }
+    }
+    if (p.stats != nullptr) {
+      // the 16 voxels of a lane group (a fixed butterfly): one row per workgroup; each wave owns its rows
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        float s = ssum[rr], s2 = ssq[rr];
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) { s += __shfl_xor(s, o); s2 += __shfl_xor(s2, o); }
+        if (l15 == 0) {
+          p.stats[((long long)blockIdx.x * p.Cout + co + rr) * 2] = s;
+          p.stats[((long long)blockIdx.x * p.Cout + co + rr) * 2 + 1] = s2;
+        }
+      }
+    }
+  }
+}
+
+// ---- weight gradient G[Cout][K] = sum over (n, t) of dZ[co] R(X)[k]: a workgroup owns a 64 (co) x 64 (k) tile and one split of the
+// columns; per chunk of 32 T voxels its threads load dZ (8 channels of one voxel) and the resampled source (8 operator columns of one
+// voxel), write both into LDS transposed to [row][voxel], and each wave runs the 16 x 64 x 32 product from LDS.
+struct SfWg {
+  SfSrcs src;
+  const void* dz; long long dz_ss;
+  float* slab;
+  int D, H, W;
+  int Cout, K;
+  long long cols, chunks_per_split;
+};
+
+template <typename T, int ND, bool ACT>
+__global__ __launch_bounds__(256) void sf_wgrad_kernel(SfWg p) {
+  __shared__ __attribute__((aligned(16))) T sA[64 * SF_LD16];
+  __shared__ __attribute__((aligned(16))) T sB[64 * SF_LD16];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, l15 = lane & 15;
+  const int co0 = blockIdx.y * 64, kb = blockIdx.z * 64;
+  const long long vT = (long long)p.D * p.H * p.W;
+  const long long nchunks = (p.cols + 31) / 32;
+  const long long c_lo = (long long)blockIdx.x * p.chunks_per_split, c_hi = min(nchunks, c_lo + p.chunks_per_split);
+  const T* dz = (const T*)p.dz;
+  const int g = threadIdx.x >> 5, jc = threadIdx.x & 31;
+  const int co_l = co0 + g * 8, k_l = kb + g * 8;
+  const bool co_ok = co_l < p.Cout, k_ok = k_l < p.K;
+  int si = 0;
+  if (k_ok)
+    while (si + 1 < p.src.n && k_l >= p.src.s[si + 1].koff) ++si;
+  const SfSrc& s = p.src.s[si];
+  const int c0 = k_l - s.koff;
+  f32x4 acc[4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (long long ck = c_lo; ck < c_hi; ++ck) {
+    const long long col = ck * 32 + jc;
+    V8T<T> va, vb;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { va[j] = from_f32<T>(0.f); vb[j] = from_f32<T>(0.f); }
+    if (col < p.cols) {
+      const int n = (int)(col / vT);
+      const long long r = col - (long long)n * vT;
+      if (co_ok) va = *(const V8T<T>*)(dz + (long long)n * p.dz_ss + ((long long)(co_l >> 3) * vT + r) * 8);
+      if (k_ok) {
+        const int w = (int)(r % p.W), h = (int)((r / p.W) % p.H), d = (int)(r / ((long long)p.W * p.H));
+        const SfAx ad = ND == 3 ? sf_axis(d, p.D, s.D) : SfAx{0, 0, 0.f};
+        const SfAx ah = sf_axis(h, p.H, s.H), aw = sf_axis(w, p.W, s.W);
+        float v[8];
+        sf_sample<T, ND, ACT>(s, n, c0, ad, ah, aw, v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) vb[j] = from_f32<T>(v[j]);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { sA[(g * 8 + j) * SF_LD16 + jc] = va[j]; sB[(g * 8 + j) * SF_LD16 + jc] = vb[j]; }
+    __syncthreads();
+    const V8T<T> a = *(const V8T<T>*)(sA + (wave * 16 + l15) * SF_LD16 + q * 8);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const V8T<T> b = *(const V8T<T>*)(sB + (t * 16 + l15) * SF_LD16 + q * 8);
+      acc[t] = mfma16<T>(a, b, acc[t]);
+    }
+  }
+  float* out = p.slab + (long long)blockIdx.x * p.Cout * p.K;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int kk = kb + t * 16 + l15;
+    if (kk >= p.K) continue;
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const int co = co0 + wave * 16 + q * 4 + rr;
+      if (co < p.Cout) out[(long long)co * p.K + kk] = acc[t][rr];
+    }
+  }
+}
+
+int sf_wgrad_splits(long long cols, long long per_split_floats) {
+  const long long nchunks = (cols + 31) / 32;
+  long long s = (nchunks + 15) / 16;                  // at least 16 chunks (512 voxels) per split
+  if (s > 64) s = 64;
+  if (s < 1) s = 1;
+  while (s > 1 && s * per_split_floats > (8ll << 20)) s >>= 1;
+  return (int)s;
+}
+
+__global__ __launch_bounds__(256) void sf_wgrad_reduce_kernel(const float* __restrict__ slab, int splits, long long total, float* __restrict__ G) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  float s = 0.f;
+  for (int sp = 0; sp < splits; ++sp) s += slab[(long long)sp * total + i];
+  G[i] = s;
+}
+
+// ---- adjoint of the resize, as a gather: dx[n][c][p] = sum over T voxels t of w(t, p) u[n][c][t], w the product of the per-axis weights
+// (an axis where i0 == i1 at the border gives that sample both its weights).  One thread per (voxel p, 8 channels); fp32 sum, one rounding.
+__device__ __forceinline__ void sf_adj_range(int p, int nin, int nout, int& lo, int& hi) {
+  // the T indices whose taps can reach p: src(t) in [p - 1, p + 1), widened by one index on each side (the clamp at 0 included)
+  const float inv = (float)nout / (float)nin;
+  lo = (int)floorf(((float)p - 0.5f) * inv - 0.5f) - 1;
+  hi = (int)ceilf(((float)p + 1.5f) * inv - 0.5f) + 1;
+  if (p <= 1) lo = 0;
+  lo = max(lo, 0);
+  hi = min(hi, nout - 1);
+}
+
+__device__ __forceinline__ float sf_adj_w(int t, int p, int nout, int nin) {
+  const SfAx a = sf_axis(t, nout, nin);
+  return (a.i0 == p ? 1.f - a.l1 : 0.f) + (a.i1 == p ? a.l1 : 0.f);
+}
+
+template <typename T, int ND>
+__global__ __launch_bounds__(256) void sf_adjoint_kernel(const T* __restrict__ u, long long u_ss, int Dt, int Ht, int Wt, T* __restrict__ dx,
+                                                         long long dx_ss, int Ds, int Hs, int Ws, int C, int N) {
+  const long long vs = (long long)Ds * Hs * Ws, vT = (long long)Dt * Ht * Wt;
+  const long long total = (long long)N * (C / 8) * vs;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const long long r = i % vs;
+  const int pl = (int)((i / vs) % (C / 8)), n = (int)(i / (vs * (C / 8)));
+  const int pw = (int)(r % Ws), ph = (int)((r / Ws) % Hs), pd = (int)(r / ((long long)Ws * Hs));
+  int dlo = 0, dhi = 0, hlo, hhi, wlo, whi;
+  if (ND == 3) sf_adj_range(pd, Ds, Dt, dlo, dhi);
+  sf_adj_range(ph, Hs, Ht, hlo, hhi);
+  sf_adj_range(pw, Ws, Wt, wlo, whi);
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+  const T* us = u + (long long)n * u_ss + (long long)pl * vT * 8;
+  for (int td = dlo; td <= dhi; ++td) {
+    const float wd = ND == 3 ? sf_adj_w(td, pd, Dt, Ds) : 1.f;
+    if (wd == 0.f) continue;
+    for (int th = hlo; th <= hhi; ++th) {
+      const float wh = sf_adj_w(th, ph, Ht, Hs);
+      if (wh == 0.f) continue;
+      for (int tw = wlo; tw <= whi; ++tw) {
+        const float ww = sf_adj_w(tw, pw, Wt, Ws);
+        if (ww == 0.f) continue;
+        const float wgt = wd * wh * ww;
+        const V8T<T> v = *(const V8T<T>*)(us + (((long long)td * Ht + th) * Wt + tw) * 8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = fmaf(wgt, to_f32<T>(v[j]), acc[j]);
+      }
+    }
+  }
+  V8T<T> o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = from_f32<T>(acc[j]);
+  *(V8T<T>*)(dx + (long long)n * dx_ss + ((long long)pl * vs + r) * 8) = o;
+}
+
+// ---- the small fp32 operator kernels (C^2 sum ch MACs; one thread per output, sums in ascending index order)
+struct SfOps {
+  const float* wf;                   // fuse.conv.weight [C][L C] (block j reads level L-1-j)
+  const float* w[SF_MAXS];           // mlp{l}.weight [C][ch[l]]
+  const float* b[SF_MAXS];           // mlp{l}.bias [C]
+  int ch[SF_MAXS], koff[SF_MAXS];
+  int L, C, K;
+};
+
+__device__ __forceinline__ int sf_level(const SfOps& o, int k) {
+  int l = 0;
+  while (l + 1 < o.L && k >= o.koff[l + 1]) ++l;
+  return l;
+}
+
+// dst[c][k] = s_c sum_j W_f,l[c][j] W_l[j][k - koff_l] (s_c = the eval BatchNorm scale or 1); dstT[k][c] = the unscaled value;
+// bias[c] = beta_c (no fold) or s_c (beta_c - mean_c) + bn.bias_c
+template <typename OT>
+__global__ __launch_bounds__(256) void sf_pack_kernel(SfOps o, const float* gamma, const float* bnb, const float* mean, const float* var, float eps,
+                                                      OT* __restrict__ dst, OT* dstT, float* bias) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long nop = (long long)o.C * o.K;
+  if (i < nop) {
+    const int c = (int)(i / o.K), k = (int)(i - (long long)c * o.K);
+    const int l = sf_level(o, k), kk = k - o.koff[l];
+    const float* wf = o.wf + (long long)c * o.L * o.C + (long long)(o.L - 1 - l) * o.C;
+    float s = 0.f;
+    for (int j = 0; j < o.C; ++j) s = fmaf(wf[j], o.w[l][(long long)j * o.ch[l] + kk], s);
+    const float sc = gamma != nullptr ? gamma[c] / sqrtf(var[c] + eps) : 1.f;
+    dst[i] = (OT)(s * sc);
+    if (dstT != nullptr) dstT[(long long)k * o.C + c] = (OT)s;
+  } else if (i < nop + o.C && bias != nullptr) {
+    const int c = (int)(i - nop);
+    float s = 0.f;
+    for (int l = 0; l < o.L; ++l) {
+      const float* wf = o.wf + (long long)c * o.L * o.C + (long long)(o.L - 1 - l) * o.C;
+      for (int j = 0; j < o.C; ++j) s = fmaf(wf[j], o.b[l][j], s);
+    }
+    if (gamma != nullptr) {
+      const float sc = gamma[c] / sqrtf(var[c] + eps);
+      s = sc * (s - mean[c]) + bnb[c];
+    }
+    bias[c] = s;
+  }
+}
+
+// dW_l[j][k] = sum_c W_f,l[c][j] G[c][koff_l + k];  dW_f[c][(L-1-l) C + j] = sum_k G[c][koff_l + k] W_l[j][k] + r[c] b_l[j];
+// db_l[j] = sum_c W_f,l[c][j] r[c];  r[c] = sum_n rs[n][c] (ascending n)
+struct SfGrads {
+  float* dw[SF_MAXS];
+  float* db[SF_MAXS];
+  float* dwf;
+};
+
+__global__ __launch_bounds__(256) void sf_param_grad_kernel(SfOps o, SfGrads g, const float* __restrict__ G, const float* __restrict__ rs, int N) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long n1 = (long long)o.C * o.K, n2 = n1 + (long long)o.C * o.L * o.C, n3 = n2 + (long long)o.L * o.C;
+  const int LC = o.L * o.C;
+  if (i < n1) {
+    const int j = (int)(i / o.K), k = (int)(i - (long long)j * o.K);
+    const int l = sf_level(o, k), kk = k - o.koff[l];
+    const int col = (o.L - 1 - l) * o.C + j;
+    float s = 0.f;
+    for (int c = 0; c < o.C; ++c) s = fmaf(o.wf[(long long)c * LC + col], G[(long long)c * o.K + k], s);
+    g.dw[l][(long long)j * o.ch[l] + kk] = s;
+  } else if (i < n2) {
+    const long long e = i - n1;
+    const int c = (int)(e / LC), colj = (int)(e - (long long)c * LC);
+    const int l = o.L - 1 - colj / o.C, j = colj % o.C;
+    float s = 0.f;
+    const float* gr = G + (long long)c * o.K + o.koff[l];
+    const float* wl = o.w[l] + (long long)j * o.ch[l];
+    for (int k = 0; k < o.ch[l]; ++k) s = fmaf(gr[k], wl[k], s);
+    float r = 0.f;
+    for (int n = 0; n < N; ++n) r += rs[(long long)n * o.C + c];
+    g.dwf[e] = fmaf(r, o.b[l][j], s);
+  } else if (i < n3) {
+    const long long e = i - n2;
+    const int l = (int)(e / o.C), j = (int)(e % o.C);
+    const int col = (o.L - 1 - l) * o.C + j;
+    float s = 0.f;
+    for (int c = 0; c < o.C; ++c) {
+      float r = 0.f;
+      for (int n = 0; n < N; ++n) r += rs[(long long)n * o.C + c];
+      s = fmaf(o.wf[(long long)c * LC + col], r, s);
+    }
+    g.db[l][j] = s;
+  }
+}
+
+// ---- host-side argument checks shared by the entry points
+int sf_check_t(int nd, int N, int D, int H, int W) {
+  IUNET_REQUIRE(nd == 2 || nd == 3, "segformer: nd must be 2 or 3, got %d", nd);
+  IUNET_REQUIRE_GRID("segformer", N, D, H, W);
+  IUNET_REQUIRE(nd == 3 || D == 1, "segformer: 2-D tensors have D = 1");
+  return IUNET_OK;
+}
+
+int sf_build_srcs(SfSrcs& S, int nd, int nsrc, const void* const* x, const long long* x_ss, const int* cin, const int* dims,
+                  const void* const* sc, const void* const* sh, bool& act) {
+  IUNET_REQUIRE(nsrc >= 1 && nsrc <= SF_MAXS, "segformer: 1 .. %d sources, got %d", SF_MAXS, nsrc);
+  IUNET_REQUIRE(x && x_ss && cin && dims, "segformer: null source table");
+  IUNET_REQUIRE(!sc == !sh, "segformer: the prologue needs both scale and shift tables");
+  S.n = nsrc;
+  act = sc != nullptr;
+  int koff = 0;
+  for (int i = 0; i < nsrc; ++i) {
+    SfSrc& s = S.s[i];
+    IUNET_REQUIRE(x[i], "segformer: source %d is null", i);
+    IUNET_REQUIRE(cin[i] > 0 && cin[i] % 32 == 0, "segformer: source %d has %d channels (a positive multiple of 32)", i, cin[i]);
+    IUNET_REQUIRE(dims[3 * i] > 0 && dims[3 * i + 1] > 0 && dims[3 * i + 2] > 0 && (nd == 3 || dims[3 * i] == 1),
+                  "segformer: source %d has a bad grid %d x %d x %d", i, dims[3 * i], dims[3 * i + 1], dims[3 * i + 2]);
+    IUNET_REQUIRE(!act || (sc[i] && sh[i]), "segformer: source %d lacks its prologue scale / shift", i);
+    s.x = x[i]; s.x_ss = x_ss[i];
+    s.sc = act ? (const float*)sc[i] : nullptr; s.sh = act ? (const float*)sh[i] : nullptr;
+    s.C = cin[i]; s.koff = koff; s.D = dims[3 * i]; s.H = dims[3 * i + 1]; s.W = dims[3 * i + 2];
+    koff += cin[i];
+  }
+  return IUNET_OK;
+}
+
+int sf_build_ops(SfOps& o, int L, int C, const int* ch, const void* wf, const void* const* w, const void* const* b) {
+  IUNET_REQUIRE(L >= 1 && L <= SF_MAXS, "segformer: 1 .. %d levels, got %d", SF_MAXS, L);
+  IUNET_REQUIRE(C > 0 && C % 8 == 0, "segformer: C %d (a positive multiple of 8)", C);
+  IUNET_REQUIRE(ch && wf && w && b, "segformer: null pointer");
+  o.wf = (const float*)wf; o.L = L; o.C = C;
+  int koff = 0;
+  for (int l = 0; l < L; ++l) {
+    IUNET_REQUIRE(ch[l] > 0 && ch[l] % 8 == 0, "segformer: level %d has %d channels (a positive multiple of 8)", l, ch[l]);
+    IUNET_REQUIRE(w[l] && b[l], "segformer: level %d: null mlp weight / bias", l);
+    o.w[l] = (const float*)w[l]; o.b[l] = (const float*)b[l]; o.ch[l] = ch[l]; o.koff[l] = koff;
+    koff += ch[l];
+  }
+  o.K = koff;
+  return IUNET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int iunet_sf_pack(int dtype, int L, int C, const int* ch, const void* wf, const void* const* w, const void* const* b, const void* gamma,
+                  const void* beta, const void* mean, const void* var, float eps, void* dst, void* dstT, void* bias, void* stream) {
+  IUNET_REQUIRE(dtype >= 0 && dtype <= 2, "sf_pack: dtype must be 0 (f16), 1 (bf16) or 2 (f32), got %d", dtype);
+  SfOps o;
+  const int rc = sf_build_ops(o, L, C, ch, wf, w, b);
+  if (rc != IUNET_OK) return rc;
+  IUNET_REQUIRE(dst, "sf_pack: null operator");
+  IUNET_REQUIRE(!gamma || (beta && mean && var), "sf_pack: a BatchNorm fold needs gamma, beta, mean and var");
+  const long long total = (long long)C * o.K + C;
+  const dim3 grid((unsigned)((total + 255) / 256));
+#define SFP(OT) hipLaunchKernelGGL(sf_pack_kernel<OT>, grid, dim3(256), 0, (hipStream_t)stream, o, (const float*)gamma, (const float*)beta, \
+                                   (const float*)mean, (const float*)var, eps, (OT*)dst, (OT*)dstT, (float*)bias)
+  if (dtype == 0) SFP(f16); else if (dtype == 1) SFP(bf16); else SFP(float);
+#undef SFP
+  IUNET_CHECK_HIP(hipGetLastError());
+  return IUNET_OK;
+}
+
+int iunet_sf_stats_parts(int N, int D, int H, int W) {
+  if (N <= 0 || D <= 0 || H <= 0 || W <= 0) return -1;
+  return (int)(((long long)N * D * H * W + SF_COLS - 1) / SF_COLS);
+}
+
+int iunet_sf_gemm(int dtype, int nd, int nsrc, const void* const* x, const long long* x_ss, const int* cin, const int* dims, const void* const* sc,
+                  const void* const* sh, const void* wpk, const void* bias, void* y, long long y_ss, void* stats, int epi, int N, int D, int H,
+                  int W, int Cout, void* stream) {
+  IUNET_REQUIRE(dtype >= 0 && dtype <= 2, "sf_gemm: dtype must be 0 (f16), 1 (bf16) or 2 (planar f32), got %d", dtype);
+  const int rc = sf_check_t(nd, N, D, H, W);
+  if (rc != IUNET_OK) return rc;
+  IUNET_REQUIRE(Cout > 0 && Cout % 16 == 0 && Cout <= SF_MAXC, "sf_gemm: Cout %d (a multiple of 16 up to %d)", Cout, SF_MAXC);
+  IUNET_REQUIRE(wpk && bias && y, "sf_gemm: null pointer");
+  IUNET_REQUIRE(epi == 0 || epi == 1, "sf_gemm: epi must be 0 (raw + statistics) or 1 (relu(acc + bias)), got %d", epi);
+  IUNET_REQUIRE(epi == 0 || !stats, "sf_gemm: statistics are taken of the raw output (epi 0) only");
+  SfGemm p;
+  bool act = false;
+  const int rs = sf_build_srcs(p.src, nd, nsrc, x, x_ss, cin, dims, sc, sh, act);
+  if (rs != IUNET_OK) return rs;
+  p.wpk = wpk; p.K = p.src.s[nsrc - 1].koff + p.src.s[nsrc - 1].C; p.bias = (const float*)bias;
+  p.y = y; p.y_ss = y_ss; p.stats = (float*)stats;
+  p.D = D; p.H = H; p.W = W; p.Cout = Cout; p.epi = epi;
+  p.cols = (long long)N * D * H * W;
+  const dim3 grid((unsigned)iunet_sf_stats_parts(N, D, H, W));
+  const size_t es = dtype == 2 ? 4 : 2, ld = dtype == 2 ? SF_LD32 : SF_LD16;
+  const size_t lds = (size_t)(SF_COLS + Cout) * ld * es;
+#define SFG(TT, NDV, AV) do { \
+    if (lds > 65536) IUNET_SET_MAX_LDS((sf_gemm_kernel<TT, NDV, AV>), (int)lds); \
+    hipLaunchKernelGGL((sf_gemm_kernel<TT, NDV, AV>), grid, dim3(256), lds, (hipStream_t)stream, p); } while (0)
+#define SFG_A(TT, NDV) do { if (act) SFG(TT, NDV, true); else SFG(TT, NDV, false); } while (0)
+#define SFG_D(TT) do { if (nd == 3) SFG_A(TT, 3); else SFG_A(TT, 2); } while (0)
+  if (dtype == 0) SFG_D(f16); else if (dtype == 1) SFG_D(bf16); else SFG_D(float);
+#undef SFG_D
+#undef SFG_A
+#undef SFG
+  IUNET_CHECK_HIP(hipGetLastError());
+  return IUNET_OK;
+}
+
+long long iunet_sf_wgrad_slab_floats(int N, int D, int H, int W, int K, int Cout) {
+  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || K <= 0 || Cout <= 0) return -1;
+  const long long per = (long long)Cout * K;
+  return sf_wgrad_splits((long long)N * D * H * W, per) * per;
+}
+
+int iunet_sf_wgrad(int dtype, int nd, int nsrc, const void* const* x, const long long* x_ss, const int* cin, const int* dims, const void* const* sc,
+                   const void* const* sh, const void* dz, long long dz_ss, void* slab, void* G, int N, int D, int H, int W, int Cout, void* stream) {
+  IUNET_REQUIRE(dtype == 0 || dtype == 1, "sf_wgrad: dtype must be 0 (f16) or 1 (bf16), got %d", dtype);
+  const int rc = sf_check_t(nd, N, D, H, W);
+  if (rc != IUNET_OK) return rc;
+  IUNET_REQUIRE(Cout > 0 && Cout % 8 == 0, "sf_wgrad: Cout %d (a positive multiple of 8)", Cout);
+  IUNET_REQUIRE(dz && slab && G, "sf_wgrad: null pointer");
+  SfWg p;
+  bool act = false;
+  const int rs = sf_build_srcs(p.src, nd, nsrc, x, x_ss, cin, dims, sc, sh, act);
+  if (rs != IUNET_OK) return rs;
+  p.dz = dz; p.dz_ss = dz_ss; p.slab = (float*)slab;
+  p.D = D; p.H = H; p.W = W; p.Cout = Cout; p.K = p.src.s[nsrc - 1].koff + p.src.s[nsrc - 1].C;
+  p.cols = (long long)N * D * H * W;
+  const long long per = (long long)Cout * p.K;
+  const int splits = sf_wgrad_splits(p.cols, per);
+  const long long nchunks = (p.cols + 31) / 32;
+  p.chunks_per_split = (nchunks + splits - 1) / splits;
+  const dim3 grid(splits, (Cout + 63) / 64, (p.K + 63) / 64);
+#define SFW(TT, NDV, AV) hipLaunchKernelGGL((sf_wgrad_kernel<TT, NDV, AV>), grid, dim3(256), 0, (hipStream_t)stream, p)
+#define SFW_A(TT, NDV) do { if (act) SFW(TT, NDV, true); else SFW(TT, NDV, false); } while (0)
+  if (dtype == 0) { if (nd == 3) SFW_A(f16, 3); else SFW_A(f16, 2); }
+  else { if (nd == 3) SFW_A(bf16, 3); else SFW_A(bf16, 2); }
+#undef SFW_A
+#undef SFW
+  IUNET_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(sf_wgrad_reduce_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)slab, splits,
+                     per, (float*)G);
+  IUNET_CHECK_HIP(hipGetLastError());
+  return IUNET_OK;
+}
+
+int iunet_sf_adjoint(int dtype, int nd, const void* u, long long u_ss, int Dt, int Ht, int Wt, void* dx, long long dx_ss, int Ds, int Hs, int Ws,
+                     int C, int N, void* stream) {
+  IUNET_REQUIRE(dtype == 0 || dtype == 1, "sf_adjoint: dtype must be 0 (f16) or 1 (bf16), got %d", dtype);
+  int rc = sf_check_t(nd, N, Dt, Ht, Wt);
+  if (rc != IUNET_OK) return rc;
+  rc = sf_check_t(nd, N, Ds, Hs, Ws);
+  if (rc != IUNET_OK) return rc;
+  IUNET_REQUIRE(C > 0 && C % 8 == 0, "sf_adjoint: C %d (a positive multiple of 8)", C);
+  IUNET_REQUIRE(u && dx, "sf_adjoint: null pointer");
+  const long long total = (long long)N * (C / 8) * Ds * Hs * Ws;
+  const dim3 grid((unsigned)((total + 255) / 256));
+#define SFA(TT, NDV) hipLaunchKernelGGL((sf_adjoint_kernel<TT, NDV>), grid, dim3(256), 0, (hipStream_t)stream, (const TT*)u, u_ss, Dt, Ht, Wt, \
+                                        (TT*)dx, dx_ss, Ds, Hs, Ws, C, N)
+  if (dtype == 0) { if (nd == 3) SFA(f16, 3); else SFA(f16, 2); }
+  else { if (nd == 3) SFA(bf16, 3); else SFA(bf16, 2); }
+#undef SFA
+  IUNET_CHECK_HIP(hipGetLastError());
+  return IUNET_OK;
+}
+
+int iunet_sf_param_grads(int L, int C, const int* ch, const void* wf, const void* const* w, const void* const* b, const void* G, const void* rs,
+                         int N, void* const* dw, void* const* db, void* dwf, void* stream) {
+  SfOps o;
+  const int rc = sf_build_ops(o, L, C, ch, wf, w, b);
+  if (rc != IUNET_OK) return rc;
+  IUNET_REQUIRE(G && rs && dw && db && dwf && N > 0, "sf_param_grads: null pointer or N %d", N);
+  SfGrads g;
+  for (int l = 0; l < L; ++l) {
+    IUNET_REQUIRE(dw[l] && db[l], "sf_param_grads: level %d: null gradient", l);
+    g.dw[l] = (float*)dw[l]; g.db[l] = (float*)db[l];
+  }
+  g.dwf = (float*)dwf;
+  const long long total = (long long)C * o.K + (long long)C * L * C + (long long)L * C;
+  hipLaunchKernelGGL(sf_param_grad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, o, g, (const float*)G,
+                     (const float*)rs, N);
+  IUNET_CHECK_HIP(hipGetLastError());
+  return IUNET_OK;
+}
+
+}  // extern "C"

@@ -16,6 +16,8 @@ _lib = None
 
 c_void_p, c_int, c_ll, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
 _IP = ctypes.POINTER(c_int)
+_LP = ctypes.POINTER(c_ll)
+_VP = ctypes.POINTER(c_void_p)
 
 # name -> argtypes (all functions return int status except where noted)
 _SIGS = {
@@ -269,13 +271,20 @@ _SIGS = {
     'iunet_dl_up_loss_fwd': [c_int, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     'iunet_dl_up_loss_bwd': [c_int, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_void_p],
     'iunet_dl_head_bwd': [c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_int, c_void_p, c_ll] + [c_void_p] * 3 + [c_int, c_ll, c_void_p],
+    # ---- Segformer decoder (csrc/segformer.hip)
+    'iunet_sf_pack': [c_int, c_int, c_int, _IP, c_void_p, _VP, _VP] + [c_void_p] * 4 + [c_float] + [c_void_p] * 4,
+    'iunet_sf_gemm': [c_int, c_int, c_int, _VP, _LP, _IP, _IP, _VP, _VP, c_void_p, c_void_p, c_void_p, c_ll, c_void_p] + [c_int] * 6 + [c_void_p],
+    'iunet_sf_wgrad': [c_int, c_int, c_int, _VP, _LP, _IP, _IP, _VP, _VP, c_void_p, c_ll, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p],
+    'iunet_sf_adjoint': [c_int, c_int, c_void_p, c_ll, c_int, c_int, c_int, c_void_p, c_ll] + [c_int] * 5 + [c_void_p],
+    'iunet_sf_param_grads': [c_int, c_int, _IP, c_void_p, _VP, _VP, c_void_p, c_void_p, c_int, _VP, _VP, c_void_p, c_void_p],
 }
 # functions that return a size / count instead of a status
 _INT_RETURN = ['iunet_pack_desc_bytes', 'iunet_augment_desc_bytes', 'iunet_x2_prep_desc_bytes']
-_INT_RETURN_ARGS = {'iunet_dl_num_taps': [c_int] * 5, 'iunet_dl_up_loss_num_parts': [c_int, c_ll], 'iunet_dl_head_bwd_parts': [c_int, c_ll], 'iunet_zoom_nearest_len': [c_int, ctypes.c_double], 'iunet_x2_convT_kc': [c_int], 'iunet_x2m_head_fusable': [c_int, c_int], 'iunet_x2m_pool_fusable': [c_int, c_int], 'iunet_x2m_first_stage_fusable': [c_int] * 6, 'iunet_x2_pack_mode': [c_int], 'iunet_f8_pack_order': [c_int, c_int]}
+_INT_RETURN_ARGS = {'iunet_sf_stats_parts': [c_int] * 4, 'iunet_dl_num_taps': [c_int] * 5, 'iunet_dl_up_loss_num_parts': [c_int, c_ll], 'iunet_dl_head_bwd_parts': [c_int, c_ll], 'iunet_zoom_nearest_len': [c_int, ctypes.c_double], 'iunet_x2_convT_kc': [c_int], 'iunet_x2m_head_fusable': [c_int, c_int], 'iunet_x2m_pool_fusable': [c_int, c_int], 'iunet_x2m_first_stage_fusable': [c_int] * 6, 'iunet_x2_pack_mode': [c_int], 'iunet_f8_pack_order': [c_int, c_int]}
 _LL_RETURN = {'iunet_gn_precise_slab_bytes': [c_int, c_int, c_ll], 'iunet_net_eval_scratch_bytes': [c_void_p, c_int, c_int, c_int, c_int], 'iunet_x2m_w8_bytes': [c_int] * 2, 'iunet_x2m_w8_bytes_nd': [c_int] * 3, 'iunet_train_num_params': [c_void_p], 'iunet_train_packed_bytes': [c_void_p], 'iunet_train_workspace_bytes': [c_void_p, c_int, c_int, c_int, c_int], 'iunet_conv3_wgrad_slab_floats': [c_int] * 7, 'iunet_f32_pack_conv_elems': [c_int] * 3, 'iunet_f8_pack_conv3_bytes': [c_int] * 3, 'iunet_conv3_f8_workspace_elems': [c_int] * 7, 'iunet_pack_conv3_elems': [c_int] * 4,
               'iunet_pack_first_conv_elems': [c_int] * 3, 'iunet_slice_scatter_workspace_bytes': [c_int],
               'iunet_lk_pack_elems': [c_int] * 4, 'iunet_lk_wgrad_slab_floats': [c_int] * 8, 'iunet_dl_wgrad_slab_floats': [c_int] * 8,
+              'iunet_sf_wgrad_slab_floats': [c_int] * 6,
               'iunet_net_num_params': [c_void_p], 'iunet_net_packed_bytes': [c_void_p], 'iunet_net_workspace_bytes': [c_void_p] + [c_int] * 4}
 
 
@@ -469,3 +478,8 @@ def int_array(vals):
 
 DTYPE_CODE = {torch.float16: 0, torch.bfloat16: 1}
 IN_DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.uint8: 2, torch.bfloat16: 3}
+
+
+def ptr_array(vals):
+    """A C array of pointers (tensors, raw addresses or None) for the `const void* const*` arguments."""
+    return (c_void_p * len(vals))(*[None if v is None else (v.data_ptr() if hasattr(v, 'data_ptr') else int(v)) for v in vals])

@@ -386,7 +386,10 @@ class TrainEngineF32:
 def make_train_engine(model, **kw):
     """The training engine of a module: 16-bit activations (TrainEngine) or, for act_dtype='fp32', the fp32 parity form; U-Net++
     modules train on train_engine_nested.NestedTrainEngine, LinkNet modules on train_engine_linknet.LinkNetTrainEngine, DeepLabV3 modules on
-    train_engine_deeplab.DeepLabV3TrainEngine."""
+    train_engine_deeplab.DeepLabV3TrainEngine, Segformer modules on train_engine_segformer.SegformerTrainEngine."""
+    if getattr(model, 'architecture', 'U-Net') == 'Segformer':
+        from .train_engine_segformer import SegformerTrainEngine
+        return SegformerTrainEngine(model, **kw)
     if getattr(model, 'architecture', 'U-Net') == 'DeepLabV3':
         from .train_engine_deeplab import DeepLabV3TrainEngine
         return DeepLabV3TrainEngine(model, **kw)

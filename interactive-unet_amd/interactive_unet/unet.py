@@ -4,7 +4,8 @@
 the native canonical U-Net (engine.py) instead of segmentation_models_pytorch.
 
 architecture='U-Net', 'U-Net++' (the canonical nested form: engine_nested.py, train_engine_nested.py), 'LinkNet' (engine_linknet.py,
-train_engine_linknet.py) and 'DeepLabV3' (engine_deeplab.py, train_engine_deeplab.py) exist natively;
+train_engine_linknet.py), 'DeepLabV3' (engine_deeplab.py, train_engine_deeplab.py) and 'Segformer' (engine_segformer.py,
+train_engine_segformer.py) exist natively;
 `encoder_name` is accepted and ignored (the canonical nets have their own plain conv encoder), `pretrained` is a no-op with a warning (no imagenet
 weights for a from-scratch encoder; no network access).  Extra keyword arguments (dim, levels,
 base, act_dtype, infer_dtype) select the 3-D / wider variants of BASELINE.json's configs.
@@ -39,7 +40,8 @@ _ACT_NAME = {torch.float16: 'fp16', torch.bfloat16: 'bf16', torch.float32: 'fp32
 NESTED = 'U-Net++'
 LINKNET = 'LinkNet'
 DEEPLAB = 'DeepLabV3'
-ARCHITECTURES = ('U-Net', NESTED, LINKNET, DEEPLAB)
+SEGFORMER = 'Segformer'
+ARCHITECTURES = ('U-Net', NESTED, LINKNET, DEEPLAB, SEGFORMER)
 
 
 def nested_nodes(levels):
@@ -55,7 +57,9 @@ def param_shapes(dim=2, levels=4, base=32, cin=1, ncls=2, architecture='U-Net', 
     the block dec{l} (conv1 1x1 ch[l+1] -> m, ConvTranspose k4 s2 p1 m -> m, conv2 1x1 m -> ch[l], m = ch[l+1] / 4, a BatchNorm after
     each, no conv bias), then the head.  architecture='DeepLabV3': the encoder, then the ASPP on ch[L-1] (aspp.b0 1x1, aspp.b1..b3 dilated
     3^d, aspp.pool 1x1 after the global mean, aspp.project 1x1 over the 5 C concat; C = decoder_channels), dec.conv 3^d C -> C, each conv
-    without bias and with a BatchNorm `<prefix>.bn`, then the head C -> ncls."""
+    without bias and with a BatchNorm `<prefix>.bn`, then the head C -> ncls.  architecture='Segformer': the encoder, then mlp{l} (nn.Linear
+    ch[l] -> C, weight [C, ch[l]], bias [C]) for l = 0 .. L-1, fuse (conv 1x1 L C -> C without bias over the deepest-first concat, BatchNorm
+    `fuse.bn`), then the head C -> ncls; C = decoder_channels."""
     if architecture not in ARCHITECTURES:
         raise NotImplementedError(f'architecture {architecture!r}: the native networks are {ARCHITECTURES}')
     ch = [base * 2 ** l for l in range(levels)]
@@ -69,6 +73,17 @@ def param_shapes(dim=2, levels=4, base=32, cin=1, ncls=2, architecture='U-Net', 
                 shapes[f'{prefix}.bn{j}.{k}'] = (b,)
     for l in range(levels):
         stage(f'enc{l}', cin if l == 0 else ch[l - 1], ch[l])
+    if architecture == SEGFORMER:
+        C = decoder_channels
+        for l in range(levels):
+            shapes[f'mlp{l}.weight'] = (C, ch[l])
+            shapes[f'mlp{l}.bias'] = (C,)
+        shapes['fuse.conv.weight'] = (C, levels * C) + k1
+        for k in ('weight', 'bias', 'running_mean', 'running_var'):
+            shapes[f'fuse.bn.{k}'] = (C,)
+        shapes['head.weight'] = (ncls, C) + k1
+        shapes['head.bias'] = (ncls,)
+        return shapes
     if architecture == DEEPLAB:
         C, Cb = decoder_channels, ch[-1]
         for prefix, shp in (('aspp.b0', (C, Cb) + k1), ('aspp.b1', (C, Cb) + k3), ('aspp.b2', (C, Cb) + k3), ('aspp.b3', (C, Cb) + k3),
@@ -169,6 +184,29 @@ def _check_deeplab(levels, base, cin, ncls, act_dtype, weight_dtype, norm, infer
         raise NotImplementedError(f'DeepLabV3 with decoder_atrous_rates={rates!r}: {what}')
 
 
+def _check_segformer(levels, base, cin, ncls, act_dtype, weight_dtype, norm, infer_dtype, infer_policy, channels):
+    """The combinations the native Segformer supports: BatchNorm, 16-bit training (fp16 / bf16), prediction in fp32 (default) or fp16 /
+    bf16, 3 .. 6 levels, base a multiple of 32, 1 .. 4 input channels, 2 .. 10 classes, decoder_segmentation_channels a multiple of 32 in
+    32 .. 512."""
+    what = ("Segformer supports norm='batch', act_dtype None / 'fp16' / 'bf16' (training), infer_dtype None / 'fp32' / 'fp16' / "
+            "'bf16' (prediction), 3 .. 6 levels, base a multiple of 32, 1 .. 4 input channels, 2 .. 10 classes and "
+            "decoder_segmentation_channels a multiple of 32 in 32 .. 512")
+    if norm != 'batch':
+        raise NotImplementedError(f'Segformer with norm={norm!r} (GroupNorm): {what}')
+    if weight_dtype is not None:
+        raise NotImplementedError(f'Segformer with weight_dtype={weight_dtype!r} (fp8 weights): {what}')
+    if act_dtype is not None and _ACT.get(act_dtype) not in (torch.float16, torch.bfloat16):
+        raise NotImplementedError(f'Segformer with act_dtype={act_dtype!r} (the fp32 training form / split precision): {what}')
+    if infer_dtype is not None and _ACT.get(infer_dtype) not in (torch.float32, torch.float16, torch.bfloat16):
+        raise NotImplementedError(f'Segformer with infer_dtype={infer_dtype!r} (split precision): {what}')
+    if infer_policy is not None:
+        raise NotImplementedError(f'Segformer with infer_policy={infer_policy!r} (split-precision forms): {what}')
+    if not (3 <= levels <= 6) or base % 32 or not (1 <= cin <= 4) or not (2 <= ncls <= 10):
+        raise NotImplementedError(f'Segformer with {levels} levels, base {base}, {cin} input channels, {ncls} classes: {what}')
+    if not isinstance(channels, int) or isinstance(channels, bool) or channels % 32 or not (32 <= channels <= 512):
+        raise NotImplementedError(f'Segformer with decoder_segmentation_channels={channels!r}: {what}')
+
+
 def _is_buffer(name):
     return name.endswith('running_mean') or name.endswith('running_var')
 
@@ -204,10 +242,11 @@ class UNet(nn.Module):
     def __init__(self, lr=0.0001, num_channels=1, num_classes=2, loss_function=metrics.mcc_ce_loss,
                  architecture='U-Net', encoder_name='mit_b0', pretrained=True,
                  dim=2, levels=4, base=32, act_dtype=None, weight_dtype=None, norm='batch', groups=8, infer_dtype=None,
-                 act_quant=None, infer_policy=None, decoder_channels=256, decoder_atrous_rates=(12, 24, 36), decoder_aspp_dropout=0.5):
+                 act_quant=None, infer_policy=None, decoder_channels=256, decoder_atrous_rates=(12, 24, 36), decoder_aspp_dropout=0.5,
+                 decoder_segmentation_channels=256):
         super().__init__()
         if architecture not in ARCHITECTURES:
-            raise NotImplementedError(f"architecture {architecture!r}: only 'U-Net', 'U-Net++', 'LinkNet' and 'DeepLabV3' have a native MI355X "
+            raise NotImplementedError(f"architecture {architecture!r}: only 'U-Net', 'U-Net++', 'LinkNet', 'DeepLabV3' and 'Segformer' have a native MI355X "
                                       f"implementation (the reference builds the others through smp, unet.py:33-54)")
         if architecture == NESTED:
             _check_nested(levels, act_dtype, weight_dtype, norm, infer_dtype, infer_policy)
@@ -218,6 +257,9 @@ class UNet(nn.Module):
                            decoder_channels, decoder_atrous_rates)
             if not (0.0 <= float(decoder_aspp_dropout) < 1.0):
                 raise ValueError(f'decoder_aspp_dropout must be in [0, 1), got {decoder_aspp_dropout!r}')
+        if architecture == SEGFORMER:
+            _check_segformer(levels, base, num_channels, num_classes, act_dtype, weight_dtype, norm, infer_dtype, infer_policy,
+                             decoder_segmentation_channels)
         if pretrained:
             warnings.warn('pretrained=True ignored: the native U-Net encoder is trained from scratch')
         self.hparams = dict(lr=lr, num_channels=num_channels, num_classes=num_classes,
@@ -234,6 +276,10 @@ class UNet(nn.Module):
             self.decoder_aspp_dropout = float(decoder_aspp_dropout)
             self.hparams.update(decoder_channels=decoder_channels, decoder_atrous_rates=list(self.decoder_atrous_rates),
                                 decoder_aspp_dropout=self.decoder_aspp_dropout)
+        self.decoder_segmentation_channels = None
+        if architecture == SEGFORMER:       # (only Segformer modules carry it)
+            self.decoder_segmentation_channels = decoder_segmentation_channels
+            self.hparams.update(decoder_segmentation_channels=decoder_segmentation_channels)
         self.lr = lr
         self.loss_function = loss_function
         self.dim, self.levels, self.base = dim, levels, base
@@ -244,7 +290,7 @@ class UNet(nn.Module):
         self.act_dtype = torch.float16 if act_dtype is None else _ACT[act_dtype]
         if infer_dtype is not None:
             self.infer_dtype = _ACT[infer_dtype]
-        elif architecture in (NESTED, LINKNET, DEEPLAB):
+        elif architecture in (NESTED, LINKNET, DEEPLAB, SEGFORMER):
             self.infer_dtype = torch.float32   # these nets predict in the fp32 form (within 1e-3 of the CPU fp32 logits)
         elif act_dtype is None and weight_dtype is None:
             self.infer_dtype = X2              # (GroupNorm networks too: engine_auto runs them in the full fp16x2 form)
@@ -264,7 +310,8 @@ class UNet(nn.Module):
         self.norm, self.groups = norm, groups
         self._names = []
         for name, shp in param_shapes(dim, levels, base, num_channels, num_classes, architecture,
-                                      decoder_channels if architecture == DEEPLAB else 256).items():
+                                      decoder_channels if architecture == DEEPLAB else
+                                      decoder_segmentation_channels if architecture == SEGFORMER else 256).items():
             t = torch.empty(shp, dtype=torch.float32)
             key = name.replace('.', '__')
             if _is_buffer(name):
@@ -287,6 +334,8 @@ class UNet(nn.Module):
                 if name.endswith('conv1.weight') or name.endswith('conv2.weight') or name == 'head.weight' or name.endswith('.conv.weight'):
                     fan_in = shp[1] * math.prod(shp[2:])
                     t.copy_(torch.randn(shp, generator=g) * math.sqrt(2.0 / fan_in))      # He-normal
+                elif name.startswith('mlp') and name.endswith('.weight'):
+                    t.copy_(torch.randn(shp, generator=g) * math.sqrt(2.0 / shp[1]))       # He-normal, fan-in ch[l]
                 elif name.endswith('up.weight'):
                     t.copy_(torch.randn(shp, generator=g) * math.sqrt(1.0 / shp[0]))
                 elif name.endswith('running_var') or name.endswith('bn1.weight') or name.endswith('bn2.weight') or name.endswith('bn3.weight') \
@@ -329,6 +378,16 @@ class UNet(nn.Module):
             raise RuntimeError('the native U-Net runs on the GPU only: move the module with .to("cuda") '
                                '(there is no CPU fallback)')
         eng = self._engines.get(dev)
+        if eng is None and self.architecture == SEGFORMER:
+            from .engine_segformer import SegformerEngine, SegformerEngineF32
+            args = (self.dim, self.levels, self.base, self.num_channels, self.num_classes)
+            kw = dict(decoder_channels=self.decoder_segmentation_channels, device=dev)
+            if self.infer_dtype == torch.float32:
+                eng = SegformerEngineF32(*args, **kw)
+            else:
+                eng = SegformerEngine(*args, act_dtype=self.infer_dtype, **kw)
+            self._engines = {dev: eng}
+            self._packed_sig = None
         if eng is None and self.architecture == DEEPLAB:
             from .engine_deeplab import DeepLabV3Engine, DeepLabV3EngineF32
             args = (self.dim, self.levels, self.base, self.num_channels, self.num_classes)
