@@ -25,6 +25,13 @@ def _vox(dims):
     return dims[0] * dims[1] * dims[2]
 
 
+def check_spatial(dim, levels, D, H, W):
+    """Every level halves the grid: H, W (and D in 3-D) must be divisible by 2^(levels-1), and D == 1 in 2-D."""
+    f = 2 ** (levels - 1)
+    if H % f or W % f or (dim == 3 and D % f) or (dim == 2 and D != 1):
+        raise ValueError(f'spatial size {(D, H, W)} must be divisible by {f} (and D == 1 in 2-D)')
+
+
 class F8Conv:
     """A stage conv's operator for the fp8 matrix cores: e4m3 bytes (K16 order) + fp32 per-output-channel scales."""
 
@@ -208,9 +215,7 @@ class Engine:
         return out
 
     def check_shape(self, D, H, W):
-        f = 2 ** (self.levels - 1)
-        if H % f or W % f or (self.dim == 3 and D % f) or (self.dim == 2 and D != 1):
-            raise ValueError(f'spatial size {(D, H, W)} must be divisible by {f} (and D == 1 in 2-D)')
+        check_spatial(self.dim, self.levels, D, H, W)
 
     def workspace(self, N, D, H, W):
         key = (N, D, H, W)
@@ -456,3 +461,136 @@ class Engine:
         t = flat.reshape(N, C // 8, *sp, 8)
         perm = [0, 1, 2 + len(sp)] + list(range(2, 2 + len(sp)))
         return t.permute(*perm).reshape(N, C, *sp)
+
+
+class EncoderOnly:
+    """What the forward engines of the encoder-only decoders (LinkNet, DeepLabV3, Segformer) share in both numeric forms: the U-Net's
+    encoder with X^l written to x{l}, a workspace laid out by the architecture's `_bufs(dims, N)` -> (activation element counts, fp32
+    element counts), and no C-sequenced handle."""
+
+    def enc_names(self):
+        return [f'enc{l}' for l in range(self.levels)]
+
+    def enc_io(self, prefix):
+        l = int(prefix[3:])
+        return (self.cin if l == 0 else self.ch[l - 1]), self.ch[l]
+
+    def _graph(self):
+        return None          # (every forward is sequenced from Python)
+
+    def bytes_per_slice(self, input_size):
+        """Workspace bytes of one 2-D slice of input_size^2 (predict.find_max_batch_size)."""
+        S = input_size
+        act, f32 = self._bufs([(1, S >> l, S >> l) for l in range(self.levels)], 1)
+        return sum(act.values()) * self._es + sum(f32.values()) * 4
+
+    def workspace(self, N, D, H, W):
+        key = (N, D, H, W)
+        ws = self._ws_cache.get(key)
+        if ws is None:
+            check_spatial(self.dim, self.levels, D, H, W)
+            dims = self.level_dims(D, H, W)
+            act, f32 = self._bufs(dims, N)
+            ws = {k: torch.empty(n, dtype=self.act_dtype, device=self.device) for k, n in act.items()}
+            ws.update({k: torch.empty(n, dtype=torch.float32, device=self.device) for k, n in f32.items()})
+            ws['dims'] = dims
+            self._ws_cache = {key: ws}
+        return ws
+
+    def _P(self, t, off_elems=0):
+        return ctypes.c_void_p(t.data_ptr() + off_elems * self._es)
+
+    def _encoder(self, x, x_strides, N, D, H, W):
+        """The encoder into x{l} of the workspace, which it returns (the decoder's launches follow)."""
+        if self.packed is None:
+            raise RuntimeError(f'{type(self).__name__}.load_eval() has not been called')
+        ws = self.workspace(N, D, H, W)
+        self._encoder_forward(ws, x, x_strides, N)
+        return ws
+
+
+class CoarseLogits:
+    """DeepLabV3 and Segformer: the decoder `_decode(ws, N)` leaves C = self.C channels in ws['feat'] on level `coarse_level`'s grid, the
+    1x1 head gives fp32 coarse logits ws['lc'] there, and iunet_dl_up_head upsamples them x 2^coarse_level (align_corners=True) into
+    iunet_head_fwd's output contract (logits / probs / class map, strides, divisor, accumulate)."""
+
+    def coarse_logits(self, x, x_strides, N, D, H, W):
+        """The forward up to the head: fp32 coarse logits [N][ncls][coarse grid] (the workspace's, overwritten by the next call)."""
+        ws = self._encoder(x, x_strides, N, D, H, W)
+        self._decode(ws, N)
+        dc = ws['dims'][self.coarse_level]
+        vc = _vox(dc)
+        hw, hb = self.packed['head']
+        args = (self._P(ws['feat']), self.C * vc, self.C, nv.ptr(hw), nv.ptr(hb), self.ncls, nv.ptr(ws['lc']), None, None,
+                nv.ll_array((self.ncls * vc, vc, dc[1] * dc[2], dc[2], 1)), 1.0, 0, N, dc[0], dc[1], dc[2], nv.stream())
+        if self.act_dtype == torch.float32:
+            nv.call('iunet_f32_head_fwd', *args)
+        else:
+            nv.call('iunet_head_fwd', self.dt, *args)
+        return ws['lc']
+
+    def infer(self, x, x_strides, N, D, H, W, logits=None, probs=None, cls=None, out_strides=None,
+              divisor=1.0, accumulate=False, features_only=False):
+        """engine.Engine.infer's contract (features_only: the coarse fp32 logits)."""
+        lc = self.coarse_logits(x, x_strides, N, D, H, W)
+        if features_only:
+            return lc
+        dc = self.workspace(N, D, H, W)['dims'][self.coarse_level]
+        if out_strides is None:
+            v = D * H * W
+            out_strides = (self.ncls * v, v, H * W, W, 1)
+        nv.call('iunet_dl_up_head', self.dim, nv.ptr(lc), self.ncls, dc[0], dc[1], dc[2], 2 ** self.coarse_level, nv.ptr(logits), nv.ptr(probs),
+                nv.ptr(cls), nv.ll_array(out_strides), float(divisor), int(bool(accumulate)), N, nv.stream())
+
+
+class EncoderEngine(EncoderOnly, Engine):
+    """The 16-bit (fp16 / bf16) forward of an encoder-only decoder: the encoder's stage convs with folded BatchNorm; the architecture adds
+    `_pack_decoder(src, dtype_code)` -> {name: operators} and its decoder launches."""
+
+    def __init__(self, dim=2, levels=4, base=32, cin=1, ncls=2, act_dtype=torch.float16, device='cuda'):
+        if act_dtype not in (torch.float16, torch.bfloat16):
+            name = type(self).__name__
+            raise NotImplementedError(f"{name} runs fp16 / bf16 activations ({name}F32: the fp32 form)")
+        Engine.__init__(self, dim, levels, base, cin, ncls, act_dtype, device)
+        self.use_graph = False
+        self._es, self._pack_dtype = 2, act_dtype
+
+    def load_eval(self, params):
+        """Fold eval-mode BatchNorm into every conv and pack all operators."""
+        if not hasattr(self, '_stage'):
+            self._stage = {}
+        src = lambda n: self._source(params, n)
+        P, descs, keep = {}, [], []
+        for prefix in self.enc_names():
+            ci, co = self.enc_io(prefix)
+            for j, (a, b) in enumerate(((ci, co), (co, co)), 1):
+                w = src(f'{prefix}.conv{j}.weight')
+                bn = [src(f'{prefix}.bn{j}.{k}') for k in ('weight', 'bias', 'running_mean', 'running_var')]
+                keep += [w] + bn
+                bias = torch.empty(b, dtype=torch.float32, device=self.device)
+                if prefix == 'enc0' and j == 1:
+                    dst = torch.empty(nv.lib().iunet_pack_first_conv_elems(b, a, self.taps), dtype=self.act_dtype, device=self.device)
+                    descs.append(nv.make_desc(w, dst, b, a, self.taps, 2, self.act_dtype, bn=bn, bias_out=bias, eps=BN_EPS))
+                else:
+                    dst = nv.PackedConv(b, a, self.taps, self.act_dtype, self.device)
+                    descs += dst.descs(w, bn, bias, BN_EPS, None)
+                P[f'{prefix}.conv{j}'] = (dst, bias)
+        nv.PackTable(descs, self.device, sources=keep).run()
+        P.update(self._pack_decoder(src, self.dt))
+        self.packed = P
+
+    def _encoder_forward(self, ws, x, x_strides, N):
+        dims, L, ch, s, P = ws['dims'], self.levels, self.ch, nv.stream(), self._P
+        for l in range(L):
+            v = _vox(dims[l])
+            if l == 0:
+                w, b = self.packed['enc0.conv1']
+                nv.call('iunet_first_conv_fwd', self.dt, self.dim, nv.ptr(x), nv.IN_DTYPE_CODE[x.dtype], nv.ll_array(x_strides),
+                        P(ws['a0']), ch[0] * v, nv.ptr(w), nv.ptr(b), None, N, dims[0][0], dims[0][1], dims[0][2], self.cin, ch[0], 1, s)
+            else:
+                self._conv3(P(ws[f'pin{l}']), ch[l - 1] * v, P(ws[f'a{l}']), ch[l] * v, f'enc{l}.conv1', N, dims[l], ch[l - 1], ch[l], s)
+            self._conv3(P(ws[f'a{l}']), ch[l] * v, P(ws[f'x{l}']), ch[l] * v, f'enc{l}.conv2', N, dims[l], ch[l], ch[l], s)
+            if l < L - 1:
+                do = dims[l + 1]
+                nv.call('iunet_maxpool_fwd', self.dt, self.dim, P(ws[f'x{l}']), ch[l] * v, P(ws[f'pin{l + 1}']), ch[l] * _vox(do), ch[l], N,
+                        do[0], do[1], do[2], s)

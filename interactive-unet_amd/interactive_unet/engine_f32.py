@@ -13,7 +13,7 @@ import ctypes
 import torch
 
 from . import _native as nv
-from .engine import BN_EPS, _vox
+from .engine import BN_EPS, EncoderOnly, _vox, check_spatial
 
 
 class EngineF32:
@@ -83,9 +83,7 @@ class EngineF32:
         key = (N, D, H, W)
         ws = self._ws_cache.get(key)
         if ws is None:
-            f = 2 ** (self.levels - 1)
-            if H % f or W % f or (self.dim == 3 and D % f) or (self.dim == 2 and D != 1):
-                raise ValueError(f'spatial size {(D, H, W)} must be divisible by {f} (and D == 1 in 2-D)')
+            check_spatial(self.dim, self.levels, D, H, W)
             dims = self.level_dims(D, H, W)
             mk = lambda c, v: torch.empty(N * c * v, dtype=torch.float32, device=self.device)
             ws = {'dims': dims}
@@ -158,3 +156,52 @@ class EngineF32:
         nv.call('iunet_f32_head_fwd', Pt(b_of(0)), ch[0] * _vox(dims[0]), ch[0], nv.ptr(hw), nv.ptr(hb), self.ncls,
                 nv.ptr(logits), nv.ptr(probs), nv.ptr(cls), nv.ll_array(out_strides), float(divisor),
                 int(bool(accumulate)), N, D, H, W, s)
+
+
+class EncoderEngineF32(EncoderOnly, EngineF32):
+    """The fp32 forward of an encoder-only decoder (planar fp32 activations, the f32-input matrix instruction): the encoder's stage convs
+    with folded BatchNorm; the architecture adds `_pack_decoder(src, 2)` -> {name: operators} and its decoder launches."""
+    dt = 2                 # (the fp32 code of the decoder kernels' dtype argument)
+
+    def __init__(self, dim=2, levels=4, base=32, cin=1, ncls=2, device='cuda'):
+        EngineF32.__init__(self, dim, levels, base, cin, ncls, device)
+        self._es, self._pack_dtype = 4, torch.float32
+        self.use_graph = False
+
+    def load_eval(self, params):
+        f32 = lambda n: torch.empty(n, dtype=torch.float32, device=self.device)
+        src = lambda name: params[name].detach().to(self.device, torch.float32).contiguous()
+        lib, s, P = nv.lib(), nv.stream(), {}
+        for prefix in self.enc_names():
+            ci, co = self.enc_io(prefix)
+            for j, (a, b) in enumerate(((ci, co), (co, co)), 1):
+                w = src(f'{prefix}.conv{j}.weight')
+                bn = [src(f'{prefix}.bn{j}.{k}') for k in ('weight', 'bias', 'running_mean', 'running_var')]
+                dst, bias = f32(lib.iunet_f32_pack_conv_elems(b, a, self.taps)), f32(b)
+                nv.call('iunet_f32_pack_conv', nv.ptr(w), nv.ptr(dst), nv.ptr(bias), nv.ptr(bn[0]), nv.ptr(bn[1]),
+                        nv.ptr(bn[2]), nv.ptr(bn[3]), BN_EPS, b, a, self.taps, 0, s)
+                P[f'{prefix}.conv{j}'] = (dst, bias)
+        P.update(self._pack_decoder(src, self.dt))
+        torch.cuda.current_stream().synchronize()          # the staging copies above may be freed by the caller
+        self.packed = P
+
+    def _encoder_forward(self, ws, x, x_strides, N):
+        dims, L, ch, s, P = ws['dims'], self.levels, self.ch, nv.stream(), self._P
+
+        def conv(name, xp, in_dt, strides, yp, y_ss, d, ci, co):
+            w, b = self.packed[name]
+            nv.call('iunet_f32_conv_fwd', self.dim, xp, in_dt, nv.ll_array(strides), yp, y_ss, nv.ptr(w), nv.ptr(b),
+                    N, d[0], d[1], d[2], ci, co, 1, 0, s)
+
+        planar = lambda ss, d: (ss, _vox(d), d[1] * d[2], d[2], 1)
+        for l in range(L):
+            d, v = dims[l], _vox(dims[l])
+            if l == 0:
+                conv('enc0.conv1', nv.ptr(x), nv.IN_DTYPE_CODE[x.dtype], x_strides, P(ws['a0']), ch[0] * v, d, self.cin, ch[0])
+            else:
+                conv(f'enc{l}.conv1', P(ws[f'pin{l}']), 0, planar(ch[l - 1] * v, d), P(ws[f'a{l}']), ch[l] * v, d, ch[l - 1], ch[l])
+            conv(f'enc{l}.conv2', P(ws[f'a{l}']), 0, planar(ch[l] * v, d), P(ws[f'x{l}']), ch[l] * v, d, ch[l], ch[l])
+            if l < L - 1:
+                do = dims[l + 1]
+                nv.call('iunet_f32_maxpool_fwd', self.dim, P(ws[f'x{l}']), ch[l] * v, P(ws[f'pin{l + 1}']), ch[l] * _vox(do), ch[l], N,
+                        do[0], do[1], do[2], s)

@@ -17,7 +17,7 @@ import ctypes
 import torch
 
 from . import _native as nv
-from .engine import BN_EPS, Engine, _vox
+from .engine import BN_EPS, Engine, _vox, check_spatial
 from .engine_f32 import EngineF32
 from .unet import nested_nodes
 
@@ -231,9 +231,7 @@ class NestedEngineF32(_Nested, EngineF32):
         key = (N, D, H, W)
         ws = self._ws_cache.get(key)
         if ws is None:
-            f = 2 ** (self.levels - 1)
-            if H % f or W % f or (self.dim == 3 and D % f) or (self.dim == 2 and D != 1):
-                raise ValueError(f'spatial size {(D, H, W)} must be divisible by {f} (and D == 1 in 2-D)')
+            check_spatial(self.dim, self.levels, D, H, W)
             dims = self.level_dims(D, H, W)
             ws = {k: torch.empty(n, dtype=torch.float32, device=self.device) for k, n in _level_bufs(self.levels, self.ch, dims, N, 0).items()}
             ws['dims'] = dims

@@ -25,7 +25,7 @@ import os
 import torch
 
 from . import _native as nv
-from .engine import BN_EPS, _vox
+from .engine import BN_EPS, _vox, check_spatial
 
 
 class EngineX2:
@@ -215,9 +215,7 @@ class EngineX2:
         return [((D >> l) if self.dim == 3 else 1, H >> l, W >> l) for l in range(self.levels)]
 
     def check_shape(self, D, H, W):
-        f = 2 ** (self.levels - 1)
-        if H % f or W % f or (self.dim == 3 and D % f) or (self.dim == 2 and D != 1):
-            raise ValueError(f'spatial size {(D, H, W)} must be divisible by {f} (and D == 1 in 2-D)')
+        check_spatial(self.dim, self.levels, D, H, W)
 
     def workspace(self, N, D, H, W):
         key = (N, D, H, W)

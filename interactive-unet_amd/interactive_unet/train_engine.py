@@ -14,7 +14,7 @@ import os
 import torch
 
 from . import _native as nv
-from .engine import BN_EPS
+from .engine import BN_EPS, check_spatial
 
 LOSS_KINDS = {'ce': 0, 'dice': 1, 'iou': 2, 'mcc': 3, 'dice_ce': 4, 'iou_ce': 5, 'mcc_ce': 6}
 BN_MOMENTUM = 0.1
@@ -162,6 +162,10 @@ class TrainEngine:
         ci = (self.cin if l == 0 else self.ch[l - 1]) if prefix.startswith('enc') else 2 * self.ch[l]
         return ci, self.ch[l], l
 
+    def up_convs(self):
+        """(prefix, level l) of every transposed conv ch[l+1] -> ch[l], in parameter order."""
+        return [(f'dec{l}', l) for l in range(self.levels - 2, -1, -1)]
+
     def _alloc_packed(self):
         self.pk = {}
         for prefix in self.stage_names():
@@ -174,14 +178,18 @@ class TrainEngine:
                 else:
                     self.pk[name] = (nv.PackedConv(b, a, self.taps, self.T, self.dev),
                                      nv.PackedConv(b, a, self.taps, self.T, self.dev, dgrad=True))
-        for l in range(self.levels - 2, -1, -1):
+        for prefix, l in self.up_convs():
             n = self.ch[l + 1] * self.ch[l] * self.npos
-            self.pk[f'dec{l}.up'] = (torch.empty(n, dtype=self.T, device=self.dev),
-                                     torch.empty(n, dtype=self.T, device=self.dev))
+            self.pk[f'{prefix}.up'] = (torch.empty(n, dtype=self.T, device=self.dev),
+                                       torch.empty(n, dtype=self.T, device=self.dev))
+        self._alloc_decoder()
+
+    def _alloc_decoder(self):
+        """The packed operators of a decoder that is not made of stages and transposed convs (EncoderTrainEngine's subclasses)."""
 
     def repack(self):
         """fp32 master weights -> MFMA fragment order (forward and data-gradient operators): one launch over a
-        descriptor table built once (the flat master tensor and the packed buffers never move)."""
+        descriptor table built once (the flat master tensor and the packed buffers never move), then _pack_decoder."""
         if getattr(self, '_pack_table', None) is None:
             descs = []
             for prefix in self.stage_names():
@@ -194,13 +202,17 @@ class TrainEngine:
                         descs.append(nv.make_desc(w, fwd, b, a, self.taps, 2, self.T))
                     else:
                         descs += fwd.descs(w) + dg.descs(w)
-            for l in range(self.levels - 2, -1, -1):
-                w = self.p(f'dec{l}.up.weight')
-                fwd, dg = self.pk[f'dec{l}.up']
+            for prefix, l in self.up_convs():
+                w = self.p(f'{prefix}.up.weight')
+                fwd, dg = self.pk[f'{prefix}.up']
                 descs.append(nv.make_desc(w, fwd, self.ch[l], self.ch[l + 1], self.npos, 3, self.T))
                 descs.append(nv.make_desc(w, dg, self.ch[l], self.ch[l + 1], self.npos, 4, self.T))
             self._pack_table = nv.PackTable(descs, self.dev, sources=[self.flat])
         self._pack_table.run()
+        self._pack_decoder()
+
+    def _pack_decoder(self):
+        """Launches that pack the operators _alloc_decoder allocated (after the table's)."""
 
     # ------------------------------------------------------------------ workspace
     def workspace(self, N, D, H, W):
@@ -208,9 +220,7 @@ class TrainEngine:
         ws = self._ws.get(key)
         if ws is not None:
             return ws
-        f = 2 ** (self.levels - 1)
-        if H % f or W % f or (self.dim == 3 and D % f) or (self.dim == 2 and D != 1):
-            raise ValueError(f'spatial size {(D, H, W)} must be divisible by {f}')
+        check_spatial(self.dim, self.levels, D, H, W)
         L, ch = self.levels, self.ch
         dims = [((D >> l) if self.dim == 3 else 1, H >> l, W >> l) for l in range(L)]
         act = lambda c, v: torch.empty(N * c * v, dtype=self.T, device=self.dev)
@@ -251,20 +261,24 @@ class TrainEngine:
             if l > 0:
                 ws[f'pin{l}'] = act(ch[l - 1], v)
                 ws[f'dpin{l}'] = act(ch[l - 1], v)
-        v0 = _vox(dims[0])
         ws['dy'] = act(max(ch[l] * _vox(dims[l]) for l in range(L)), 1)
         ws['stats'] = f32(max_stats)
         ws['wslab'] = f32(max_wslab)
         ws['bnslab'] = f32(max_bn)
         ws['bncoef'] = f32(3 * max(ch) * (N if self.gn else 1))
-        nparts = lib.iunet_head_loss_num_parts(N, v0)
-        ws['lslab'] = f32(nparts * self.ncls * 8)
-        ws['hslab'] = f32(lib.iunet_head_loss_bwd_num_parts(N, v0, self.ncls, ch[0]) * self.ncls * (ch[0] + 1))
-        ws['htmp'] = f32(self.ncls * (ch[0] + 1))
+        for k, n in self._loss_slabs(N, D, H, W, dims).items():
+            ws[k] = f32(n)
         ws['out4'] = f32(4)
         ws['coef'] = f32(self.ncls * 3)
         self._ws = {key: ws}
         return ws
+
+    def _loss_slabs(self, N, D, H, W, dims):
+        """fp32 element counts of the head / loss kernels' partial-sum slabs (the head on the full-resolution grid)."""
+        lib, v0, c0 = nv.lib(), _vox(dims[0]), self.ch[0]
+        return {'lslab': lib.iunet_head_loss_num_parts(N, v0) * self.ncls * 8,
+                'hslab': lib.iunet_head_loss_bwd_num_parts(N, v0, self.ncls, c0) * self.ncls * (c0 + 1),
+                'htmp': self.ncls * (c0 + 1)}
 
     def _P(self, t, off_elems=0):
         return ctypes.c_void_p(t.data_ptr() + off_elems * self.es)
@@ -675,9 +689,13 @@ class TrainEngine:
         if m.infer_dtype == self.T:
             return m.engine('eval')
         if getattr(self, '_eval_eng', None) is None:
-            from .engine import Engine
-            self._eval_eng = Engine(self.dim, self.levels, m.base, self.cin, self.ncls, self.T, self.dev, norm=self.norm,
-                                    groups=self.groups)
+            from .unet import NATIVE, native_engine
+            if getattr(m, 'architecture', 'U-Net') in NATIVE:
+                self._eval_eng = native_engine(m, self.T, self.dev)
+            else:
+                from .engine import Engine
+                self._eval_eng = Engine(self.dim, self.levels, m.base, self.cin, self.ncls, self.T, self.dev, norm=self.norm,
+                                        groups=self.groups)
         sig = (m._signature(), getattr(self, '_steps_seen', 0))
         if sig != getattr(self, '_eval_sig', None):              # re-pack only when a step (or anyone else) moved the weights: a validation
             self._eval_eng.load_eval(m.named_tensors())          # pass over many batches folds once (one launch over a cached table) and
@@ -762,6 +780,200 @@ class TrainEngine:
         o = ws['out4'].tolist()
         return {'Loss': o[0], 'Dice': o[1], 'IoU': o[2], 'MCC': o[3]}
 
+
+
+class EncoderTrainEngine(TrainEngine):
+    """Training of the encoder-only decoders (LinkNet, DeepLabV3, Segformer): the U-Net's encoder stages with X^l written to x{l} and a
+    decoder of the architecture's own, sequenced from Python on one GPU (TrainHandle builds the U-Net and U-Net++ only).  A subclass names
+    its `architecture`, adds its decoder's operators (_alloc_decoder / _pack_decoder) and buffers (_decoder_workspace), runs its decoder
+    between _encoder_forward and _encoder_backward, and gives each level's skip gradient: the buffers `skip_grad`{l} the workspace holds,
+    or its own _skip_grad."""
+    architecture = None
+    skip_grad = None
+
+    def __init__(self, model, lr=None, loss_kind='mcc_ce', betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
+                 loss_scale=None, process_group=None):
+        a = self.architecture
+        if process_group is not None:
+            raise NotImplementedError(f'{a} training runs on one GPU: a process_group (data parallel training) is not supported')
+        if getattr(model, 'norm', 'batch') != 'batch':
+            raise NotImplementedError(f'{a} training supports BatchNorm only')
+        if model.act_dtype not in (torch.float16, torch.bfloat16):
+            raise NotImplementedError(f"{a} training runs with 16-bit activations (act_dtype 'fp16' / 'bf16')")
+        super().__init__(model, lr=lr, loss_kind=loss_kind, betas=betas, eps=eps, weight_decay=weight_decay, loss_scale=loss_scale)
+
+    def stage_names(self):
+        return [f'enc{l}' for l in range(self.levels)]
+
+    def up_convs(self):
+        return []
+
+    def _handle(self):
+        self._steps_seen = getattr(self, '_steps_seen', 0) + 1
+        return None               # (no C-sequenced step: TrainHandle would build the U-Net)
+
+    # ------------------------------------------------------------------ workspace
+    def _act(self, N, c, v):
+        return torch.empty(N * c * v, dtype=self.T, device=self.dev)
+
+    def _f32(self, n):
+        return torch.empty(n, dtype=torch.float32, device=self.dev)
+
+    def _bn_bufs(self, ws, mx, N, name, c, v):
+        """scale / shift / mean / invstd of a BatchNorm over c channels of v voxels per sample, and its share of the running maxima."""
+        for k in ('scale', 'shift', 'mean', 'invstd'):
+            ws[f'{k}.{name}'] = self._f32(c)
+        mx['bn'] = max(mx['bn'], nv.lib().iunet_bn_bwd_num_parts(N, v) * c * 2)
+        mx['dy'] = max(mx['dy'], c * v)
+
+    def workspace(self, N, D, H, W):
+        """The encoder's buffers, the decoder's (_decoder_workspace, which extends the running maxima `mx` of the shared scratch
+        buffers: stats / wslab / bnslab / dy rows, and the widest BatchNorm in bncoef) and the head / loss slabs."""
+        key = (N, D, H, W)
+        ws = self._ws.get(key)
+        if ws is not None:
+            return ws
+        check_spatial(self.dim, self.levels, D, H, W)
+        L, ch, lib = self.levels, self.ch, nv.lib()
+        dims = [((D >> l) if self.dim == 3 else 1, H >> l, W >> l) for l in range(L)]
+        ws = {'dims': dims}
+        mx = {'stats': 0, 'wslab': 0, 'bn': 0, 'dy': 0, 'coef': max(ch)}
+        for l in range(L):
+            d, v = dims[l], _vox(dims[l])
+            ci = self.cin if l == 0 else ch[l - 1]
+            for j, (a, b) in enumerate(((ci, ch[l]), (ch[l], ch[l])), 1):
+                name = f'enc{l}.conv{j}'
+                ws['y.' + name] = self._act(N, b, v)
+                if j == 1:
+                    ws['z.' + name] = self._act(N, b, v)
+                    ws['dz.' + name] = self._act(N, b, v)
+                self._bn_bufs(ws, mx, N, name, b, v)
+                if name == 'enc0.conv1':
+                    mx['stats'] = max(mx['stats'], lib.iunet_conv3_num_tiles(self.dim, N, *d) * b * 2)
+                    mx['wslab'] = max(mx['wslab'], lib.iunet_first_conv_wgrad_blocks(self.dim, N, *d) * b * 112)
+                else:
+                    mx['stats'] = max(mx['stats'], max(lib.iunet_conv3_stats_parts(self.dim, N, *d, b, lay) for lay in (0, 2)) * b * 2)
+                    mx['wslab'] = max(mx['wslab'], lib.iunet_conv3_wgrad_slab_floats(self.dim, N, *d, a, b))
+            ws[f'x{l}'] = self._act(N, ch[l], v)                      # X^l
+            if self.skip_grad:
+                ws[f'{self.skip_grad}{l}'] = self._act(N, ch[l], v)   # the gradient X^l receives from the decoder
+            if l > 0:
+                ws[f'pin{l}'] = self._act(N, ch[l - 1], v)
+                ws[f'dpin{l}'] = self._act(N, ch[l - 1], v)
+        self._decoder_workspace(ws, mx, N, D, H, W)
+        ws['dy'] = self._act(N, mx['dy'], 1)
+        ws['stats'] = self._f32(mx['stats'])
+        ws['wslab'] = self._f32(mx['wslab'])
+        ws['bnslab'] = self._f32(mx['bn'])
+        ws['bncoef'] = self._f32(3 * mx['coef'])
+        for k, n in self._loss_slabs(N, D, H, W, dims).items():
+            ws[k] = self._f32(n)
+        ws['out4'] = self._f32(4)
+        ws['coef'] = self._f32(self.ncls * 3)
+        self._ws = {key: ws}
+        return ws
+
+    # ------------------------------------------------------------------ encoder
+    def _encoder_forward(self, ws, x, x_strides, N):
+        L, ch, dims = self.levels, self.ch, ws['dims']
+        for l in range(L):
+            v = _vox(dims[l])
+            ci = self.cin if l == 0 else ch[l - 1]
+            x2, act, z1p = self._conv2_input(ws, f'enc{l}', l, N)
+            if l == 0:
+                self._stage_conv_fwd(ws, 'enc0.conv1', None, 0, ci, ch[0], 0, z1p, ch[0] * v, N, x_raw=(x, x_strides))
+            else:
+                self._stage_conv_fwd(ws, f'enc{l}.conv1', self._P(ws[f'pin{l}']), ci * v, ci, ch[l], l, z1p, ch[l] * v, N)
+            pool = None
+            if l < L - 1:
+                do = dims[l + 1]
+                pool = (self._P(ws[f'pin{l + 1}']), ch[l] * _vox(do), do)
+            self._stage_conv_fwd(ws, f'enc{l}.conv2', x2, ch[l] * v, ch[l], ch[l], l, self._P(ws[f'x{l}']), ch[l] * v, N, x_act=act, pool=pool)
+
+    def _skip_grad(self, ws, l):
+        """(pointer, sample stride) of the gradient X^l receives from the decoder."""
+        return self._P(ws[f'{self.skip_grad}{l}']), self.ch[l] * _vox(ws['dims'][l])
+
+    def _encoder_backward(self, ws, x, x_strides, N):
+        """The encoder, bottom level upwards: X^l's gradient is its skip gradient + the max-pool route of the next level's input gradient."""
+        L, ch, dims, P = self.levels, self.ch, ws['dims'], self._P
+        for l in range(L - 1, -1, -1):
+            v = _vox(dims[l])
+            dz_ptr, dz_ss = self._skip_grad(ws, l)
+            pool_bwd = None
+            if l < L - 1:
+                do = dims[l + 1]
+                pool_bwd = (P(ws[f'dpin{l + 1}']), ch[l] * _vox(do), do)
+            x2, act, _ = self._conv2_input(ws, f'enc{l}', l, N)
+            self._stage_conv_bwd(ws, f'enc{l}.conv2', dz_ptr, dz_ss, None, ch[l] * v, x2, ch[l] * v, ch[l], ch[l], l,
+                                 P(ws[f'dz.enc{l}.conv1']), ch[l] * v, N, x_act=act, pool_bwd=pool_bwd, feeds=f'enc{l}.conv1')
+            dz1 = P(ws[f'dz.enc{l}.conv1'])
+            if l == 0:
+                self._stage_conv_bwd(ws, 'enc0.conv1', dz1, ch[0] * v, None, ch[0] * v, None, 0, self.cin, ch[0], 0, None, 0, N,
+                                     x_raw=(x, x_strides))
+            else:
+                self._stage_conv_bwd(ws, f'enc{l}.conv1', dz1, ch[l] * v, None, ch[l] * v, P(ws[f'pin{l}']), ch[l - 1] * v,
+                                     ch[l - 1], ch[l], l, P(ws[f'dpin{l}']), ch[l - 1] * v, N)
+
+
+class CoarseTrainEngine(EncoderTrainEngine):
+    """DeepLabV3 and Segformer: the decoder's activation F (self.C channels, ws['feat']) on level `coarse_level`'s grid, the 1x1 head
+    giving coarse logits ws['lc'] there, upsampled x 2^coarse_level (align_corners=True) inside the fused softmax + loss kernel."""
+    coarse_level = None
+
+    def _coarse_bufs(self, ws, N, D, H, W):
+        """The coarse logits and the loss backward's buffers (the gradient at full resolution, the interpolation's adjoint)."""
+        dc = ws['dims'][self.coarse_level]
+        ws['lc'] = self._f32(N * self.ncls * _vox(dc))
+        ws['dlc'] = self._f32(N * self.ncls * _vox(dc))
+        ws['dfine'] = self._f32(N * self.ncls * D * H * W)
+        ws['utmp'] = self._f32(N * self.ncls * D * H * dc[2])
+
+    def _loss_slabs(self, N, D, H, W, dims):
+        lib = nv.lib()
+        return {'lslab': lib.iunet_dl_up_loss_num_parts(N, D * H * W) * self.ncls * 8,
+                'hslab': lib.iunet_dl_head_bwd_parts(N, _vox(dims[self.coarse_level])) * (self.C // 8 + 1) * 80}
+
+    def _up_loss(self, ws, lc, y, w, N):
+        tdt = {torch.float32: 0, torch.float16: 1}[y.dtype]
+        if w is not None and w.dtype != y.dtype:
+            w = w.to(y.dtype)
+        dc = ws['dims'][self.coarse_level]
+        nv.call('iunet_dl_up_loss_fwd', self.dim, nv.ptr(lc), self.ncls, dc[0], dc[1], dc[2], 2 ** self.coarse_level, nv.ptr(y), nv.ptr(w), tdt,
+                self.kind, nv.ptr(ws['lslab']), nv.ptr(ws['out4']), nv.ptr(ws['coef']), N, nv.stream())
+        return tdt, w
+
+    def train_loss_forward(self, ws, y, w, N, vox):
+        return self._up_loss(ws, ws['lc'], y, w, N)
+
+    def _head_fwd(self, ws, N):
+        """The 1x1 head on F: the coarse logits ws['lc']."""
+        dc, C = ws['dims'][self.coarse_level], self.C
+        vc = _vox(dc)
+        nv.call('iunet_head_fwd', self.dt, self._P(ws['feat']), C * vc, C, nv.ptr(self.p('head.weight')), nv.ptr(self.p('head.bias')), self.ncls,
+                nv.ptr(ws['lc']), None, None, nv.ll_array((self.ncls * vc, vc, dc[1] * dc[2], dc[2], 1)), 1.0, 0, N, dc[0], dc[1], dc[2],
+                nv.stream())
+
+    def _head_bwd(self, ws, y, w, tdt, N):
+        """The loss gradient at full resolution, the interpolation's adjoint as a gather, the head: F's gradient into ws['dfeat']."""
+        dc, C, s = ws['dims'][self.coarse_level], self.C, nv.stream()
+        vc = _vox(dc)
+        nv.call('iunet_dl_up_loss_bwd', self.dim, nv.ptr(ws['lc']), self.ncls, dc[0], dc[1], dc[2], 2 ** self.coarse_level, nv.ptr(y), nv.ptr(w),
+                tdt, nv.ptr(ws['coef']), nv.ptr(self.state), nv.ptr(ws['dfine']), nv.ptr(ws['utmp']), nv.ptr(ws['dlc']), N, s)
+        nv.call('iunet_dl_head_bwd', self.dt, self._P(ws['feat']), C * vc, C, nv.ptr(self.p('head.weight')), nv.ptr(ws['dlc']), self.ncls,
+                self._P(ws['dfeat']), C * vc, nv.ptr(ws['hslab']), nv.ptr(self.g('head.weight')), nv.ptr(self.g('head.bias')), N, vc, s)
+
+    def eval_step(self, X, y, w=None, sync=True):
+        """validation_step: eval-mode BatchNorm (and no dropout); the coarse logits of the eval forward, upsampled in the fused loss kernel."""
+        self.sync_weights()
+        X, y, w, N, D, H, W, vox, xs = self._prep(X, y, w)
+        lc = self._eval_engine().coarse_logits(X, xs, N, D, H, W)
+        ws = self.workspace(N, D, H, W)
+        self._up_loss(ws, lc, y, w, N)
+        if not sync:
+            return ws['out4']
+        o = ws['out4'].tolist()
+        return {'Loss': o[0], 'Dice': o[1], 'IoU': o[2], 'MCC': o[3]}
 
 _HOOK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int)       # iunet_train_hook
 

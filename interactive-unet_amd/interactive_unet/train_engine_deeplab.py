@@ -1,5 +1,5 @@
-"""Native 16-bit training step of DeepLabV3 (engine_deeplab.py has the graph), sequenced from Python on train_engine.TrainEngine's encoder
-stage helpers, flat AdamW, loss scaling and device-resident training state.
+"""Native 16-bit training step of DeepLabV3 (engine_deeplab.py has the graph), sequenced from Python on train_engine.EncoderTrainEngine's encoder
+and train_engine.CoarseTrainEngine's coarse-logit loss, flat AdamW, loss scaling and device-resident training state.
 
 Forward on the coarse grid (csrc/deeplab.hip): each spatial ASPP branch writes its raw output into its slot of one 4C-channel buffer plus
 BatchNorm partial sums; iunet_bn_finalize writes its scale / shift into the matching quarter of one [4C] pair, so the projection reads the
@@ -18,43 +18,32 @@ import torch
 from . import _native as nv
 from .engine import BN_EPS
 from .engine_deeplab import BRANCHES
-from .train_engine import BN_MOMENTUM, TrainEngine, _vox
+from .train_engine import BN_MOMENTUM, CoarseTrainEngine, _vox
 
 N1_MESSAGE = 'Expected more than 1 value per channel when training (the ASPP pooling branch normalises over the batch)'
 
 
-class DeepLabV3TrainEngine(TrainEngine):
+class DeepLabV3TrainEngine(CoarseTrainEngine):
+    architecture = 'DeepLabV3'
+
     def __init__(self, model, lr=None, loss_kind='mcc_ce', betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
                  loss_scale=None, process_group=None, seed=None):
-        if process_group is not None:
-            raise NotImplementedError('DeepLabV3 training runs on one GPU: a process_group (data parallel training) is not supported')
-        if getattr(model, 'norm', 'batch') != 'batch':
-            raise NotImplementedError('DeepLabV3 training supports BatchNorm only')
-        if model.act_dtype not in (torch.float16, torch.bfloat16):
-            raise NotImplementedError("DeepLabV3 training runs with 16-bit activations (act_dtype 'fp16' / 'bf16')")
         self.C = model.decoder_channels
         self.rates = (0,) + tuple(model.decoder_atrous_rates)
         self.p_drop = float(model.decoder_aspp_dropout)
-        super().__init__(model, lr=lr, loss_kind=loss_kind, betas=betas, eps=eps, weight_decay=weight_decay, loss_scale=loss_scale)
+        super().__init__(model, lr=lr, loss_kind=loss_kind, betas=betas, eps=eps, weight_decay=weight_decay, loss_scale=loss_scale,
+                         process_group=process_group)
         self.kvol = 3 ** self.dim
         self.gen = torch.Generator(device=self.dev)
         self.gen.manual_seed(0 if seed is None else int(seed))
         self.last_dropout_mask = None
 
-    # ------------------------------------------------------------------ graph
-    def stage_names(self):
-        return [f'enc{l}' for l in range(self.levels)]
+    @property
+    def coarse_level(self):
+        return self.levels - 1
 
-    def _alloc_packed(self):
-        self.pk = {}
-        for prefix in self.stage_names():
-            ci, co, _ = self.stage_io(prefix)
-            for j, (a, b) in enumerate(((ci, co), (co, co)), 1):
-                name = f'{prefix}.conv{j}'
-                if name == 'enc0.conv1':
-                    self.pk[name] = (torch.empty(nv.lib().iunet_pack_first_conv_elems(b, a, self.taps), dtype=self.T, device=self.dev), None)
-                else:
-                    self.pk[name] = (nv.PackedConv(b, a, self.taps, self.T, self.dev), nv.PackedConv(b, a, self.taps, self.T, self.dev, dgrad=True))
+    # ------------------------------------------------------------------ graph
+    def _alloc_decoder(self):
         C, Cb, kv = self.C, self.ch[-1], 3 ** self.dim
         e = lambda n: torch.empty(n, dtype=self.T, device=self.dev)
         for b, r in zip(BRANCHES, self.rates):
@@ -70,21 +59,7 @@ class DeepLabV3TrainEngine(TrainEngine):
         nv.call('iunet_dl_pack', self.dt, self.dim, mode, ksz, nv.ptr(self.p(name)), None, None, None, None, 0.0, nv.ptr(dst), None,
                 Cout, Cin, Cin_tot, 0, k_off, ld, nv.stream())
 
-    def repack(self):
-        if getattr(self, '_pack_table', None) is None:
-            descs = []
-            for prefix in self.stage_names():
-                ci, co, _ = self.stage_io(prefix)
-                for j, (a, b) in enumerate(((ci, co), (co, co)), 1):
-                    name = f'{prefix}.conv{j}'
-                    w = self.p(name + '.weight')
-                    fwd, dg = self.pk[name]
-                    if name == 'enc0.conv1':
-                        descs.append(nv.make_desc(w, fwd, b, a, self.taps, 2, self.T))
-                    else:
-                        descs += fwd.descs(w) + dg.descs(w)
-            self._pack_table = nv.PackTable(descs, self.dev, sources=[self.flat])
-        self._pack_table.run()
+    def _pack_decoder(self):
         C, Cb, kv = self.C, self.ch[-1], 3 ** self.dim
         for k, (b, r) in enumerate(zip(BRANCHES, self.rates)):
             ksz, kk = (1, 1) if r == 0 else (3, kv)
@@ -96,47 +71,9 @@ class DeepLabV3TrainEngine(TrainEngine):
         self._dl_pack(1, 3, 'dec.conv.weight', self.pk['dg.dec'], C, C, C, 0, kv * C)
 
     # ------------------------------------------------------------------ workspace
-    def workspace(self, N, D, H, W):
-        key = (N, D, H, W)
-        ws = self._ws.get(key)
-        if ws is not None:
-            return ws
-        f = 2 ** (self.levels - 1)
-        if H % f or W % f or (self.dim == 3 and D % f) or (self.dim == 2 and D != 1):
-            raise ValueError(f'spatial size {(D, H, W)} must be divisible by {f}')
-        L, ch, lib, C = self.levels, self.ch, nv.lib(), self.C
-        dims = [((D >> l) if self.dim == 3 else 1, H >> l, W >> l) for l in range(L)]
-        act = lambda c, v: torch.empty(N * c * v, dtype=self.T, device=self.dev)
-        f32 = lambda n: torch.empty(n, dtype=torch.float32, device=self.dev)
-        ws = {'dims': dims}
-        max_stats, max_wslab, max_bn, max_dy = 0, 0, 0, 0
-
-        def bn_bufs(name, c, v):
-            nonlocal max_bn, max_dy
-            for k in ('scale', 'shift', 'mean', 'invstd'):
-                ws[f'{k}.{name}'] = f32(c)
-            max_bn = max(max_bn, lib.iunet_bn_bwd_num_parts(N, v) * c * 2)
-            max_dy = max(max_dy, c * v)
-        for l in range(L):
-            d, v = dims[l], _vox(dims[l])
-            ci = self.cin if l == 0 else ch[l - 1]
-            for j, (a, b) in enumerate(((ci, ch[l]), (ch[l], ch[l])), 1):
-                name = f'enc{l}.conv{j}'
-                ws['y.' + name] = act(b, v)
-                if j == 1:
-                    ws['z.' + name] = act(b, v)
-                    ws['dz.' + name] = act(b, v)
-                bn_bufs(name, b, v)
-                if name == 'enc0.conv1':
-                    max_stats = max(max_stats, lib.iunet_conv3_num_tiles(self.dim, N, *d) * b * 2)
-                    max_wslab = max(max_wslab, lib.iunet_first_conv_wgrad_blocks(self.dim, N, *d) * b * 112)
-                else:
-                    max_stats = max(max_stats, max(lib.iunet_conv3_stats_parts(self.dim, N, *d, b, lay) for lay in (0, 2)) * b * 2)
-                    max_wslab = max(max_wslab, lib.iunet_conv3_wgrad_slab_floats(self.dim, N, *d, a, b))
-            ws[f'x{l}'] = act(ch[l], v)
-            if l > 0:
-                ws[f'pin{l}'] = act(ch[l - 1], v)
-                ws[f'dpin{l}'] = act(ch[l - 1], v)
+    def _decoder_workspace(self, ws, mx, N, D, H, W):
+        dims, ch, lib, C, L = ws['dims'], self.ch, nv.lib(), self.C, self.levels
+        act, f32 = (lambda c, v: self._act(N, c, v)), self._f32
         dc, vc, Cb = dims[-1], _vox(dims[-1]), ch[-1]
         ws['dx'] = act(Cb, vc)                               # the gradient of X^{L-1}
         ws['zeros'] = act(max([ch[l] * _vox(dims[l]) for l in range(L - 1)] + [8]), 1).zero_()   # the skip gradient of the upper levels
@@ -146,34 +83,24 @@ class DeepLabV3TrainEngine(TrainEngine):
         for k in ('scale', 'shift', 'mean', 'invstd'):
             ws[f'{k}.cat'] = f32(4 * C)
         for name in ('aspp.project', 'dec', 'aspp.pool'):
-            bn_bufs(name, C, vc)
-        max_bn = max(max_bn, lib.iunet_bn_bwd_num_parts(N, vc) * C * 2)
+            self._bn_bufs(ws, mx, N, name, C, vc)
+        mx['coef'] = max(mx['coef'], 4 * C)
         ws['y.aspp.project'], ws['a'], ws['da'] = act(C, vc), act(C, vc), act(C, vc)
         ws['y.dec'], ws['feat'], ws['dfeat'] = act(C, vc), act(C, vc), act(C, vc)
-        max_stats = max(max_stats, lib.iunet_dl_stats_parts(N, *dc, C) * C * 2, N * C * 2)
+        mx['stats'] = max(mx['stats'], lib.iunet_dl_stats_parts(N, *dc, C) * C * 2, N * C * 2)
         for r, ci, co in [(r, Cb, C) for r in self.rates] + [(0, 4 * C, C), (1, C, C)]:
-            max_wslab = max(max_wslab, lib.iunet_dl_wgrad_slab_floats(self.dim, r, N, *dc, ci, co))
+            mx['wslab'] = max(mx['wslab'], lib.iunet_dl_wgrad_slab_floats(self.dim, r, N, *dc, ci, co))
         for k in ('xmean', 'dxmean'):
             ws[k] = f32(N * Cb)
         for k in ('ypool', 'bp', 'psb', 'dpsb'):
             ws[k] = f32(N * C)
         ws['pscratch'] = f32(2 * N * C)
-        vf = _vox((D, H, W))
-        ws['lc'] = f32(N * self.ncls * vc)
-        ws['dlc'] = f32(N * self.ncls * vc)
-        ws['dfine'] = f32(N * self.ncls * vf)
-        ws['utmp'] = f32(N * self.ncls * D * H * dc[2])
-        ws['dy'] = act(max_dy, 1)
-        ws['stats'] = f32(max_stats)
-        ws['wslab'] = f32(max_wslab)
-        ws['bnslab'] = f32(max_bn)
-        ws['bncoef'] = f32(3 * max(max(ch), 4 * C))
-        ws['lslab'] = f32(lib.iunet_dl_up_loss_num_parts(N, vf) * self.ncls * 8)
-        ws['hslab'] = f32(lib.iunet_dl_head_bwd_parts(N, vc) * (C // 8 + 1) * 80)
-        ws['out4'] = f32(4)
-        ws['coef'] = f32(self.ncls * 3)
-        self._ws = {key: ws}
-        return ws
+        self._coarse_bufs(ws, N, D, H, W)
+
+    def _skip_grad(self, ws, l):
+        if l == self.levels - 1:
+            return self._P(ws['dx']), self.ch[l] * _vox(ws['dims'][l])
+        return self._P(ws['zeros']), 0          # the upper levels receive gradient through the max-pool only
 
     # ------------------------------------------------------------------ forward
     def _finalize(self, ws, bn, stats_parts, c, count, out):
@@ -193,21 +120,9 @@ class DeepLabV3TrainEngine(TrainEngine):
     def forward_train(self, x, x_strides, N, D, H, W):
         ws = self.workspace(N, D, H, W)
         self._ws_cur = ws
+        self._encoder_forward(ws, x, x_strides, N)
         L, ch, dims, C = self.levels, self.ch, ws['dims'], self.C
         s = nv.stream()
-        for l in range(L):
-            v = _vox(dims[l])
-            ci = self.cin if l == 0 else ch[l - 1]
-            x2, act, z1p = self._conv2_input(ws, f'enc{l}', l, N)
-            if l == 0:
-                self._stage_conv_fwd(ws, 'enc0.conv1', None, 0, ci, ch[0], 0, z1p, ch[0] * v, N, x_raw=(x, x_strides))
-            else:
-                self._stage_conv_fwd(ws, f'enc{l}.conv1', self._P(ws[f'pin{l}']), ci * v, ci, ch[l], l, z1p, ch[l] * v, N)
-            pool = None
-            if l < L - 1:
-                do = dims[l + 1]
-                pool = (self._P(ws[f'pin{l + 1}']), ch[l] * _vox(do), do)
-            self._stage_conv_fwd(ws, f'enc{l}.conv2', x2, ch[l] * v, ch[l], ch[l], l, self._P(ws[f'x{l}']), ch[l] * v, N, x_act=act, pool=pool)
         dc, vc, Cb, X = dims[-1], _vox(dims[-1]), ch[-1], ws[f'x{L - 1}']
         nparts = nv.lib().iunet_dl_stats_parts(N, *dc, C)
         # pooling branch -> per-sample bias of the projection
@@ -236,21 +151,8 @@ class DeepLabV3TrainEngine(TrainEngine):
         self._finalize(ws, 'dec.bn', nparts, C, N * vc, 'dec')
         nv.call('iunet_bn_relu_fwd', self.dt, self._P(ws['y.dec']), C * vc, self._P(ws['feat']), C * vc, nv.ptr(ws['scale.dec']),
                 nv.ptr(ws['shift.dec']), C, N, vc, s)
-        nv.call('iunet_head_fwd', self.dt, self._P(ws['feat']), C * vc, C, nv.ptr(self.p('head.weight')), nv.ptr(self.p('head.bias')), self.ncls,
-                nv.ptr(ws['lc']), None, None, nv.ll_array((self.ncls * vc, vc, dc[1] * dc[2], dc[2], 1)), 1.0, 0, N, dc[0], dc[1], dc[2], s)
+        self._head_fwd(ws, N)
         return ws
-
-    def _up_loss(self, ws, lc, y, w, N):
-        tdt = {torch.float32: 0, torch.float16: 1}[y.dtype]
-        if w is not None and w.dtype != y.dtype:
-            w = w.to(y.dtype)
-        dc = ws['dims'][-1]
-        nv.call('iunet_dl_up_loss_fwd', self.dim, nv.ptr(lc), self.ncls, dc[0], dc[1], dc[2], 2 ** (self.levels - 1), nv.ptr(y), nv.ptr(w), tdt,
-                self.kind, nv.ptr(ws['lslab']), nv.ptr(ws['out4']), nv.ptr(ws['coef']), N, nv.stream())
-        return tdt, w
-
-    def train_loss_forward(self, ws, y, w, N, vox):
-        return self._up_loss(ws, ws['lc'], y, w, N)
 
     # ------------------------------------------------------------------ backward
     def _bn_bwd(self, ws, dz, dz_ss, y, y_ss, dy, dy_ss, bn, name, off, c, v, N):
@@ -269,10 +171,7 @@ class DeepLabV3TrainEngine(TrainEngine):
         s = nv.stream()
         dc, vc, Cb, X = dims[-1], _vox(dims[-1]), ch[-1], ws[f'x{L - 1}']
         P = self._P
-        nv.call('iunet_dl_up_loss_bwd', self.dim, nv.ptr(ws['lc']), self.ncls, dc[0], dc[1], dc[2], 2 ** (L - 1), nv.ptr(y), nv.ptr(w), tdt,
-                nv.ptr(ws['coef']), nv.ptr(self.state), nv.ptr(ws['dfine']), nv.ptr(ws['utmp']), nv.ptr(ws['dlc']), N, s)
-        nv.call('iunet_dl_head_bwd', self.dt, P(ws['feat']), C * vc, C, nv.ptr(self.p('head.weight')), nv.ptr(ws['dlc']), self.ncls,
-                P(ws['dfeat']), C * vc, nv.ptr(ws['hslab']), nv.ptr(self.g('head.weight')), nv.ptr(self.g('head.bias')), N, vc, s)
+        self._head_bwd(ws, y, w, tdt, N)
         # dec.conv
         self._bn_bwd(ws, P(ws['dfeat']), C * vc, P(ws['y.dec']), C * vc, P(ws['dy']), C * vc, 'dec.bn', 'dec', 0, C, vc, N)
         self._wgrad(ws, 1, P(ws['a']), C * vc, P(ws['dy']), C * vc, 'dec.conv.weight', C, N, dc, C, C)
@@ -302,24 +201,7 @@ class DeepLabV3TrainEngine(TrainEngine):
         kv = self.kvol
         self._dl(self.pk['dg.aspp'], self.aspp_ld, P(ws['dycat']), 4 * C * vc, P(ws['dx']), Cb * vc, list(self.rates), [0, C, 2 * C, 3 * C],
                  [0, C, C + kv * C, C + 2 * kv * C], N, dc, C, Cb, psb=nv.ptr(ws['dxmean']), psb_scale=1.0 / vc, stats=False)
-        # encoder
-        for l in range(L - 1, -1, -1):
-            v = _vox(dims[l])
-            if l == L - 1:
-                dz_ptr, dz_ss, pool_bwd = P(ws['dx']), ch[l] * v, None
-            else:
-                do = dims[l + 1]
-                dz_ptr, dz_ss, pool_bwd = P(ws['zeros']), 0, (P(ws[f'dpin{l + 1}']), ch[l] * _vox(do), do)
-            x2, act, _ = self._conv2_input(ws, f'enc{l}', l, N)
-            self._stage_conv_bwd(ws, f'enc{l}.conv2', dz_ptr, dz_ss, None, ch[l] * v, x2, ch[l] * v, ch[l], ch[l], l,
-                                 P(ws[f'dz.enc{l}.conv1']), ch[l] * v, N, x_act=act, pool_bwd=pool_bwd, feeds=f'enc{l}.conv1')
-            dz1 = P(ws[f'dz.enc{l}.conv1'])
-            if l == 0:
-                self._stage_conv_bwd(ws, 'enc0.conv1', dz1, ch[0] * v, None, ch[0] * v, None, 0, self.cin, ch[0], 0, None, 0, N,
-                                     x_raw=(x, x_strides))
-            else:
-                self._stage_conv_bwd(ws, f'enc{l}.conv1', dz1, ch[l] * v, None, ch[l] * v, P(ws[f'pin{l}']), ch[l - 1] * v,
-                                     ch[l - 1], ch[l], l, P(ws[f'dpin{l}']), ch[l - 1] * v, N)
+        self._encoder_backward(ws, x, x_strides, N)
 
     # ------------------------------------------------------------------ public steps
     def _check_batch(self, X):
@@ -333,34 +215,3 @@ class DeepLabV3TrainEngine(TrainEngine):
     def step_forward(self, X, y, w=None):
         self._check_batch(X)
         return super().step_forward(X, y, w)
-
-    def _handle(self):
-        self._steps_seen = getattr(self, '_steps_seen', 0) + 1
-        return None               # (no C-sequenced DeepLabV3 step: TrainHandle would build the U-Net)
-
-    def _eval_engine(self):
-        """The folded-BatchNorm DeepLabV3 forward in the training dtype."""
-        m = self.model
-        if m.infer_dtype == self.T:
-            return m.engine('eval')
-        if getattr(self, '_eval_eng', None) is None:
-            from .engine_deeplab import DeepLabV3Engine
-            self._eval_eng = DeepLabV3Engine(self.dim, self.levels, m.base, self.cin, self.ncls, self.T, self.dev,
-                                             decoder_channels=self.C, rates=self.rates[1:])
-        sig = (m._signature(), getattr(self, '_steps_seen', 0))
-        if sig != getattr(self, '_eval_sig', None):
-            self._eval_eng.load_eval(m.named_tensors())
-            self._eval_sig = sig
-        return self._eval_eng
-
-    def eval_step(self, X, y, w=None, sync=True):
-        """validation_step: eval-mode BatchNorm, no dropout; the coarse logits of the eval forward, upsampled in the fused loss kernel."""
-        self.sync_weights()
-        X, y, w, N, D, H, W, vox, xs = self._prep(X, y, w)
-        lc = self._eval_engine().coarse_logits(X, xs, N, D, H, W)
-        ws = self.workspace(N, D, H, W)
-        self._up_loss(ws, lc, y, w, N)
-        if not sync:
-            return ws['out4']
-        o = ws['out4'].tolist()
-        return {'Loss': o[0], 'Dice': o[1], 'IoU': o[2], 'MCC': o[3]}

@@ -18,7 +18,7 @@ import ctypes
 import torch
 
 from . import _native as nv
-from .engine import BN_EPS, _vox
+from .engine import BN_EPS, _vox, check_spatial
 from .train_engine import LOSS_KINDS
 
 BN_MOMENTUM = 0.1
@@ -126,9 +126,7 @@ class TrainEngineF32:
         ws = self._ws.get(key)
         if ws is not None:
             return ws
-        f = 2 ** (self.levels - 1)
-        if H % f or W % f or (self.dim == 3 and D % f) or (self.dim == 2 and D != 1):
-            raise ValueError(f'spatial size {(D, H, W)} must be divisible by {f}')
+        check_spatial(self.dim, self.levels, D, H, W)
         L, ch = self.levels, self.ch
         dims = [((D >> l) if self.dim == 3 else 1, H >> l, W >> l) for l in range(L)]
         f32 = lambda n: torch.empty(int(n), dtype=torch.float32, device=self.dev)
@@ -384,21 +382,12 @@ class TrainEngineF32:
 
 
 def make_train_engine(model, **kw):
-    """The training engine of a module: 16-bit activations (TrainEngine) or, for act_dtype='fp32', the fp32 parity form; U-Net++
-    modules train on train_engine_nested.NestedTrainEngine, LinkNet modules on train_engine_linknet.LinkNetTrainEngine, DeepLabV3 modules on
-    train_engine_deeplab.DeepLabV3TrainEngine, Segformer modules on train_engine_segformer.SegformerTrainEngine."""
-    if getattr(model, 'architecture', 'U-Net') == 'Segformer':
-        from .train_engine_segformer import SegformerTrainEngine
-        return SegformerTrainEngine(model, **kw)
-    if getattr(model, 'architecture', 'U-Net') == 'DeepLabV3':
-        from .train_engine_deeplab import DeepLabV3TrainEngine
-        return DeepLabV3TrainEngine(model, **kw)
-    if getattr(model, 'architecture', 'U-Net') == 'LinkNet':
-        from .train_engine_linknet import LinkNetTrainEngine
-        return LinkNetTrainEngine(model, **kw)
-    if getattr(model, 'architecture', 'U-Net') == 'U-Net++':
-        from .train_engine_nested import NestedTrainEngine
-        return NestedTrainEngine(model, **kw)
+    """The training engine of a module: 16-bit activations (TrainEngine) or, for act_dtype='fp32', the fp32 parity form; the other
+    architectures train on the engine unet.NATIVE names."""
+    from .unet import NATIVE, native_class
+    spec = NATIVE.get(getattr(model, 'architecture', 'U-Net'))
+    if spec is not None:
+        return native_class(spec['train'])(model, **kw)
     if model.act_dtype == torch.float32:
         kw.pop('loss_scale', None)
         return TrainEngineF32(model, **kw)

@@ -21,6 +21,7 @@ import ctypes
 import torch
 
 from . import _native as nv
+from .engine import check_spatial
 from .train_engine import TrainEngine, _vox
 from .unet import nested_nodes
 
@@ -58,40 +59,8 @@ class NestedTrainEngine(TrainEngine):
         i, j = (int(t) for t in prefix[3:].split('_'))
         return (j + 1) * self.ch[i], self.ch[i], i
 
-    def _alloc_packed(self):
-        self.pk = {}
-        for prefix in self.stage_names():
-            ci, co, _ = self.stage_io(prefix)
-            for j, (a, b) in enumerate(((ci, co), (co, co)), 1):
-                name = f'{prefix}.conv{j}'
-                if name == 'enc0.conv1':
-                    self.pk[name] = (torch.empty(nv.lib().iunet_pack_first_conv_elems(b, a, self.taps), dtype=self.T, device=self.dev), None)
-                else:
-                    self.pk[name] = (nv.PackedConv(b, a, self.taps, self.T, self.dev), nv.PackedConv(b, a, self.taps, self.T, self.dev, dgrad=True))
-        for i, j in self.nodes:
-            n = self.ch[i + 1] * self.ch[i] * self.npos
-            self.pk[f'dec{i}_{j}.up'] = (torch.empty(n, dtype=self.T, device=self.dev), torch.empty(n, dtype=self.T, device=self.dev))
-
-    def repack(self):
-        if getattr(self, '_pack_table', None) is None:
-            descs = []
-            for prefix in self.stage_names():
-                ci, co, _ = self.stage_io(prefix)
-                for j, (a, b) in enumerate(((ci, co), (co, co)), 1):
-                    name = f'{prefix}.conv{j}'
-                    w = self.p(name + '.weight')
-                    fwd, dg = self.pk[name]
-                    if name == 'enc0.conv1':
-                        descs.append(nv.make_desc(w, fwd, b, a, self.taps, 2, self.T))
-                    else:
-                        descs += fwd.descs(w) + dg.descs(w)
-            for i, j in self.nodes:
-                w = self.p(f'dec{i}_{j}.up.weight')
-                fwd, dg = self.pk[f'dec{i}_{j}.up']
-                descs.append(nv.make_desc(w, fwd, self.ch[i], self.ch[i + 1], self.npos, 3, self.T))
-                descs.append(nv.make_desc(w, dg, self.ch[i], self.ch[i + 1], self.npos, 4, self.T))
-            self._pack_table = nv.PackTable(descs, self.dev, sources=[self.flat])
-        self._pack_table.run()
+    def up_convs(self):
+        return [(f'dec{i}_{j}', i) for i, j in self.nodes]
 
     # ------------------------------------------------------------------ workspace
     def workspace(self, N, D, H, W):
@@ -99,9 +68,7 @@ class NestedTrainEngine(TrainEngine):
         ws = self._ws.get(key)
         if ws is not None:
             return ws
-        f = 2 ** (self.levels - 1)
-        if H % f or W % f or (self.dim == 3 and D % f) or (self.dim == 2 and D != 1):
-            raise ValueError(f'spatial size {(D, H, W)} must be divisible by {f}')
+        check_spatial(self.dim, self.levels, D, H, W)
         L, ch, lib = self.levels, self.ch, nv.lib()
         dims = [((D >> l) if self.dim == 3 else 1, H >> l, W >> l) for l in range(L)]
         act = lambda c, v: torch.empty(N * c * v, dtype=self.T, device=self.dev)
@@ -328,17 +295,3 @@ class NestedTrainEngine(TrainEngine):
     def train_loss_forward(self, ws, y, w, N, vox):
         feat, act = self._head_input(ws)
         return self.loss_forward(ws, feat, y, w, N, vox, act=act)
-
-    def _eval_engine(self):
-        """The folded-BatchNorm nested forward in the training dtype (its features feed the fused head + loss kernel)."""
-        m = self.model
-        if m.infer_dtype == self.T:
-            return m.engine('eval')
-        if getattr(self, '_eval_eng', None) is None:
-            from .engine_nested import NestedEngine
-            self._eval_eng = NestedEngine(self.dim, self.levels, m.base, self.cin, self.ncls, self.T, self.dev)
-        sig = (m._signature(), getattr(self, '_steps_seen', 0))
-        if sig != getattr(self, '_eval_sig', None):
-            self._eval_eng.load_eval(m.named_tensors())
-            self._eval_sig = sig
-        return self._eval_eng

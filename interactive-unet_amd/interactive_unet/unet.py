@@ -22,6 +22,7 @@ instruction for prediction (engine_f32.py) AND training (train_engine_f32.py: th
 CPU autograd), 1/16 of the 16-bit rate; 'fp16x2' is inference-only.  `infer_dtype` overrides the
 mode of `forward()` alone.
 """
+import importlib
 import math
 import warnings
 
@@ -117,94 +118,82 @@ def param_shapes(dim=2, levels=4, base=32, cin=1, ncls=2, architecture='U-Net', 
     return shapes
 
 
-def _check_nested(levels, act_dtype, weight_dtype, norm, infer_dtype, infer_policy):
-    """The combinations the native U-Net++ supports: BatchNorm, 16-bit training (fp16 / bf16), prediction in fp32 (default) or
-    fp16 / bf16, 2 .. 9 levels (a stage output has at most 8 summed gradient sources)."""
-    what = ("U-Net++ supports norm='batch', act_dtype None / 'fp16' / 'bf16' (training), infer_dtype None / 'fp32' / 'fp16' / "
-            "'bf16' (prediction) and 2 .. 9 levels")
+# The architectures beside the U-Net: their native limits (the level range; whether base, input channels and classes are limited; the
+# decoder-width argument; DeepLabV3's ASPP arguments), their forward engines (module, 16-bit class, fp32 class, constructor keywords) and
+# their training engine (module, class)
+NATIVE = {
+    NESTED: dict(levels=(2, 9), shape=False, width=None, aspp=False,
+                 engines=('engine_nested', 'NestedEngine', 'NestedEngineF32', lambda m: {}), train=('train_engine_nested', 'NestedTrainEngine')),
+    LINKNET: dict(levels=(2, 6), shape=True, width=None, aspp=False,
+                  engines=('engine_linknet', 'LinkNetEngine', 'LinkNetEngineF32', lambda m: {}),
+                  train=('train_engine_linknet', 'LinkNetTrainEngine')),
+    DEEPLAB: dict(levels=(2, 6), shape=True, width='decoder_channels', aspp=True,
+                  engines=('engine_deeplab', 'DeepLabV3Engine', 'DeepLabV3EngineF32',
+                           lambda m: dict(decoder_channels=m.decoder_channels, rates=m.decoder_atrous_rates)),
+                  train=('train_engine_deeplab', 'DeepLabV3TrainEngine')),
+    SEGFORMER: dict(levels=(3, 6), shape=True, width='decoder_segmentation_channels', aspp=False,
+                    engines=('engine_segformer', 'SegformerEngine', 'SegformerEngineF32',
+                             lambda m: dict(decoder_channels=m.decoder_segmentation_channels)),
+                    train=('train_engine_segformer', 'SegformerTrainEngine')),
+}
+
+
+def native_class(where):
+    """(module, class name) -> the class, imported on first use."""
+    return getattr(importlib.import_module('.' + where[0], __package__), where[1])
+
+
+def native_engine(model, dtype, device):
+    """The forward engine of a NATIVE module in `dtype` (torch.float32: the fp32 form, else 16-bit activations)."""
+    module, f16, f32, kw = NATIVE[model.architecture]['engines']
+    args = (model.dim, model.levels, model.base, model.num_channels, model.num_classes)
+    if dtype == torch.float32:
+        return native_class((module, f32))(*args, device=device, **kw(model))
+    return native_class((module, f16))(*args, act_dtype=dtype, device=device, **kw(model))
+
+
+def _check_native(architecture, levels, base, cin, ncls, act_dtype, weight_dtype, norm, infer_dtype, infer_policy, **decoder):
+    """The combinations a NATIVE architecture supports: BatchNorm, 16-bit training (fp16 / bf16), prediction in fp32 (default) or fp16 /
+    bf16, its level range and the table's further limits (base a multiple of 32, 1 .. 4 input channels, 2 .. 10 classes; a decoder width
+    that is a multiple of 32 in 32 .. 512; three positive integer atrous rates)."""
+    spec = NATIVE[architecture]
+    lo, hi = spec['levels']
+    parts = ["norm='batch'", "act_dtype None / 'fp16' / 'bf16' (training)", "infer_dtype None / 'fp32' / 'fp16' / 'bf16' (prediction)",
+             f'{lo} .. {hi} levels']
+    if spec['shape']:
+        parts += ['base a multiple of 32', '1 .. 4 input channels', '2 .. 10 classes']
+    if spec['width']:
+        parts.append(f"{spec['width']} a multiple of 32 in 32 .. 512")
+    if spec['aspp']:
+        parts.append('three positive integer decoder_atrous_rates')
+    what = f"{architecture} supports {', '.join(parts[:-1])} and {parts[-1]}"
     if norm != 'batch':
-        raise NotImplementedError(f'U-Net++ with norm={norm!r} (GroupNorm): {what}')
+        raise NotImplementedError(f'{architecture} with norm={norm!r} (GroupNorm): {what}')
     if weight_dtype is not None:
-        raise NotImplementedError(f'U-Net++ with weight_dtype={weight_dtype!r} (fp8 weights): {what}')
+        raise NotImplementedError(f'{architecture} with weight_dtype={weight_dtype!r} (fp8 weights): {what}')
     if act_dtype is not None and _ACT.get(act_dtype) not in (torch.float16, torch.bfloat16):
-        raise NotImplementedError(f'U-Net++ with act_dtype={act_dtype!r} (the fp32 training form / split precision): {what}')
+        raise NotImplementedError(f'{architecture} with act_dtype={act_dtype!r} (the fp32 training form / split precision): {what}')
     if infer_dtype is not None and _ACT.get(infer_dtype) not in (torch.float32, torch.float16, torch.bfloat16):
-        raise NotImplementedError(f'U-Net++ with infer_dtype={infer_dtype!r} (split precision): {what}')
+        raise NotImplementedError(f'{architecture} with infer_dtype={infer_dtype!r} (split precision): {what}')
     if infer_policy is not None:
-        raise NotImplementedError(f'U-Net++ with infer_policy={infer_policy!r} (split-precision forms): {what}')
-    if not (2 <= levels <= 9):
-        raise NotImplementedError(f'U-Net++ with {levels} levels: {what}')
-
-
-def _check_linknet(levels, base, cin, ncls, act_dtype, weight_dtype, norm, infer_dtype, infer_policy):
-    """The combinations the native LinkNet supports: BatchNorm, 16-bit training (fp16 / bf16), prediction in fp32 (default) or fp16 /
-    bf16, 2 .. 6 levels, base a multiple of 32, 1 .. 4 input channels, 2 .. 10 classes."""
-    what = ("LinkNet supports norm='batch', act_dtype None / 'fp16' / 'bf16' (training), infer_dtype None / 'fp32' / 'fp16' / "
-            "'bf16' (prediction), 2 .. 6 levels, base a multiple of 32, 1 .. 4 input channels and 2 .. 10 classes")
-    if norm != 'batch':
-        raise NotImplementedError(f'LinkNet with norm={norm!r} (GroupNorm): {what}')
-    if weight_dtype is not None:
-        raise NotImplementedError(f'LinkNet with weight_dtype={weight_dtype!r} (fp8 weights): {what}')
-    if act_dtype is not None and _ACT.get(act_dtype) not in (torch.float16, torch.bfloat16):
-        raise NotImplementedError(f'LinkNet with act_dtype={act_dtype!r} (the fp32 training form / split precision): {what}')
-    if infer_dtype is not None and _ACT.get(infer_dtype) not in (torch.float32, torch.float16, torch.bfloat16):
-        raise NotImplementedError(f'LinkNet with infer_dtype={infer_dtype!r} (split precision): {what}')
-    if infer_policy is not None:
-        raise NotImplementedError(f'LinkNet with infer_policy={infer_policy!r} (split-precision forms): {what}')
-    if not (2 <= levels <= 6) or base % 32 or not (1 <= cin <= 4) or not (2 <= ncls <= 10):
-        raise NotImplementedError(f'LinkNet with {levels} levels, base {base}, {cin} input channels, {ncls} classes: {what}')
-
-
-def _check_deeplab(levels, base, cin, ncls, act_dtype, weight_dtype, norm, infer_dtype, infer_policy, decoder_channels, rates):
-    """The combinations the native DeepLabV3 supports: BatchNorm, 16-bit training (fp16 / bf16), prediction in fp32 (default) or fp16 /
-    bf16, 2 .. 6 levels, base a multiple of 32, 1 .. 4 input channels, 2 .. 10 classes, decoder_channels a multiple of 32 in 32 .. 512 and
-    three positive integer atrous rates."""
-    what = ("DeepLabV3 supports norm='batch', act_dtype None / 'fp16' / 'bf16' (training), infer_dtype None / 'fp32' / 'fp16' / "
-            "'bf16' (prediction), 2 .. 6 levels, base a multiple of 32, 1 .. 4 input channels, 2 .. 10 classes, decoder_channels a "
-            "multiple of 32 in 32 .. 512 and three positive integer decoder_atrous_rates")
-    if norm != 'batch':
-        raise NotImplementedError(f'DeepLabV3 with norm={norm!r} (GroupNorm): {what}')
-    if weight_dtype is not None:
-        raise NotImplementedError(f'DeepLabV3 with weight_dtype={weight_dtype!r} (fp8 weights): {what}')
-    if act_dtype is not None and _ACT.get(act_dtype) not in (torch.float16, torch.bfloat16):
-        raise NotImplementedError(f'DeepLabV3 with act_dtype={act_dtype!r} (the fp32 training form / split precision): {what}')
-    if infer_dtype is not None and _ACT.get(infer_dtype) not in (torch.float32, torch.float16, torch.bfloat16):
-        raise NotImplementedError(f'DeepLabV3 with infer_dtype={infer_dtype!r} (split precision): {what}')
-    if infer_policy is not None:
-        raise NotImplementedError(f'DeepLabV3 with infer_policy={infer_policy!r} (split-precision forms): {what}')
-    if not (2 <= levels <= 6) or base % 32 or not (1 <= cin <= 4) or not (2 <= ncls <= 10):
-        raise NotImplementedError(f'DeepLabV3 with {levels} levels, base {base}, {cin} input channels, {ncls} classes: {what}')
-    if not isinstance(decoder_channels, int) or decoder_channels % 32 or not (32 <= decoder_channels <= 512):
-        raise NotImplementedError(f'DeepLabV3 with decoder_channels={decoder_channels!r}: {what}')
-    try:
-        ok = len(rates) == 3 and all(isinstance(r, int) and not isinstance(r, bool) and r > 0 for r in rates)
-    except TypeError:
-        ok = False
-    if not ok:
-        raise NotImplementedError(f'DeepLabV3 with decoder_atrous_rates={rates!r}: {what}')
-
-
-def _check_segformer(levels, base, cin, ncls, act_dtype, weight_dtype, norm, infer_dtype, infer_policy, channels):
-    """The combinations the native Segformer supports: BatchNorm, 16-bit training (fp16 / bf16), prediction in fp32 (default) or fp16 /
-    bf16, 3 .. 6 levels, base a multiple of 32, 1 .. 4 input channels, 2 .. 10 classes, decoder_segmentation_channels a multiple of 32 in
-    32 .. 512."""
-    what = ("Segformer supports norm='batch', act_dtype None / 'fp16' / 'bf16' (training), infer_dtype None / 'fp32' / 'fp16' / "
-            "'bf16' (prediction), 3 .. 6 levels, base a multiple of 32, 1 .. 4 input channels, 2 .. 10 classes and "
-            "decoder_segmentation_channels a multiple of 32 in 32 .. 512")
-    if norm != 'batch':
-        raise NotImplementedError(f'Segformer with norm={norm!r} (GroupNorm): {what}')
-    if weight_dtype is not None:
-        raise NotImplementedError(f'Segformer with weight_dtype={weight_dtype!r} (fp8 weights): {what}')
-    if act_dtype is not None and _ACT.get(act_dtype) not in (torch.float16, torch.bfloat16):
-        raise NotImplementedError(f'Segformer with act_dtype={act_dtype!r} (the fp32 training form / split precision): {what}')
-    if infer_dtype is not None and _ACT.get(infer_dtype) not in (torch.float32, torch.float16, torch.bfloat16):
-        raise NotImplementedError(f'Segformer with infer_dtype={infer_dtype!r} (split precision): {what}')
-    if infer_policy is not None:
-        raise NotImplementedError(f'Segformer with infer_policy={infer_policy!r} (split-precision forms): {what}')
-    if not (3 <= levels <= 6) or base % 32 or not (1 <= cin <= 4) or not (2 <= ncls <= 10):
-        raise NotImplementedError(f'Segformer with {levels} levels, base {base}, {cin} input channels, {ncls} classes: {what}')
-    if not isinstance(channels, int) or isinstance(channels, bool) or channels % 32 or not (32 <= channels <= 512):
-        raise NotImplementedError(f'Segformer with decoder_segmentation_channels={channels!r}: {what}')
+        raise NotImplementedError(f'{architecture} with infer_policy={infer_policy!r} (split-precision forms): {what}')
+    if not spec['shape'] and not (lo <= levels <= hi):
+        raise NotImplementedError(f'{architecture} with {levels} levels: {what}')
+    if spec['shape'] and (not (lo <= levels <= hi) or base % 32 or not (1 <= cin <= 4) or not (2 <= ncls <= 10)):
+        raise NotImplementedError(f'{architecture} with {levels} levels, base {base}, {cin} input channels, {ncls} classes: {what}')
+    width = decoder.get(spec['width'])
+    if spec['width'] and (not isinstance(width, int) or isinstance(width, bool) or width % 32 or not (32 <= width <= 512)):
+        raise NotImplementedError(f"{architecture} with {spec['width']}={width!r}: {what}")
+    if spec['aspp']:
+        rates = decoder['decoder_atrous_rates']
+        try:
+            ok = len(rates) == 3 and all(isinstance(r, int) and not isinstance(r, bool) and r > 0 for r in rates)
+        except TypeError:
+            ok = False
+        if not ok:
+            raise NotImplementedError(f'{architecture} with decoder_atrous_rates={rates!r}: {what}')
+        if not (0.0 <= float(decoder['decoder_aspp_dropout']) < 1.0):
+            raise ValueError(f"decoder_aspp_dropout must be in [0, 1), got {decoder['decoder_aspp_dropout']!r}")
 
 
 def _is_buffer(name):
@@ -248,18 +237,10 @@ class UNet(nn.Module):
         if architecture not in ARCHITECTURES:
             raise NotImplementedError(f"architecture {architecture!r}: only 'U-Net', 'U-Net++', 'LinkNet', 'DeepLabV3' and 'Segformer' have a native MI355X "
                                       f"implementation (the reference builds the others through smp, unet.py:33-54)")
-        if architecture == NESTED:
-            _check_nested(levels, act_dtype, weight_dtype, norm, infer_dtype, infer_policy)
-        if architecture == LINKNET:
-            _check_linknet(levels, base, num_channels, num_classes, act_dtype, weight_dtype, norm, infer_dtype, infer_policy)
-        if architecture == DEEPLAB:
-            _check_deeplab(levels, base, num_channels, num_classes, act_dtype, weight_dtype, norm, infer_dtype, infer_policy,
-                           decoder_channels, decoder_atrous_rates)
-            if not (0.0 <= float(decoder_aspp_dropout) < 1.0):
-                raise ValueError(f'decoder_aspp_dropout must be in [0, 1), got {decoder_aspp_dropout!r}')
-        if architecture == SEGFORMER:
-            _check_segformer(levels, base, num_channels, num_classes, act_dtype, weight_dtype, norm, infer_dtype, infer_policy,
-                             decoder_segmentation_channels)
+        if architecture in NATIVE:
+            _check_native(architecture, levels, base, num_channels, num_classes, act_dtype, weight_dtype, norm, infer_dtype, infer_policy,
+                          decoder_channels=decoder_channels, decoder_atrous_rates=decoder_atrous_rates,
+                          decoder_aspp_dropout=decoder_aspp_dropout, decoder_segmentation_channels=decoder_segmentation_channels)
         if pretrained:
             warnings.warn('pretrained=True ignored: the native U-Net encoder is trained from scratch')
         self.hparams = dict(lr=lr, num_channels=num_channels, num_classes=num_classes,
@@ -290,7 +271,7 @@ class UNet(nn.Module):
         self.act_dtype = torch.float16 if act_dtype is None else _ACT[act_dtype]
         if infer_dtype is not None:
             self.infer_dtype = _ACT[infer_dtype]
-        elif architecture in (NESTED, LINKNET, DEEPLAB, SEGFORMER):
+        elif architecture in NATIVE:
             self.infer_dtype = torch.float32   # these nets predict in the fp32 form (within 1e-3 of the CPU fp32 logits)
         elif act_dtype is None and weight_dtype is None:
             self.infer_dtype = X2              # (GroupNorm networks too: engine_auto runs them in the full fp16x2 form)
@@ -378,40 +359,8 @@ class UNet(nn.Module):
             raise RuntimeError('the native U-Net runs on the GPU only: move the module with .to("cuda") '
                                '(there is no CPU fallback)')
         eng = self._engines.get(dev)
-        if eng is None and self.architecture == SEGFORMER:
-            from .engine_segformer import SegformerEngine, SegformerEngineF32
-            args = (self.dim, self.levels, self.base, self.num_channels, self.num_classes)
-            kw = dict(decoder_channels=self.decoder_segmentation_channels, device=dev)
-            if self.infer_dtype == torch.float32:
-                eng = SegformerEngineF32(*args, **kw)
-            else:
-                eng = SegformerEngine(*args, act_dtype=self.infer_dtype, **kw)
-            self._engines = {dev: eng}
-            self._packed_sig = None
-        if eng is None and self.architecture == DEEPLAB:
-            from .engine_deeplab import DeepLabV3Engine, DeepLabV3EngineF32
-            args = (self.dim, self.levels, self.base, self.num_channels, self.num_classes)
-            kw = dict(decoder_channels=self.decoder_channels, rates=self.decoder_atrous_rates, device=dev)
-            if self.infer_dtype == torch.float32:
-                eng = DeepLabV3EngineF32(*args, **kw)
-            else:
-                eng = DeepLabV3Engine(*args, act_dtype=self.infer_dtype, **kw)
-            self._engines = {dev: eng}
-            self._packed_sig = None
-        if eng is None and self.architecture == LINKNET:
-            from .engine_linknet import LinkNetEngine, LinkNetEngineF32
-            if self.infer_dtype == torch.float32:
-                eng = LinkNetEngineF32(self.dim, self.levels, self.base, self.num_channels, self.num_classes, dev)
-            else:
-                eng = LinkNetEngine(self.dim, self.levels, self.base, self.num_channels, self.num_classes, self.infer_dtype, dev)
-            self._engines = {dev: eng}
-            self._packed_sig = None
-        if eng is None and self.architecture == NESTED:
-            from .engine_nested import NestedEngine, NestedEngineF32
-            if self.infer_dtype == torch.float32:
-                eng = NestedEngineF32(self.dim, self.levels, self.base, self.num_channels, self.num_classes, dev)
-            else:
-                eng = NestedEngine(self.dim, self.levels, self.base, self.num_channels, self.num_classes, self.infer_dtype, dev)
+        if eng is None and self.architecture in NATIVE:
+            eng = native_engine(self, self.infer_dtype, dev)
             self._engines = {dev: eng}
             self._packed_sig = None
         if eng is None:
