@@ -34,8 +34,31 @@ template <typename T> struct Vec8;
 template <> struct Vec8<f16> { typedef f16x8 type; };
 template <> struct Vec8<bf16> { typedef bf16x8 type; };
 
+template <typename T> using V8T = typename Vec8<T>::type;
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+template <typename T> struct Vec4;
+template <> struct Vec4<f16> { typedef f16x4 type; };
+template <> struct Vec4<bf16> { typedef bf16x4 type; };
+
 template <typename T> __device__ __forceinline__ float to_f32(T v) { return (float)v; }
 template <typename T> __device__ __forceinline__ T from_f32(float v) { return (T)v; }
+
+// relu(scale * x + shift) rounded to T: the bits iunet_bn_relu_fwd stores (channel c; 8 lanes: channels c0 .. c0 + 7)
+template <typename T>
+__device__ __forceinline__ T bn_relu1(T v, const float* sc, const float* sh, int c) {
+  return from_f32<T>(fmaxf(fmaf(sc[c], to_f32<T>(v), sh[c]), 0.f));
+}
+template <typename T>
+__device__ __forceinline__ V8T<T> bn_relu8(V8T<T> v, const float* sc, const float* sh, int c0) {
+  V8T<T> o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = bn_relu1<T>(v[j], sc, sh, c0 + j);
+  return o;
+}
+
+// Eval-mode BatchNorm folded into an operator: row c is scaled by bn_fold_scale, the bias is bn_fold_bias of that scale
+__device__ __forceinline__ float bn_fold_scale(const float* gamma, const float* var, float eps, int c) { return gamma[c] / sqrtf(var[c] + eps); }
+__device__ __forceinline__ float bn_fold_bias(const float* beta, const float* mean, float scale, int c) { return beta[c] - mean[c] * scale; }
 
 // fp16x2 split precision: v ~ hi + lo with hi = T(v), lo = T(v - hi) -- for T = f16 22 significant bits (the lo word is subnormal, i.e.
 // exact to 2^-24, once |v| < 2^-2: callers keep activations scaled up by a power of two).  Finite by construction: |v| is clamped

@@ -18,21 +18,15 @@
 // branch's adjoint dmean[n][c] / vox to the ASPP data gradient: one fp32 sum, one rounding.
 //
 // All reductions are fixed-order (per-workgroup slabs, then ordered sums): no float atomics, two identical calls are bit-identical.
+//
+// The GEMMs are gather_gemm.h's skeletons under the DlFwdGather / DlWgGather policies (segformer.hip calls the forward for M^T dZ).
 #include "common.h"
+#include "gather_gemm.h"
 #include "loss_terms.h"
 #include "../../include/iunet.h"
 
 namespace {
 
-template <typename T> using V8T = typename Vec8<T>::type;
-typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-template <typename T> struct Vec4;
-template <> struct Vec4<f16> { typedef f16x4_t type; };
-template <> struct Vec4<bf16> { typedef bf16x4_t type; };
-
-constexpr int DL_WAVES = 4;          // waves per workgroup of the forward GEMM
-constexpr int DL_COG = 64;           // output channels per workgroup (4 row tiles of 16 per wave)
 constexpr int DL_MAXT = 96;          // taps per launch (the 3-D ASPP data gradient: 1 + 3 x 27)
 constexpr int DL_MAXBR = 4;          // branches per launch
 
@@ -64,230 +58,61 @@ bool dl_add_taps(DlTaps& t, int nd, int rate, int D, int H, int W, int cbase, in
   return true;
 }
 
-// relu(scale * x + shift) rounded to T: the bits iunet_bn_relu_fwd stores
-template <typename T>
-__device__ __forceinline__ V8T<T> dl_act(V8T<T> v, const float* sc, const float* sh, int c0) {
-  V8T<T> o;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = from_f32<T>(fmaxf(fmaf(sc[c0 + j], to_f32<T>(v[j]), sh[c0 + j]), 0.f));
-  return o;
+// Source voxel of tap t for the column (d, h, w), -1: outside (zero)
+__device__ __forceinline__ long long dl_tap_src(const DlTaps& t, int tap, int d, int h, int w, int D, int H, int W) {
+  const int sd = d + t.od[tap], sh = h + t.oh[tap], sw = w + t.ow[tap];
+  if (sd < 0 || sd >= D || sh < 0 || sh >= H || sw < 0 || sw >= W) return -1;
+  return ((long long)sd * H + sh) * W + sw;
 }
 
-struct DlConv {
-  const void* x; long long x_ss;
-  void* y; long long y_ss;
-  const void* wpk; int Kw;            // operator [Cout][Kw]
-  const float* in_scale; const float* in_shift;
-  const float* bias;
-  const float* psb; float psb_scale;  // per-sample bias [N][Cout] (x psb_scale) or null
-  float* stats;                       // [gridDim.x][Cout][2] or null
-  int N, D, H, W;
-  int Cin, Cout, K;                   // K = taps * Cin (the kept taps)
-  long long cols;
-  int epi;                            // 0 raw (+ stats), 1 + bias + ReLU
+// gather_gemm.h forward policy: one class, input and output on the column grid, operator [Cout][lda = Kw] without padding, a per-sample
+// bias [N][Cout] (x psb_scale) or null added to the accumulator
+struct DlFwdGather {
+  int lda;
+  const float* psb; float psb_scale;
   DlTaps taps;
+  static constexpr bool A_PADDED = false;
+  static __device__ __forceinline__ long long in_vox(int D, int H, int W) { return (long long)D * H * W; }
+  static __device__ __forceinline__ long long out_vox(int D, int H, int W) { return (long long)D * H * W; }
+  __device__ __forceinline__ long long a_row0(int, int co0, int) const { return co0; }
+  __device__ __forceinline__ int a_col(int tap, int c, int) const { return taps.col[tap] + c; }
+  __device__ __forceinline__ long long src(int tap, int, int d, int h, int w, int D, int H, int W, int& cb) const {
+    cb = taps.cb[tap];
+    return dl_tap_src(taps, tap, d, h, w, D, H, W);
+  }
+  static __device__ __forceinline__ long long dst(int, int, int, int, long long r, int, int, int) { return r; }
+  __device__ __forceinline__ float pre(float v, int n, int co, int Cout) const {
+    return psb != nullptr ? v + psb[(long long)n * Cout + co] * psb_scale : v;
+  }
+  template <typename T>
+  __device__ __forceinline__ void extra(float (&)[4], int, int, long long, long long) const {}
+  __device__ __forceinline__ float post(float v, float) const { return v; }
+  __device__ __forceinline__ float post32(float v, int, int, long long, long long) const { return v; }
 };
 
-// grid (blocks, Cout / 64 rounded up); 256 threads; each wave walks column tiles of 16 voxels
-template <typename T, int ND, bool ACT>
-__global__ __launch_bounds__(256) void dl_conv_kernel(DlConv p) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int co0 = blockIdx.y * DL_COG;
-  const int ntile = min(4, (p.Cout - co0) / 16);
-  const T* x = (const T*)p.x;
-  const T* wpk = (const T*)p.wpk + (long long)co0 * p.Kw;
-  const long long vgrid = (long long)p.D * p.H * p.W;
-  const long long ntiles = (p.cols + 15) / 16;
-  const long long per_block = (ntiles + gridDim.x - 1) / gridDim.x;
-  const long long t0 = (long long)blockIdx.x * per_block, t1 = min(ntiles, t0 + per_block);
-  float ssum[4][4], ssq[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { ssum[a][r] = 0.f; ssq[a][r] = 0.f; }
-  const int q = lane >> 4, l15 = lane & 15;
-  for (long long tile = t0 + wave; tile < t1; tile += DL_WAVES) {
-    const long long col = tile * 16 + l15;
-    const bool ok = col < p.cols;
-    const long long cc = ok ? col : 0;
-    const int n = (int)(cc / vgrid);
-    const long long r = cc - (long long)n * vgrid;
-    const int w = (int)(r % p.W), h = (int)((r / p.W) % p.H), d = (int)(r / ((long long)p.W * p.H));
-    const T* xs = x + (long long)n * p.x_ss;
-    f32x4 acc[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < p.K; k0 += 32) {
-      const int kg = k0 + q * 8;
-      const bool kok = kg < p.K;
-      const int tap = kok ? kg / p.Cin : 0, c0 = kg - tap * p.Cin;
-      const int acol = kok ? p.taps.col[tap] + c0 : 0;
-      V8T<T> b;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) b[j] = from_f32<T>(0.f);
-      if (ok && kok) {
-        const int sd = d + p.taps.od[tap], sh = h + p.taps.oh[tap], sw = w + p.taps.ow[tap];
-        if (sd >= 0 && sd < p.D && sh >= 0 && sh < p.H && sw >= 0 && sw < p.W) {
-          const int ch = p.taps.cb[tap] + c0;
-          b = *(const V8T<T>*)(xs + ((long long)(ch >> 3) * vgrid + ((long long)sd * p.H + sh) * p.W + sw) * 8);
-          if constexpr (ACT) b = dl_act<T>(b, p.in_scale, p.in_shift, ch);
-        }
-      }
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        if (a < ntile) {
-          V8T<T> av;
-          if (kok) {
-            av = *(const V8T<T>*)(wpk + (long long)(a * 16 + l15) * p.Kw + acol);
-          } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) av[j] = from_f32<T>(0.f);
-          }
-          acc[a] = mfma16<T>(av, b, acc[a]);
-        }
-      }
-    }
-    if (!ok) continue;
-    T* ys = (T*)p.y + (long long)n * p.y_ss;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      if (a >= ntile) continue;
-      const int co = co0 + a * 16 + q * 4;
-      typename Vec4<T>::type o;
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        float v = acc[a][rr];
-        if (p.psb != nullptr) v += p.psb[(long long)n * p.Cout + co + rr] * p.psb_scale;
-        if (p.epi == 0) {
-          o[rr] = from_f32<T>(v);
-          ssum[a][rr] += v;
-          ssq[a][rr] += v * v;
-        } else {
-          o[rr] = from_f32<T>(fmaxf(v + p.bias[co + rr], 0.f));
-        }
-      }
-      *(typename Vec4<T>::type*)(ys + ((long long)(co >> 3) * vgrid + r) * 8 + (co & 7)) = o;
-    }
-  }
-  if (p.stats == nullptr) return;
-  // BatchNorm partial sums: the 16 columns of a lane group, then the 4 waves in a fixed order -> one row per workgroup
-  __shared__ float red[DL_WAVES][DL_COG][2];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      float s = ssum[a][rr], s2 = ssq[a][rr];
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) { s += __shfl_xor(s, o); s2 += __shfl_xor(s2, o); }
-      if (l15 == 0) { red[wave][a * 16 + q * 4 + rr][0] = s; red[wave][a * 16 + q * 4 + rr][1] = s2; }
-    }
-  __syncthreads();
-  if (threadIdx.x < 2 * ntile * 16) {
-    const int c = threadIdx.x >> 1, which = threadIdx.x & 1;
-    const float v = (red[0][c][which] + red[1][c][which]) + (red[2][c][which] + red[3][c][which]);
-    p.stats[((long long)blockIdx.x * p.Cout + co0 + c) * 2 + which] = v;
-  }
-}
+int dl_fwd_blocks(int N, int D, int H, int W, int Cout) { return gg_fwd_blocks((long long)N * D * H * W, (Cout + GG_COG - 1) / GG_COG); }
 
-int dl_fwd_blocks(int N, int D, int H, int W, int Cout) {
-  const long long cols = (long long)N * D * H * W;
-  const long long tiles = (cols + 15) / 16;
-  const int ncg = (Cout + DL_COG - 1) / DL_COG;
-  long long b = (tiles + 4 * DL_WAVES - 1) / (4 * DL_WAVES);
-  const long long cap = (2048 + ncg - 1) / ncg;
-  if (b > cap) b = cap;
-  if (b > 1024) b = 1024;
-  return (int)(b < 1 ? 1 : b);
-}
-
-// ---- weight gradient, staged through LDS: slab[split][Cout][K] = sum over the split's columns of dy[col][co] * act(x)[tap-shifted][k'].
-// A workgroup owns a 64 (co) x 64 (k') tile; per chunk of 32 columns its 256 threads load dy (8 channels of one column each, 16 bytes)
-// and the gathered x (8 k' of one column each), write both into LDS transposed to [row][column], and each wave runs the 16 x 64 x 32
-// product with both operands read from LDS as 16-byte rows.
-constexpr int DW_LD = 40;            // LDS row stride (elements) of the [64][32] operand images
-struct DlWg {
+// gather_gemm.h weight-gradient policy: B[k' = (tap, ci)] = act(x)[cb_tap + ci] at the tap-shifted voxel
+struct DlWgGather {
   const void* x; long long x_ss;
-  const void* dy; long long dy_ss;
   const float* in_scale; const float* in_shift;
-  float* slab;
-  int N, D, H, W;
-  int Cin, Cout, K;                   // K = taps * Cin
-  long long cols;
-  long long chunks_per_split;
+  int Cin;
   DlTaps taps;
+  struct Lane { int tap, ch; };
+  __device__ __forceinline__ Lane lane(int k_l, bool k_ok) const {      // one tap: Cin is a multiple of 8
+    const int tap = k_ok ? k_l / Cin : 0;
+    return Lane{tap, taps.cb[tap] + k_l - tap * Cin};
+  }
+  template <typename T, bool ACT>
+  __device__ __forceinline__ V8T<T> column(const Lane& l, int n, long long r, int D, int H, int W) const {
+    const int w = (int)(r % W), h = (int)((r / W) % H), d = (int)(r / ((long long)W * H));
+    const long long sv = dl_tap_src(taps, l.tap, d, h, w, D, H, W);
+    if (sv < 0) return gg_zero8<T>();
+    const V8T<T> v = *(const V8T<T>*)((const T*)x + (long long)n * x_ss + ((long long)(l.ch >> 3) * ((long long)D * H * W) + sv) * 8);
+    return ACT ? bn_relu8<T>(v, in_scale, in_shift, l.ch) : v;
+  }
 };
 
-template <typename T, int ND, bool ACT>
-__global__ __launch_bounds__(256) void dl_wgrad_kernel(DlWg p) {
-  __shared__ __attribute__((aligned(16))) T sA[64 * DW_LD];
-  __shared__ __attribute__((aligned(16))) T sB[64 * DW_LD];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, l15 = lane & 15;
-  const int co0 = blockIdx.y * 64, kb = blockIdx.z * 64;
-  const long long vgrid = (long long)p.D * p.H * p.W;
-  const long long nchunks = (p.cols + 31) / 32;
-  const long long c_lo = (long long)blockIdx.x * p.chunks_per_split, c_hi = min(nchunks, c_lo + p.chunks_per_split);
-  const T* x = (const T*)p.x;
-  const T* dy = (const T*)p.dy;
-  // this thread's loads: group g = 8 rows, column j
-  const int g = threadIdx.x >> 5, jc = threadIdx.x & 31;
-  const int co_l = co0 + g * 8;                       // dy rows co_l .. +8
-  const int k_l = kb + g * 8;                         // x rows k_l .. +8 (one tap: Cin is a multiple of 8)
-  const bool co_ok = co_l < p.Cout, k_ok = k_l < p.K;
-  const int tap = k_ok ? k_l / p.Cin : 0, cin0 = k_l - tap * p.Cin, ch = p.taps.cb[tap] + cin0;
-  f32x4 acc[4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (long long ck = c_lo; ck < c_hi; ++ck) {
-    const long long col = ck * 32 + jc;
-    V8T<T> va, vb;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { va[j] = from_f32<T>(0.f); vb[j] = from_f32<T>(0.f); }
-    if (col < p.cols) {
-      const int n = (int)(col / vgrid);
-      const long long r = col - (long long)n * vgrid;
-      if (co_ok) va = *(const V8T<T>*)(dy + (long long)n * p.dy_ss + ((long long)(co_l >> 3) * vgrid + r) * 8);
-      if (k_ok) {
-        const int w = (int)(r % p.W), h = (int)((r / p.W) % p.H), d = (int)(r / ((long long)p.W * p.H));
-        const int sd = d + p.taps.od[tap], sh = h + p.taps.oh[tap], sw = w + p.taps.ow[tap];
-        if (sd >= 0 && sd < p.D && sh >= 0 && sh < p.H && sw >= 0 && sw < p.W) {
-          vb = *(const V8T<T>*)(x + (long long)n * p.x_ss + ((long long)(ch >> 3) * vgrid + ((long long)sd * p.H + sh) * p.W + sw) * 8);
-          if constexpr (ACT) vb = dl_act<T>(vb, p.in_scale, p.in_shift, ch);
-        }
-      }
-    }
-    __syncthreads();                                   // the previous chunk's operands are consumed
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { sA[(g * 8 + j) * DW_LD + jc] = va[j]; sB[(g * 8 + j) * DW_LD + jc] = vb[j]; }
-    __syncthreads();
-    const V8T<T> a = *(const V8T<T>*)(sA + (wave * 16 + l15) * DW_LD + q * 8);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const V8T<T> b = *(const V8T<T>*)(sB + (t * 16 + l15) * DW_LD + q * 8);
-      acc[t] = mfma16<T>(a, b, acc[t]);
-    }
-  }
-  // D[row = co][col = k']: lane holds rows co0 + wave*16 + q*4 + rr at column kb + t*16 + l15
-  float* out = p.slab + (long long)blockIdx.x * p.Cout * p.K;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int kk = kb + t * 16 + l15;
-    if (kk >= p.K) continue;
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      const int co = co0 + wave * 16 + q * 4 + rr;
-      if (co < p.Cout) out[(long long)co * p.K + kk] = acc[t][rr];
-    }
-  }
-}
-
-int dl_wgrad_splits(long long cols, long long per_split_floats) {
-  const long long nchunks = (cols + 31) / 32;
-  long long s = (nchunks + 15) / 16;                  // at least 16 chunks (512 columns) per split
-  if (s > 64) s = 64;
-  if (s < 1) s = 1;
-  while (s > 1 && s * per_split_floats > (8ll << 20)) s >>= 1;
-  return (int)s;
-}
 
 // dW[co][ci_off + ci][kidx] = alpha * sum over splits (fixed order) of the kept taps' columns; a pruned tap's gradient is zero
 __global__ __launch_bounds__(256) void dl_wgrad_reduce_kernel(const float* __restrict__ slab, int splits, int Cin, int Cout, int K, int kvol,
@@ -321,70 +146,11 @@ __global__ __launch_bounds__(256) void dl_pack_kernel(const float* __restrict__ 
   const int kidx = (int)(i % kvol), ci = (int)((i / kvol) % Cin), co = (int)(i / ((long long)kvol * Cin));
   float v = w[((long long)co * Cin_tot + ci_off + ci) * kvol + kidx];
   if (mode == 0) {
-    if (gamma != nullptr) v *= gamma[co] / sqrtf(var[co] + eps);
+    if (gamma != nullptr) v *= bn_fold_scale(gamma, var, eps, co);
     dst[(long long)co * ld + k_off + (long long)kidx * Cin + ci] = (OT)v;
-    if (bias_out != nullptr && gamma != nullptr && ci == 0 && kidx == 0) bias_out[co] = beta[co] - mean[co] * (gamma[co] / sqrtf(var[co] + eps));
+    if (bias_out != nullptr && gamma != nullptr && ci == 0 && kidx == 0) bias_out[co] = bn_fold_bias(beta, mean, bn_fold_scale(gamma, var, eps, co), co);
   } else {
     dst[(long long)ci * ld + k_off + (long long)(kvol - 1 - kidx) * Cout + co] = (OT)v;
-  }
-}
-
-// ---- fp32 form: planar fp32 [N][C][vox] (sample strides in elements), v_mfma_f32_16x16x4_f32: A[row l&15][k l>>4], B[k l>>4][col l&15]
-struct DlF32 {
-  const float* x; long long x_ss;
-  float* y; long long y_ss;
-  const float* wpk; int Kw;
-  const float* bias; const float* psb;
-  int D, H, W, Cin, Cout, K;
-  long long cols;
-  DlTaps taps;
-};
-
-__global__ __launch_bounds__(256) void dl_f32_kernel(DlF32 p) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, l15 = lane & 15;
-  const int co0 = blockIdx.y * DL_COG;
-  const int ntile = min(4, (p.Cout - co0) / 16);
-  const float* wpk = p.wpk + (long long)co0 * p.Kw;
-  const long long vin = (long long)p.D * p.H * p.W;
-  const long long tile = (long long)blockIdx.x * DL_WAVES + wave;
-  const long long col = tile * 16 + l15;
-  const bool ok = col < p.cols;
-  const long long cc = ok ? col : 0;
-  const int n = (int)(cc / vin);
-  const long long r = cc - (long long)n * vin;
-  const int w = (int)(r % p.W), h = (int)((r / p.W) % p.H), d = (int)(r / ((long long)p.W * p.H));
-  const float* xs = p.x + (long long)n * p.x_ss;
-  f32x4 acc[4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
-  int tap = 0, c = q;                        // k = k0 + q, walked incrementally (k0 += 4)
-  while (c >= p.Cin) { c -= p.Cin; ++tap; }
-  for (int k0 = 0; k0 < p.K; k0 += 4) {
-    float b = 0.f;
-    const bool kok = k0 + q < p.K;
-    if (ok && kok) {
-      const int sd = d + p.taps.od[tap], sh = h + p.taps.oh[tap], sw = w + p.taps.ow[tap];
-      if (sd >= 0 && sd < p.D && sh >= 0 && sh < p.H && sw >= 0 && sw < p.W)
-        b = xs[(long long)(p.taps.cb[tap] + c) * vin + ((long long)sd * p.H + sh) * p.W + sw];
-    }
-    const int acol = kok ? p.taps.col[tap] + c : 0;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-      if (a < ntile) acc[a] = __builtin_amdgcn_mfma_f32_16x16x4f32(kok ? wpk[(long long)(a * 16 + l15) * p.Kw + acol] : 0.f, b, acc[a], 0, 0, 0);
-    c += 4;
-    while (c >= p.Cin) { c -= p.Cin; ++tap; }
-  }
-  if (!ok) return;
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    if (a >= ntile) continue;
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      const int co = co0 + a * 16 + q * 4 + rr;
-      float v = acc[a][rr];
-      if (p.psb != nullptr) v += p.psb[(long long)n * p.Cout + co];
-      p.y[(long long)n * p.y_ss + (long long)co * vin + r] = fmaxf(v + p.bias[co], 0.f);
-    }
   }
 }
 
@@ -443,7 +209,7 @@ __global__ __launch_bounds__(256) void dl_pool_bp_kernel(const float* __restrict
   const int j = i % C;
   float sc, sh;
   if (scale != nullptr) { sc = scale[j]; sh = shift[j]; }
-  else { sc = gamma[j] / sqrtf(rvar[j] + eps); sh = beta[j] - rmean[j] * sc; }
+  else { sc = bn_fold_scale(gamma, rvar, eps, j); sh = bn_fold_bias(beta, rmean, sc, j); }
   bp[i] = fmaxf(fmaf(sc, ypool[i], sh), 0.f);
 }
 
@@ -454,7 +220,7 @@ __global__ __launch_bounds__(256) void dl_pool_psb_kernel(const float* __restric
   const int n = i / C, c = i - n * C;
   float s = 0.f;
   for (int j = 0; j < C; ++j) s = fmaf(wproj[(long long)c * 5 * C + 4 * C + j], bp[(long long)n * C + j], s);
-  if (pgamma != nullptr) s *= pgamma[c] / sqrtf(pvar[c] + eps);
+  if (pgamma != nullptr) s *= bn_fold_scale(pgamma, pvar, eps, c);
   psb[i] = s;
 }
 
@@ -791,10 +557,6 @@ int dl_build(DlTaps& t, int nd, int nbr, const int* rates, const int* cbase, con
 
 }  // namespace
 
-// (train_pointwise.hip: the loss / metrics / coefficient pass of the fused head + loss kernels)
-int iunet_loss_finalize_launch(const float* slab, int nparts, int ncls, int kind, int has_weight, double nvox_total, float* out4,
-                               float* coef, hipStream_t stream);
-
 extern "C" {
 
 int iunet_dl_num_taps(int nd, int rate, int D, int H, int W) {
@@ -845,25 +607,22 @@ int iunet_dl_conv_fwd(int dtype, int nd, const void* x, long long x_ss, void* y,
   IUNET_REQUIRE(epi == 0 || bias, "dl_conv_fwd: epi 1 needs a bias");
   IUNET_REQUIRE(epi == 0 || !stats, "dl_conv_fwd: statistics are taken of the raw output (epi 0) only");
   IUNET_REQUIRE(!in_scale == !in_shift, "dl_conv_fwd: the input activation needs both scale and shift");
-  DlConv p;
-  const int rb = dl_build(p.taps, nd, nbr, rates, cbase, colbase, D, H, W, Cin);
+  GgFwd p;
+  DlFwdGather g;
+  const int rb = dl_build(g.taps, nd, nbr, rates, cbase, colbase, D, H, W, Cin);
   if (rb != IUNET_OK) return rb;
-  for (int t = 0; t < p.taps.n; ++t)
-    IUNET_REQUIRE(p.taps.col[t] + Cin <= Kw, "dl_conv_fwd: tap %d reads operator columns past the row length %d", t, Kw);
+  for (int t = 0; t < g.taps.n; ++t)
+    IUNET_REQUIRE(g.taps.col[t] + Cin <= Kw, "dl_conv_fwd: tap %d reads operator columns past the row length %d", t, Kw);
   IUNET_REQUIRE(Kw % 8 == 0, "dl_conv_fwd: the operator row length must be a multiple of 8, got %d", Kw);
-  p.x = x; p.x_ss = x_ss; p.y = y; p.y_ss = y_ss; p.wpk = wpk; p.Kw = Kw;
-  p.in_scale = (const float*)in_scale; p.in_shift = (const float*)in_shift; p.bias = (const float*)bias;
-  p.psb = (const float*)psb; p.psb_scale = psb_scale; p.stats = (float*)stats;
-  p.N = N; p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.K = p.taps.n * Cin;
+  p.x = x; p.x_ss = x_ss; p.y = y; p.y_ss = y_ss; p.wpk = wpk;
+  p.in_scale = (const float*)in_scale; p.in_shift = (const float*)in_shift; p.bias = (const float*)bias; p.stats = (float*)stats;
+  p.N = N; p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.K = g.taps.n * Cin;
   p.cols = (long long)N * D * H * W; p.epi = epi;
-  const dim3 grid(dl_fwd_blocks(N, D, H, W, Cout), (Cout + DL_COG - 1) / DL_COG);
-  const bool act = in_scale != nullptr;
-#define DLF(TT, NDV, AV) hipLaunchKernelGGL((dl_conv_kernel<TT, NDV, AV>), grid, dim3(256), 0, (hipStream_t)stream, p)
-#define DLF_A(TT, NDV) do { if (act) DLF(TT, NDV, true); else DLF(TT, NDV, false); } while (0)
-  if (dtype == 0) { if (nd == 3) DLF_A(f16, 3); else DLF_A(f16, 2); }
-  else { if (nd == 3) DLF_A(bf16, 3); else DLF_A(bf16, 2); }
-#undef DLF_A
-#undef DLF
+  g.lda = Kw; g.psb = (const float*)psb; g.psb_scale = psb_scale;
+  const dim3 grid(dl_fwd_blocks(N, D, H, W, Cout), (Cout + GG_COG - 1) / GG_COG);
+  gg_dispatch(dtype, nd, in_scale != nullptr, [&](auto t, auto, auto act) {
+    hipLaunchKernelGGL((gg_fwd_kernel<decltype(t), act.value, DlFwdGather>), grid, dim3(256), 0, (hipStream_t)stream, p, g);
+  });
   IUNET_CHECK_HIP(hipGetLastError());
   return IUNET_OK;
 }
@@ -872,7 +631,7 @@ long long iunet_dl_wgrad_slab_floats(int nd, int rate, int N, int D, int H, int 
   const int nt = iunet_dl_num_taps(nd, rate, D, H, W);
   if (nt <= 0 || N <= 0 || Cin <= 0 || Cout <= 0) return -1;
   const long long per = (long long)Cout * nt * Cin;
-  return dl_wgrad_splits((long long)N * D * H * W, per) * per;
+  return gg_wgrad_splits((long long)N * D * H * W, per) * per;
 }
 
 int iunet_dl_wgrad(int dtype, int nd, int rate, const void* x, long long x_ss, int cbase, const void* dy, long long dy_ss, const void* x_scale,
@@ -886,30 +645,27 @@ int iunet_dl_wgrad(int dtype, int nd, int rate, const void* x, long long x_ss, i
   IUNET_REQUIRE(ci_off >= 0 && ci_off + Cin <= Cin_tot, "dl_wgrad: channels %d at %d of %d", Cin, ci_off, Cin_tot);
   IUNET_REQUIRE(x && dy && slab && dW, "dl_wgrad: null pointer");
   IUNET_REQUIRE(!x_scale == !x_shift, "dl_wgrad: the input activation needs both scale and shift");
-  DlWg p;
+  GgWg p;
+  DlWgGather g;
   const int colbase = 0;
-  const int rb = dl_build(p.taps, nd, 1, &rate, &cbase, &colbase, D, H, W, Cin);
+  const int rb = dl_build(g.taps, nd, 1, &rate, &cbase, &colbase, D, H, W, Cin);
   if (rb != IUNET_OK) return rb;
-  p.x = x; p.x_ss = x_ss; p.dy = dy; p.dy_ss = dy_ss;
-  p.in_scale = (const float*)x_scale; p.in_shift = (const float*)x_shift; p.slab = (float*)slab;
-  p.N = N; p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.K = p.taps.n * Cin;
+  g.x = x; g.x_ss = x_ss; g.in_scale = (const float*)x_scale; g.in_shift = (const float*)x_shift; g.Cin = Cin;
+  p.dy = dy; p.dy_ss = dy_ss; p.slab = (float*)slab;
+  p.D = D; p.H = H; p.W = W; p.Cout = Cout; p.K = g.taps.n * Cin;
   p.cols = (long long)N * D * H * W;
-  const int splits = dl_wgrad_splits(p.cols, (long long)Cout * p.K);
+  const int splits = gg_wgrad_splits(p.cols, (long long)Cout * p.K);
   const long long nchunks = (p.cols + 31) / 32;
   p.chunks_per_split = (nchunks + splits - 1) / splits;
   const dim3 grid(splits, (Cout + 63) / 64, (p.K + 63) / 64);
-  const bool act = x_scale != nullptr;
-#define DLW(TT, NDV, AV) hipLaunchKernelGGL((dl_wgrad_kernel<TT, NDV, AV>), grid, dim3(256), 0, (hipStream_t)stream, p)
-#define DLW_A(TT, NDV) do { if (act) DLW(TT, NDV, true); else DLW(TT, NDV, false); } while (0)
-  if (dtype == 0) { if (nd == 3) DLW_A(f16, 3); else DLW_A(f16, 2); }
-  else { if (nd == 3) DLW_A(bf16, 3); else DLW_A(bf16, 2); }
-#undef DLW_A
-#undef DLW
+  gg_dispatch(dtype, nd, x_scale != nullptr, [&](auto t, auto, auto act) {
+    hipLaunchKernelGGL((gg_wgrad_kernel<decltype(t), act.value, DlWgGather>), grid, dim3(256), 0, (hipStream_t)stream, p, g);
+  });
   IUNET_CHECK_HIP(hipGetLastError());
   const int kvol = rate == 0 ? 1 : (nd == 3 ? 27 : 9);
   const long long total = (long long)Cout * Cin * kvol;
   hipLaunchKernelGGL(dl_wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)slab, splits,
-                     Cin, Cout, p.K, kvol, alpha, (float*)dW, Cin_tot, ci_off, p.taps);
+                     Cin, Cout, p.K, kvol, alpha, (float*)dW, Cin_tot, ci_off, g.taps);
   IUNET_CHECK_HIP(hipGetLastError());
   return IUNET_OK;
 }
@@ -920,19 +676,20 @@ int iunet_dl_f32_conv_fwd(int nd, int rate, const void* x, long long x_ss, void*
   if (rc != IUNET_OK) return rc;
   IUNET_REQUIRE(Cin > 0 && Cout > 0 && Cin % 8 == 0 && Cout % 16 == 0, "dl_f32_conv_fwd: Cin %d (multiple of 8), Cout %d (multiple of 16)", Cin, Cout);
   IUNET_REQUIRE(x && y && wpk && bias, "dl_f32_conv_fwd: null pointer");
-  DlF32 p;
+  GgFwd p = {};
+  DlFwdGather g;
   const int zero = 0;
-  const int rb = dl_build(p.taps, nd, 1, &rate, &zero, &zero, D, H, W, Cin);
+  const int rb = dl_build(g.taps, nd, 1, &rate, &zero, &zero, D, H, W, Cin);
   if (rb != IUNET_OK) return rb;
-  for (int t = 0; t < p.taps.n; ++t)
-    IUNET_REQUIRE(p.taps.col[t] + Cin <= Kw, "dl_f32_conv_fwd: tap %d reads operator columns past the row length %d", t, Kw);
-  p.x = (const float*)x; p.x_ss = x_ss; p.y = (float*)y; p.y_ss = y_ss; p.wpk = (const float*)wpk; p.Kw = Kw;
-  p.bias = (const float*)bias; p.psb = (const float*)psb;
-  p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.K = p.taps.n * Cin;
-  p.cols = (long long)N * D * H * W;
+  for (int t = 0; t < g.taps.n; ++t)
+    IUNET_REQUIRE(g.taps.col[t] + Cin <= Kw, "dl_f32_conv_fwd: tap %d reads operator columns past the row length %d", t, Kw);
+  p.x = x; p.x_ss = x_ss; p.y = y; p.y_ss = y_ss; p.wpk = wpk; p.bias = (const float*)bias;
+  p.N = N; p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.K = g.taps.n * Cin;
+  p.cols = (long long)N * D * H * W; p.epi = 1;
+  g.lda = Kw; g.psb = (const float*)psb; g.psb_scale = 1.f;
   const long long tiles = (p.cols + 15) / 16;
-  const dim3 grid((unsigned)((tiles + DL_WAVES - 1) / DL_WAVES), (Cout + DL_COG - 1) / DL_COG);
-  hipLaunchKernelGGL(dl_f32_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
+  const dim3 grid((unsigned)((tiles + GG_WAVES - 1) / GG_WAVES), (Cout + GG_COG - 1) / GG_COG);
+  hipLaunchKernelGGL(gg_f32_kernel<DlFwdGather>, grid, dim3(256), 0, (hipStream_t)stream, p, g);
   IUNET_CHECK_HIP(hipGetLastError());
   return IUNET_OK;
 }

@@ -11,20 +11,14 @@
 //   2  the data gradient of kind 1: the k4 s2 p1 strided conv over dy, dx[i] = sum_k dy[2i - 1 + k] W[.][.][k], K = 4^d Cout.
 // K runs tap-major, channel-minor, so each 8-wide k group is one 16-byte load of one plane at one voxel.  The operator is packed
 // [class][rows][Kpad] with Kpad = K rounded up to 32 (zeros), so A never needs a bound check.
+// The forward GEMMs are gather_gemm.h's skeletons under the LkGather<ND, KIND> policy.
 #include "common.h"
+#include "gather_gemm.h"
 #include "../../include/iunet.h"
 
 namespace {
 
-template <typename T> using V8T = typename Vec8<T>::type;
-typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-template <typename T> struct Vec4;
-template <> struct Vec4<f16> { typedef f16x4_t type; };
-template <> struct Vec4<bf16> { typedef bf16x4_t type; };
-
-constexpr int LK_WAVES = 4;          // waves per workgroup of the forward GEMM
-constexpr int LK_COG = 64;           // output channels per workgroup (4 row tiles of 16 per wave)
+constexpr int LK_WAVES = 4;          // waves per workgroup of the weight gradient
 
 inline int lk_taps(int nd, int kind) { return kind == 0 ? 1 : kind == 1 ? (1 << nd) : (1 << (2 * nd)); }
 inline int lk_classes(int nd, int kind) { return kind == 1 ? (1 << nd) : 1; }
@@ -53,149 +47,58 @@ __device__ __forceinline__ long long lk_src(int t, int p, int d, int h, int w, i
   }
 }
 
-// relu(scale * x + shift) rounded to T: the bits iunet_bn_relu_fwd stores
-template <typename T>
-__device__ __forceinline__ V8T<T> lk_act(V8T<T> v, const float* sc, const float* sh, int c0) {
-  V8T<T> o;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = from_f32<T>(fmaxf(fmaf(sc[c0 + j], to_f32<T>(v[j]), sh[c0 + j]), 0.f));
-  return o;
+// Output voxel of the column (d, h, w) (flat: r) of class cls: kind 1 scatters the classes over the 2x grid
+template <int ND, int KIND>
+__device__ __forceinline__ long long lk_dst(int cls, int d, int h, int w, long long r, int H, int W) {
+  if constexpr (KIND == 1) {
+    const int od = ND == 3 ? 2 * d + ((cls >> 2) & 1) : 0, oh = 2 * h + ((cls >> 1) & 1), ow = 2 * w + (cls & 1);
+    return ((long long)od * (2 * H) + oh) * (2 * W) + ow;
+  } else {
+    return r;
+  }
 }
 
-struct LkFwd {
-  const void* x; long long x_ss;
-  void* y; long long y_ss;
-  const void* wpk;
-  const float* in_scale; const float* in_shift;
-  const float* bias;
-  const void* skip; long long skip_ss;
-  float* stats;                   // [gridDim.z * gridDim.x][Cout][2] or null
-  int N, D, H, W;                 // kind 0: the grid; kind 1: the input grid; kind 2: the output grid
-  int Cin, Cout, K, Kpad;
-  long long cols;                 // columns per class = N * D * H * W
-  int epi;                        // 0 raw (+ stats), 1 + bias + ReLU (+ skip)
+// gather_gemm.h policy of the three kinds.  (D, H, W) is the column grid: kind 0 the grid; kind 1 the input grid (the output is 2x);
+// kind 2 the output grid (the input is 2x).  The operator is [class][Cout][lda = Kpad]; the eval epilogue adds the skip.
+struct LkData {
+  int lda;
+  const void* skip; long long skip_ss;   // NHWC8c T (planar fp32 in the fp32 form) or null
+};
+template <int ND, int KIND>
+struct LkGather : LkData {
+  static constexpr bool A_PADDED = true;
+  static __device__ __forceinline__ long long in_vox(int D, int H, int W) {
+    return KIND == 2 ? (long long)(ND == 3 ? 2 * D : 1) * (2 * H) * (2 * W) : (long long)D * H * W;
+  }
+  static __device__ __forceinline__ long long out_vox(int D, int H, int W) {
+    return KIND == 1 ? (long long)(ND == 3 ? 2 * D : 1) * (2 * H) * (2 * W) : (long long)D * H * W;
+  }
+  __device__ __forceinline__ long long a_row0(int cls, int co0, int Cout) const { return (long long)cls * Cout + co0; }
+  __device__ __forceinline__ int a_col(int, int, int k) const { return k; }
+  __device__ __forceinline__ long long src(int tap, int cls, int d, int h, int w, int D, int H, int W, int& cb) const {
+    cb = 0;
+    return lk_src<ND, KIND>(tap, cls, d, h, w, D, H, W);
+  }
+  static __device__ __forceinline__ long long dst(int cls, int d, int h, int w, long long r, int, int H, int W) {
+    return lk_dst<ND, KIND>(cls, d, h, w, r, H, W);
+  }
+  __device__ __forceinline__ float pre(float v, int, int, int) const { return v; }
+  template <typename T>
+  __device__ __forceinline__ void extra(float (&sk)[4], int n, int co, long long vout, long long ov) const {
+    if (skip == nullptr) return;
+    const typename Vec4<T>::type sv = *(const typename Vec4<T>::type*)((const T*)skip + (long long)n * skip_ss +
+                                                                       ((long long)(co >> 3) * vout + ov) * 8 + (co & 7));
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) sk[rr] = to_f32<T>(sv[rr]);
+  }
+  __device__ __forceinline__ float post(float v, float sk) const { return v + sk; }
+  __device__ __forceinline__ float post32(float v, int n, int co, long long vout, long long ov) const {
+    return skip != nullptr ? v + ((const float*)skip)[(long long)n * skip_ss + (long long)co * vout + ov] : v;
+  }
 };
 
-// grid (blocks, Cout / 64 rounded up, classes); 256 threads; each wave walks column tiles of 16 voxels
-template <typename T, int ND, int KIND, bool ACT>
-__global__ __launch_bounds__(256) void lk_fwd_kernel(LkFwd p) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int cls = blockIdx.z, co0 = blockIdx.y * LK_COG;
-  const int ntile = min(4, (p.Cout - co0) / 16);
-  const T* x = (const T*)p.x;
-  const T* wpk = (const T*)p.wpk + ((long long)cls * p.Cout + co0) * p.Kpad;
-  const int Din = KIND == 1 ? p.D : (KIND == 2 ? (ND == 3 ? 2 * p.D : 1) : p.D);
-  const int Hin = KIND == 2 ? 2 * p.H : p.H, Win = KIND == 2 ? 2 * p.W : p.W;
-  const long long vin = (long long)Din * Hin * Win;
-  const int Dout = KIND == 1 ? (ND == 3 ? 2 * p.D : 1) : p.D, Hout = KIND == 1 ? 2 * p.H : p.H, Wout = KIND == 1 ? 2 * p.W : p.W;
-  const long long vout = (long long)Dout * Hout * Wout, vgrid = (long long)p.D * p.H * p.W;
-  const long long ntiles = (p.cols + 15) / 16;
-  const long long per_block = (ntiles + gridDim.x - 1) / gridDim.x;
-  const long long t0 = (long long)blockIdx.x * per_block, t1 = min(ntiles, t0 + per_block);
-  float ssum[4][4], ssq[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { ssum[a][r] = 0.f; ssq[a][r] = 0.f; }
-  const int q = lane >> 4, l15 = lane & 15;
-  for (long long tile = t0 + wave; tile < t1; tile += LK_WAVES) {
-    const long long col = tile * 16 + l15;
-    const bool ok = col < p.cols;
-    const long long cc = ok ? col : 0;
-    const int n = (int)(cc / vgrid);
-    const long long r = cc - (long long)n * vgrid;
-    const int w = (int)(r % p.W), h = (int)((r / p.W) % p.H), d = (int)(r / ((long long)p.W * p.H));
-    const T* xs = x + (long long)n * p.x_ss;
-    f32x4 acc[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < p.K; k0 += 32) {
-      const int kg = k0 + q * 8;
-      V8T<T> b;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) b[j] = from_f32<T>(0.f);
-      if (ok && kg < p.K) {
-        const int tap = kg / p.Cin, c0 = kg - tap * p.Cin;
-        const long long sv = lk_src<ND, KIND>(tap, cls, d, h, w, p.D, p.H, p.W);
-        if (sv >= 0) {
-          b = *(const V8T<T>*)(xs + ((long long)(c0 >> 3) * vin + sv) * 8);
-          if constexpr (ACT) b = lk_act<T>(b, p.in_scale, p.in_shift, c0);
-        }
-      }
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        if (a < ntile) {
-          const V8T<T> av = *(const V8T<T>*)(wpk + (long long)(a * 16 + l15) * p.Kpad + kg);
-          acc[a] = mfma16<T>(av, b, acc[a]);
-        }
-      }
-    }
-    if (!ok) continue;
-    // output voxel of this column
-    long long ov;
-    if constexpr (KIND == 1) {
-      const int od = ND == 3 ? 2 * d + ((cls >> 2) & 1) : 0, oh = 2 * h + ((cls >> 1) & 1), ow = 2 * w + (cls & 1);
-      ov = ((long long)od * Hout + oh) * Wout + ow;
-    } else {
-      ov = r;
-    }
-    T* ys = (T*)p.y + (long long)n * p.y_ss;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      if (a >= ntile) continue;
-      const int co = co0 + a * 16 + q * 4;
-      typename Vec4<T>::type o;
-      if (p.epi == 0) {
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          o[rr] = from_f32<T>(acc[a][rr]);
-          ssum[a][rr] += acc[a][rr];
-          ssq[a][rr] += acc[a][rr] * acc[a][rr];
-        }
-      } else {
-        float sk[4] = {0.f, 0.f, 0.f, 0.f};
-        if (p.skip != nullptr) {
-          const typename Vec4<T>::type sv = *(const typename Vec4<T>::type*)((const T*)p.skip + (long long)n * p.skip_ss +
-                                                                             ((long long)(co >> 3) * vout + ov) * 8 + (co & 7));
-#pragma unroll
-          for (int rr = 0; rr < 4; ++rr) sk[rr] = to_f32<T>(sv[rr]);
-        }
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) o[rr] = from_f32<T>(fmaxf(acc[a][rr] + p.bias[co + rr], 0.f) + sk[rr]);
-      }
-      *(typename Vec4<T>::type*)(ys + ((long long)(co >> 3) * vout + ov) * 8 + (co & 7)) = o;
-    }
-  }
-  if (p.stats == nullptr) return;
-  // BatchNorm partial sums: the 16 columns of a lane group, then the 4 waves in a fixed order -> one row per workgroup
-  __shared__ float red[LK_WAVES][LK_COG][2];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      float s = ssum[a][rr], s2 = ssq[a][rr];
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) { s += __shfl_xor(s, o); s2 += __shfl_xor(s2, o); }
-      if (l15 == 0) { red[wave][a * 16 + q * 4 + rr][0] = s; red[wave][a * 16 + q * 4 + rr][1] = s2; }
-    }
-  __syncthreads();
-  if (threadIdx.x < 2 * ntile * 16) {
-    const int c = threadIdx.x >> 1, which = threadIdx.x & 1;
-    const float v = (red[0][c][which] + red[1][c][which]) + (red[2][c][which] + red[3][c][which]);
-    p.stats[((long long)(blockIdx.z * gridDim.x + blockIdx.x) * p.Cout + co0 + c) * 2 + which] = v;
-  }
-}
-
 int lk_fwd_blocks(int nd, int kind, int N, int D, int H, int W, int Cout) {
-  const long long cols = (long long)N * D * H * W;
-  const long long tiles = (cols + 15) / 16;
-  const int ncg = (Cout + LK_COG - 1) / LK_COG, ncls = lk_classes(nd, kind);
-  // about 4 column tiles per wave at least, at most ~2048 workgroups per launch (a statistics row per workgroup and class)
-  long long b = (tiles + 4 * LK_WAVES - 1) / (4 * LK_WAVES);
-  const long long cap = (2048 + ncg * ncls - 1) / (ncg * ncls);
-  if (b > cap) b = cap;
-  if (b > 1024) b = 1024;
-  return (int)(b < 1 ? 1 : b);
+  return gg_fwd_blocks((long long)N * D * H * W, (Cout + GG_COG - 1) / GG_COG * lk_classes(nd, kind));
 }
 
 // ---- weight gradient: slab[class][split][Cout][K'] = sum over the split's columns of dy[col][co] * act(x)[k'][col]
@@ -217,8 +120,7 @@ __global__ __launch_bounds__(256) void lk_wgrad_kernel(LkWg p) {
   const int cls = blockIdx.z, mt = blockIdx.y / p.kgroups, kgp = blockIdx.y % p.kgroups;
   const int co = mt * 16 + l15;
   const int kb = kgp * 64;
-  const int Dout = KIND == 1 ? (ND == 3 ? 2 * p.D : 1) : p.D, Hout = KIND == 1 ? 2 * p.H : p.H, Wout = KIND == 1 ? 2 * p.W : p.W;
-  const long long vout = (long long)Dout * Hout * Wout, vin = (long long)p.D * p.H * p.W;
+  const long long vout = LkGather<ND, KIND>::out_vox(p.D, p.H, p.W), vin = (long long)p.D * p.H * p.W;
   const long long steps = (p.cols + 31) / 32;
   const long long per = (steps + gridDim.x - 1) / gridDim.x;
   const long long s0 = (long long)blockIdx.x * per, s1 = min(steps, s0 + per);
@@ -253,11 +155,7 @@ __global__ __launch_bounds__(256) void lk_wgrad_kernel(LkWg p) {
       const int n = (int)(col / vin);
       const long long r = col - (long long)n * vin;
       const int w = (int)(r % p.W), h = (int)((r / p.W) % p.H), d = (int)(r / ((long long)p.W * p.H));
-      long long ov = r;
-      if constexpr (KIND == 1) {
-        const int od = ND == 3 ? 2 * d + ((cls >> 2) & 1) : 0, oh = 2 * h + ((cls >> 1) & 1), ow = 2 * w + (cls & 1);
-        ov = ((long long)od * Hout + oh) * Wout + ow;
-      }
+      const long long ov = lk_dst<ND, KIND>(cls, d, h, w, r, p.H, p.W);
       av[j] = dy[(long long)n * p.dy_ss + ((long long)(co >> 3) * vout + ov) * 8 + (co & 7)];
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
@@ -266,8 +164,7 @@ __global__ __launch_bounds__(256) void lk_wgrad_kernel(LkWg p) {
         if (sv < 0) continue;
         const int c = chk[a];
         const T v = x[(long long)n * p.x_ss + ((long long)(c >> 3) * vin + sv) * 8 + (c & 7)];
-        if constexpr (ACT) bv[a][j] = from_f32<T>(fmaxf(fmaf(p.in_scale[c], to_f32<T>(v), p.in_shift[c]), 0.f));
-        else bv[a][j] = v;
+        bv[a][j] = ACT ? bn_relu1<T>(v, p.in_scale, p.in_shift, c) : v;
       }
     }
 #pragma unroll
@@ -354,13 +251,11 @@ __global__ __launch_bounds__(256) void lk_pack_kernel(const float* __restrict__ 
       const int t = (int)(kk / Cout), co = (int)(kk - (long long)t * Cout);
       v = w[((long long)row * Cout + co) * (1 << (2 * nd)) + t];
     }
-    if (gamma != nullptr && (kind == 0 || kind == 2)) v *= gamma[row] / sqrtf(var[row] + eps);
+    if (gamma != nullptr && (kind == 0 || kind == 2)) v *= bn_fold_scale(gamma, var, eps, row);
   }
   dst[i] = (OT)v;
-  if (bias_out != nullptr && gamma != nullptr && cls == 0 && kk == 0 && (kind == 0 || kind == 2)) {
-    const float sc = gamma[row] / sqrtf(var[row] + eps);
-    bias_out[row] = beta[row] - mean[row] * sc;
-  }
+  if (bias_out != nullptr && gamma != nullptr && cls == 0 && kk == 0 && (kind == 0 || kind == 2))
+    bias_out[row] = bn_fold_bias(beta, mean, bn_fold_scale(gamma, var, eps, row), row);
 }
 
 // D = relu(scale * y + shift) + skip, the sum in fp32, one rounding
@@ -379,69 +274,6 @@ __global__ __launch_bounds__(256) void lk_bn_relu_add_kernel(const T* __restrict
   for (int j = 0; j < 8; ++j)
     o[j] = from_f32<T>(fmaxf(fmaf(scale[pl * 8 + j], to_f32<T>(a[j]), shift[pl * 8 + j]), 0.f) + to_f32<T>(b[j]));
   *(V8T<T>*)(out + n * o_ss + off) = o;
-}
-
-// ---- fp32 form: planar fp32 [N][C][vox] (sample strides in elements), v_mfma_f32_16x16x4_f32: A[row l&15][k l>>4], B[k l>>4][col l&15]
-struct LkF32 {
-  const float* x; long long x_ss;
-  float* y; long long y_ss;
-  const float* wpk; const float* bias;
-  const float* skip; long long skip_ss;
-  int D, H, W, Cin, Cout, K, Kpad;
-  long long cols;
-};
-
-template <int ND, int KIND>
-__global__ __launch_bounds__(256) void lk_f32_kernel(LkF32 p) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, l15 = lane & 15;
-  const int cls = blockIdx.z, co0 = blockIdx.y * LK_COG;
-  const int ntile = min(4, (p.Cout - co0) / 16);
-  const float* wpk = p.wpk + ((long long)cls * p.Cout + co0) * p.Kpad;
-  const long long vin = (long long)p.D * p.H * p.W;
-  const int Dout = KIND == 1 ? (ND == 3 ? 2 * p.D : 1) : p.D, Hout = KIND == 1 ? 2 * p.H : p.H, Wout = KIND == 1 ? 2 * p.W : p.W;
-  const long long vout = (long long)Dout * Hout * Wout;
-  const long long tile = (long long)blockIdx.x * LK_WAVES + wave;
-  const long long col = tile * 16 + l15;
-  const bool ok = col < p.cols;
-  const long long cc = ok ? col : 0;
-  const int n = (int)(cc / vin);
-  const long long r = cc - (long long)n * vin;
-  const int w = (int)(r % p.W), h = (int)((r / p.W) % p.H), d = (int)(r / ((long long)p.W * p.H));
-  const float* xs = p.x + (long long)n * p.x_ss;
-  f32x4 acc[4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
-  int tap = 0, c = q;                        // k = k0 + q, walked incrementally (k0 += 4)
-  while (c >= p.Cin) { c -= p.Cin; ++tap; }
-  for (int k0 = 0; k0 < p.K; k0 += 4) {
-    float b = 0.f;
-    if (ok && k0 + q < p.K) {
-      const long long sv = lk_src<ND, KIND>(tap, cls, d, h, w, p.D, p.H, p.W);
-      if (sv >= 0) b = xs[(long long)c * vin + sv];
-    }
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-      if (a < ntile) acc[a] = __builtin_amdgcn_mfma_f32_16x16x4f32(wpk[(long long)(a * 16 + l15) * p.Kpad + k0 + q], b, acc[a], 0, 0, 0);
-    c += 4;
-    while (c >= p.Cin) { c -= p.Cin; ++tap; }
-  }
-  if (!ok) return;
-  long long ov = r;
-  if constexpr (KIND == 1) {
-    const int od = ND == 3 ? 2 * d + ((cls >> 2) & 1) : 0, oh = 2 * h + ((cls >> 1) & 1), ow = 2 * w + (cls & 1);
-    ov = ((long long)od * Hout + oh) * Wout + ow;
-  }
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    if (a >= ntile) continue;
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      const int co = co0 + a * 16 + q * 4 + rr;
-      float v = fmaxf(acc[a][rr] + p.bias[co], 0.f);
-      if (p.skip != nullptr) v += p.skip[(long long)n * p.skip_ss + (long long)co * vout + ov];
-      p.y[(long long)n * p.y_ss + (long long)co * vout + ov] = v;
-    }
-  }
 }
 
 int lk_check(int nd, int kind, int N, int D, int H, int W, int Cin, int Cout) {
@@ -503,26 +335,21 @@ int iunet_lk_conv_fwd(int dtype, int nd, int kind, const void* x, long long x_ss
   IUNET_REQUIRE(epi == 0 || !stats, "lk_conv_fwd: statistics are taken of the raw output (epi 0) only");
   IUNET_REQUIRE(!in_scale == !in_shift, "lk_conv_fwd: the input activation needs both scale and shift");
   IUNET_REQUIRE(kind != 2 || !in_scale, "lk_conv_fwd: the data gradient (kind 2) takes no input activation");
-  LkFwd p;
+  GgFwd p;
   p.x = x; p.x_ss = x_ss; p.y = y; p.y_ss = y_ss; p.wpk = wpk;
-  p.in_scale = (const float*)in_scale; p.in_shift = (const float*)in_shift; p.bias = (const float*)bias;
-  p.skip = skip; p.skip_ss = skip_ss; p.stats = (float*)stats;
-  p.N = N; p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-  p.K = lk_taps(nd, kind) * Cin; p.Kpad = (int)lk_kpad(p.K);
+  p.in_scale = (const float*)in_scale; p.in_shift = (const float*)in_shift; p.bias = (const float*)bias; p.stats = (float*)stats;
+  p.N = N; p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.K = lk_taps(nd, kind) * Cin;
   p.cols = (long long)N * D * H * W; p.epi = epi;
-  const dim3 grid(lk_fwd_blocks(nd, kind, N, D, H, W, Cout), (Cout + LK_COG - 1) / LK_COG, lk_classes(nd, kind));
-  const bool act = in_scale != nullptr;
-#define LKF(TT, NDV, KV, AV) hipLaunchKernelGGL((lk_fwd_kernel<TT, NDV, KV, AV>), grid, dim3(256), 0, (hipStream_t)stream, p)
-#define LKF_K(TT, NDV)                                                          \
-  do {                                                                          \
-    if (kind == 0) { if (act) LKF(TT, NDV, 0, true); else LKF(TT, NDV, 0, false); } \
-    else if (kind == 1) { if (act) LKF(TT, NDV, 1, true); else LKF(TT, NDV, 1, false); } \
-    else LKF(TT, NDV, 2, false);                                                \
-  } while (0)
-  if (dtype == 0) { if (nd == 3) LKF_K(f16, 3); else LKF_K(f16, 2); }
-  else { if (nd == 3) LKF_K(bf16, 3); else LKF_K(bf16, 2); }
-#undef LKF_K
-#undef LKF
+  const LkData g{(int)lk_kpad(p.K), skip, skip_ss};
+  const dim3 grid(lk_fwd_blocks(nd, kind, N, D, H, W, Cout), (Cout + GG_COG - 1) / GG_COG, lk_classes(nd, kind));
+  gg_dispatch(dtype, nd, in_scale != nullptr, [&](auto t, auto ndc, auto act) {
+    auto launch = [&](auto pol) {
+      hipLaunchKernelGGL((gg_fwd_kernel<decltype(t), act.value, decltype(pol)>), grid, dim3(256), 0, (hipStream_t)stream, p, pol);
+    };
+    if (kind == 0) launch(LkGather<ndc.value, 0>{g});
+    else if (kind == 1) launch(LkGather<ndc.value, 1>{g});
+    else if constexpr (!act.value) launch(LkGather<ndc.value, 2>{g});        // (checked above: kind 2 takes no input activation)
+  });
   IUNET_CHECK_HIP(hipGetLastError());
   return IUNET_OK;
 }
@@ -547,17 +374,10 @@ int iunet_lk_wgrad(int dtype, int nd, int kind, const void* x, long long x_ss, c
   p.K = lk_taps(nd, kind) * Cin; p.cols = (long long)N * D * H * W; p.kgroups = (p.K + 63) / 64;
   const int splits = lk_wgrad_splits(nd, kind, N, D, H, W, Cin, Cout), ncls = lk_classes(nd, kind);
   const dim3 grid(splits, (Cout / 16) * p.kgroups, ncls);
-  const bool act = x_scale != nullptr;
-#define LKW(TT, NDV, KV, AV) hipLaunchKernelGGL((lk_wgrad_kernel<TT, NDV, KV, AV>), grid, dim3(256), 0, (hipStream_t)stream, p)
-#define LKW_K(TT, NDV)                                                          \
-  do {                                                                          \
-    if (kind == 0) { if (act) LKW(TT, NDV, 0, true); else LKW(TT, NDV, 0, false); } \
-    else { if (act) LKW(TT, NDV, 1, true); else LKW(TT, NDV, 1, false); }      \
-  } while (0)
-  if (dtype == 0) { if (nd == 3) LKW_K(f16, 3); else LKW_K(f16, 2); }
-  else { if (nd == 3) LKW_K(bf16, 3); else LKW_K(bf16, 2); }
-#undef LKW_K
-#undef LKW
+  gg_dispatch(dtype, nd, x_scale != nullptr, [&](auto t, auto ndc, auto act) {
+    if (kind == 0) hipLaunchKernelGGL((lk_wgrad_kernel<decltype(t), ndc.value, 0, act.value>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((lk_wgrad_kernel<decltype(t), ndc.value, 1, act.value>), grid, dim3(256), 0, (hipStream_t)stream, p);
+  });
   IUNET_CHECK_HIP(hipGetLastError());
   const long long total = (long long)ncls * Cout * p.K;
   const dim3 rg((unsigned)((total + 255) / 256));
@@ -586,14 +406,14 @@ int iunet_lk_f32_conv_fwd(int nd, int kind, const void* x, long long x_ss, void*
   if (rc != IUNET_OK) return rc;
   IUNET_REQUIRE(kind == 0 || kind == 1, "lk_f32_conv_fwd: kind must be 0 (1x1 conv) or 1 (k4 s2 p1 transposed conv), got %d", kind);
   IUNET_REQUIRE(x && y && wpk && bias, "lk_f32_conv_fwd: null pointer");
-  LkF32 p;
-  p.x = (const float*)x; p.x_ss = x_ss; p.y = (float*)y; p.y_ss = y_ss; p.wpk = (const float*)wpk; p.bias = (const float*)bias;
-  p.skip = (const float*)skip; p.skip_ss = skip_ss;
-  p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.K = lk_taps(nd, kind) * Cin; p.Kpad = (int)lk_kpad(p.K);
-  p.cols = (long long)N * D * H * W;
+  GgFwd p = {};
+  p.x = x; p.x_ss = x_ss; p.y = y; p.y_ss = y_ss; p.wpk = wpk; p.bias = (const float*)bias;
+  p.N = N; p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.K = lk_taps(nd, kind) * Cin;
+  p.cols = (long long)N * D * H * W; p.epi = 1;
+  const LkData g{(int)lk_kpad(p.K), skip, skip_ss};
   const long long tiles = (p.cols + 15) / 16;
-  const dim3 grid((unsigned)((tiles + LK_WAVES - 1) / LK_WAVES), (Cout + LK_COG - 1) / LK_COG, lk_classes(nd, kind));
-#define LK32(NDV, KV) hipLaunchKernelGGL((lk_f32_kernel<NDV, KV>), grid, dim3(256), 0, (hipStream_t)stream, p)
+  const dim3 grid((unsigned)((tiles + GG_WAVES - 1) / GG_WAVES), (Cout + GG_COG - 1) / GG_COG, lk_classes(nd, kind));
+#define LK32(NDV, KV) hipLaunchKernelGGL((gg_f32_kernel<LkGather<NDV, KV>>), grid, dim3(256), 0, (hipStream_t)stream, p, LkGather<NDV, KV>{g})
   if (nd == 3) { if (kind == 0) LK32(3, 0); else LK32(3, 1); } else { if (kind == 0) LK32(2, 0); else LK32(2, 1); }
 #undef LK32
   IUNET_CHECK_HIP(hipGetLastError());

@@ -8,7 +8,8 @@
 // The forward is ONE GEMM [C] x [K = sum ch[l]] whose B operand is gathered resampled straight out of the encoder tensors: no C-channel
 // tensor finer than T and no L C-channel concat ever exists.  The backward follows from the same identity (dZ from fuse.bn's backward,
 // r = sum over (n, t) of dZ):
-//   G_l = dZ R_l(X^l)^T (sf_wgrad_kernel), dW_l = W_f,l^T G_l, dW_f,l = G_l W_l^T + r b_l^T, db_l = W_f,l^T r (sf_param_grad_kernel),
+//   G_l = dZ R_l(X^l)^T (gather_gemm.h's staged weight gradient under the SfResample policy), dW_l = W_f,l^T G_l,
+//   dW_f,l = G_l W_l^T + r b_l^T, db_l = W_f,l^T r (sf_param_grad_kernel),
 //   dX^l = R_l^T(M_l^T dZ) (M^T dZ by iunet_dl_conv_fwd at rate 0 with the transposed operator, R^T by sf_adjoint_kernel).
 //
 // Resampling.  PyTorch's linear interpolation with align_corners=False and an output size: per axis src = max(0, (t + 0.5) in / out - 0.5),
@@ -21,16 +22,10 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gather_gemm.h"
 #include "../../include/iunet.h"
 
 namespace {
-
-template <typename T> using V8T = typename Vec8<T>::type;
-typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-template <typename T> struct Vec4;
-template <> struct Vec4<f16> { typedef f16x4_t type; };
-template <> struct Vec4<bf16> { typedef bf16x4_t type; };
 
 constexpr int SF_MAXS = 6;           // sources (levels) per launch
 constexpr int SF_COLS = 64;          // output voxels per workgroup of the forward GEMM
@@ -271,90 +266,31 @@ __global__ __launch_bounds__(256) void sf_gemm_kernel(SfGemm p) {
   }
 }
 
-// ---- weight gradient G[Cout][K] = sum over (n, t) of dZ[co] R(X)[k]: a workgroup owns a 64 (co) x 64 (k) tile and one split of the
-// columns; per chunk of 32 T voxels its threads load dZ (8 channels of one voxel) and the resampled source (8 operator columns of one
-// voxel), write both into LDS transposed to [row][voxel], and each wave runs the 16 x 64 x 32 product from LDS.
-struct SfWg {
+// ---- weight gradient G[Cout][K] = sum over (n, t) of dZ[co] R(X)[k]: gather_gemm.h's weight-gradient policy, B[k] = the source that
+// owns operator column k, resampled at the T voxel
+template <int ND>
+struct SfResample {
   SfSrcs src;
-  const void* dz; long long dz_ss;
-  float* slab;
-  int D, H, W;
-  int Cout, K;
-  long long cols, chunks_per_split;
+  struct Lane { const SfSrc* s; int c0; };
+  __device__ __forceinline__ Lane lane(int k_l, bool k_ok) const {
+    int si = 0;
+    if (k_ok)
+      while (si + 1 < src.n && k_l >= src.s[si + 1].koff) ++si;
+    return Lane{&src.s[si], k_l - src.s[si].koff};
+  }
+  template <typename T, bool ACT>
+  __device__ __forceinline__ V8T<T> column(const Lane& l, int n, long long r, int D, int H, int W) const {
+    const int w = (int)(r % W), h = (int)((r / W) % H), d = (int)(r / ((long long)W * H));
+    const SfAx ad = ND == 3 ? sf_axis(d, D, l.s->D) : SfAx{0, 0, 0.f};
+    const SfAx ah = sf_axis(h, H, l.s->H), aw = sf_axis(w, W, l.s->W);
+    float v[8];
+    sf_sample<T, ND, ACT>(*l.s, n, l.c0, ad, ah, aw, v);
+    V8T<T> vb;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) vb[j] = from_f32<T>(v[j]);
+    return vb;
+  }
 };
-
-template <typename T, int ND, bool ACT>
-__global__ __launch_bounds__(256) void sf_wgrad_kernel(SfWg p) {
-  __shared__ __attribute__((aligned(16))) T sA[64 * SF_LD16];
-  __shared__ __attribute__((aligned(16))) T sB[64 * SF_LD16];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, l15 = lane & 15;
-  const int co0 = blockIdx.y * 64, kb = blockIdx.z * 64;
-  const long long vT = (long long)p.D * p.H * p.W;
-  const long long nchunks = (p.cols + 31) / 32;
-  const long long c_lo = (long long)blockIdx.x * p.chunks_per_split, c_hi = min(nchunks, c_lo + p.chunks_per_split);
-  const T* dz = (const T*)p.dz;
-  const int g = threadIdx.x >> 5, jc = threadIdx.x & 31;
-  const int co_l = co0 + g * 8, k_l = kb + g * 8;
-  const bool co_ok = co_l < p.Cout, k_ok = k_l < p.K;
-  int si = 0;
-  if (k_ok)
-    while (si + 1 < p.src.n && k_l >= p.src.s[si + 1].koff) ++si;
-  const SfSrc& s = p.src.s[si];
-  const int c0 = k_l - s.koff;
-  f32x4 acc[4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (long long ck = c_lo; ck < c_hi; ++ck) {
-    const long long col = ck * 32 + jc;
-    V8T<T> va, vb;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { va[j] = from_f32<T>(0.f); vb[j] = from_f32<T>(0.f); }
-    if (col < p.cols) {
-      const int n = (int)(col / vT);
-      const long long r = col - (long long)n * vT;
-      if (co_ok) va = *(const V8T<T>*)(dz + (long long)n * p.dz_ss + ((long long)(co_l >> 3) * vT + r) * 8);
-      if (k_ok) {
-        const int w = (int)(r % p.W), h = (int)((r / p.W) % p.H), d = (int)(r / ((long long)p.W * p.H));
-        const SfAx ad = ND == 3 ? sf_axis(d, p.D, s.D) : SfAx{0, 0, 0.f};
-        const SfAx ah = sf_axis(h, p.H, s.H), aw = sf_axis(w, p.W, s.W);
-        float v[8];
-        sf_sample<T, ND, ACT>(s, n, c0, ad, ah, aw, v);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) vb[j] = from_f32<T>(v[j]);
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { sA[(g * 8 + j) * SF_LD16 + jc] = va[j]; sB[(g * 8 + j) * SF_LD16 + jc] = vb[j]; }
-    __syncthreads();
-    const V8T<T> a = *(const V8T<T>*)(sA + (wave * 16 + l15) * SF_LD16 + q * 8);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const V8T<T> b = *(const V8T<T>*)(sB + (t * 16 + l15) * SF_LD16 + q * 8);
-      acc[t] = mfma16<T>(a, b, acc[t]);
-    }
-  }
-  float* out = p.slab + (long long)blockIdx.x * p.Cout * p.K;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int kk = kb + t * 16 + l15;
-    if (kk >= p.K) continue;
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      const int co = co0 + wave * 16 + q * 4 + rr;
-      if (co < p.Cout) out[(long long)co * p.K + kk] = acc[t][rr];
-    }
-  }
-}
-
-int sf_wgrad_splits(long long cols, long long per_split_floats) {
-  const long long nchunks = (cols + 31) / 32;
-  long long s = (nchunks + 15) / 16;                  // at least 16 chunks (512 voxels) per split
-  if (s > 64) s = 64;
-  if (s < 1) s = 1;
-  while (s > 1 && s * per_split_floats > (8ll << 20)) s >>= 1;
-  return (int)s;
-}
 
 __global__ __launch_bounds__(256) void sf_wgrad_reduce_kernel(const float* __restrict__ slab, int splits, long long total, float* __restrict__ G) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -449,7 +385,7 @@ __global__ __launch_bounds__(256) void sf_pack_kernel(SfOps o, const float* gamm
     const float* wf = o.wf + (long long)c * o.L * o.C + (long long)(o.L - 1 - l) * o.C;
     float s = 0.f;
     for (int j = 0; j < o.C; ++j) s = fmaf(wf[j], o.w[l][(long long)j * o.ch[l] + kk], s);
-    const float sc = gamma != nullptr ? gamma[c] / sqrtf(var[c] + eps) : 1.f;
+    const float sc = gamma != nullptr ? bn_fold_scale(gamma, var, eps, c) : 1.f;
     dst[i] = (OT)(s * sc);
     if (dstT != nullptr) dstT[(long long)k * o.C + c] = (OT)s;
   } else if (i < nop + o.C && bias != nullptr) {
@@ -460,7 +396,7 @@ __global__ __launch_bounds__(256) void sf_pack_kernel(SfOps o, const float* gamm
       for (int j = 0; j < o.C; ++j) s = fmaf(wf[j], o.b[l][j], s);
     }
     if (gamma != nullptr) {
-      const float sc = gamma[c] / sqrtf(var[c] + eps);
+      const float sc = bn_fold_scale(gamma, var, eps, c);
       s = sc * (s - mean[c]) + bnb[c];
     }
     bias[c] = s;
@@ -606,15 +542,12 @@ int iunet_sf_gemm(int dtype, int nd, int nsrc, const void* const* x, const long 
   const dim3 grid((unsigned)iunet_sf_stats_parts(N, D, H, W));
   const size_t es = dtype == 2 ? 4 : 2, ld = dtype == 2 ? SF_LD32 : SF_LD16;
   const size_t lds = (size_t)(SF_COLS + Cout) * ld * es;
-#define SFG(TT, NDV, AV) do { \
-    if (lds > 65536) IUNET_SET_MAX_LDS((sf_gemm_kernel<TT, NDV, AV>), (int)lds); \
-    hipLaunchKernelGGL((sf_gemm_kernel<TT, NDV, AV>), grid, dim3(256), lds, (hipStream_t)stream, p); } while (0)
-#define SFG_A(TT, NDV) do { if (act) SFG(TT, NDV, true); else SFG(TT, NDV, false); } while (0)
-#define SFG_D(TT) do { if (nd == 3) SFG_A(TT, 3); else SFG_A(TT, 2); } while (0)
-  if (dtype == 0) SFG_D(f16); else if (dtype == 1) SFG_D(bf16); else SFG_D(float);
-#undef SFG_D
-#undef SFG_A
-#undef SFG
+  const int rl = gg_dispatch<true>(dtype, nd, act, [&](auto t, auto ndc, auto a) -> int {
+    if (lds > 65536) IUNET_SET_MAX_LDS((sf_gemm_kernel<decltype(t), ndc.value, a.value>), (int)lds);
+    hipLaunchKernelGGL((sf_gemm_kernel<decltype(t), ndc.value, a.value>), grid, dim3(256), lds, (hipStream_t)stream, p);
+    return IUNET_OK;
+  });
+  if (rl != IUNET_OK) return rl;
   IUNET_CHECK_HIP(hipGetLastError());
   return IUNET_OK;
 }
@@ -622,7 +555,7 @@ int iunet_sf_gemm(int dtype, int nd, int nsrc, const void* const* x, const long 
 long long iunet_sf_wgrad_slab_floats(int N, int D, int H, int W, int K, int Cout) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || K <= 0 || Cout <= 0) return -1;
   const long long per = (long long)Cout * K;
-  return sf_wgrad_splits((long long)N * D * H * W, per) * per;
+  return gg_wgrad_splits((long long)N * D * H * W, per) * per;
 }
 
 int iunet_sf_wgrad(int dtype, int nd, int nsrc, const void* const* x, const long long* x_ss, const int* cin, const int* dims, const void* const* sc,
@@ -632,24 +565,23 @@ int iunet_sf_wgrad(int dtype, int nd, int nsrc, const void* const* x, const long
   if (rc != IUNET_OK) return rc;
   IUNET_REQUIRE(Cout > 0 && Cout % 8 == 0, "sf_wgrad: Cout %d (a positive multiple of 8)", Cout);
   IUNET_REQUIRE(dz && slab && G, "sf_wgrad: null pointer");
-  SfWg p;
+  GgWg p;
+  SfSrcs src;
   bool act = false;
-  const int rs = sf_build_srcs(p.src, nd, nsrc, x, x_ss, cin, dims, sc, sh, act);
+  const int rs = sf_build_srcs(src, nd, nsrc, x, x_ss, cin, dims, sc, sh, act);
   if (rs != IUNET_OK) return rs;
-  p.dz = dz; p.dz_ss = dz_ss; p.slab = (float*)slab;
-  p.D = D; p.H = H; p.W = W; p.Cout = Cout; p.K = p.src.s[nsrc - 1].koff + p.src.s[nsrc - 1].C;
+  p.dy = dz; p.dy_ss = dz_ss; p.slab = (float*)slab;
+  p.D = D; p.H = H; p.W = W; p.Cout = Cout; p.K = src.s[nsrc - 1].koff + src.s[nsrc - 1].C;
   p.cols = (long long)N * D * H * W;
   const long long per = (long long)Cout * p.K;
-  const int splits = sf_wgrad_splits(p.cols, per);
+  const int splits = gg_wgrad_splits(p.cols, per);
   const long long nchunks = (p.cols + 31) / 32;
   p.chunks_per_split = (nchunks + splits - 1) / splits;
   const dim3 grid(splits, (Cout + 63) / 64, (p.K + 63) / 64);
-#define SFW(TT, NDV, AV) hipLaunchKernelGGL((sf_wgrad_kernel<TT, NDV, AV>), grid, dim3(256), 0, (hipStream_t)stream, p)
-#define SFW_A(TT, NDV) do { if (act) SFW(TT, NDV, true); else SFW(TT, NDV, false); } while (0)
-  if (dtype == 0) { if (nd == 3) SFW_A(f16, 3); else SFW_A(f16, 2); }
-  else { if (nd == 3) SFW_A(bf16, 3); else SFW_A(bf16, 2); }
-#undef SFW_A
-#undef SFW
+  gg_dispatch(dtype, nd, act, [&](auto t, auto ndc, auto a) {
+    hipLaunchKernelGGL((gg_wgrad_kernel<decltype(t), a.value, SfResample<ndc.value>>), grid, dim3(256), 0, (hipStream_t)stream, p,
+                       SfResample<ndc.value>{src});
+  });
   IUNET_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(sf_wgrad_reduce_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)slab, splits,
                      per, (float*)G);

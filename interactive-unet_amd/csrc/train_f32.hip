@@ -11,10 +11,7 @@
 //   f32_head_loss_fwd / _bwd                            1x1 head + softmax + metrics.py loss sums, and their gradient
 //   f32_channel_sum                                     bias gradients
 // A checking mode: simple, deterministic (no atomics), not tuned -- 1/16 of the 16-bit matrix rate at best.
-#include "common.h"
-
-int iunet_loss_finalize_launch(const float* slab, int nparts, int ncls, int kind, int has_weight, double nvox_total, float* out4,
-                               float* coef, hipStream_t stream);
+#include "loss_terms.h"
 
 namespace {
 

@@ -6,7 +6,6 @@
 
 namespace {
 
-template <typename T> using V8T = typename Vec8<T>::type;
 
 // ------------------------------------------------------------------ convT k2 s2: dx = W . dy(gathered)
 // dx[ci][v] = sum_{pos, co} W[ci][co][pos] * dy[co][2v + pos].

@@ -7,7 +7,6 @@
 
 namespace {
 
-template <typename T> using V8T = typename Vec8<T>::type;
 
 // ------------------------------------------------------------------ BN statistics -> scale/shift
 // slab [nparts][C][2] (sum, sumsq of the raw conv output).  One block per channel.
@@ -1442,7 +1441,7 @@ __global__ __launch_bounds__(256) void bn_sum_pool_bwd_kernel(SumSrcs src, const
     else hipLaunchKernelGGL((kern<bf16>), grid, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); \
   } while (0)
 
-// (train_f32.hip: the fp32 parity form of the head + loss forward shares the finalize pass)
+// (declared in loss_terms.h)
 int iunet_loss_finalize_launch(const float* slab, int nparts, int ncls, int kind, int has_weight, double nvox_total, float* out4,
                                float* coef, hipStream_t stream) {
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, stream, slab, nparts, ncls, kind, has_weight, nvox_total, out4, coef);

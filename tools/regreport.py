@@ -29,9 +29,16 @@ def pretty(n):
         return n
     k = int(m.group(1))
     base, rest = n[m.end():m.end() + k], n[m.end() + k:]
-    args = re.findall(r'DF16_|DF16b|L[ib]\d+E|f', rest.split('Ev')[0]) if rest.startswith('I') else []
     dec = {'DF16_': 'f16', 'DF16b': 'bf16', 'f': 'float'}
-    out = [dec.get(a, a[2:-1] if a[0] == 'L' else a) for a in args]
+    out, rest = [], rest.split('Ev')[0] if rest.startswith('I') else ''
+    while rest:                                   # template arguments: types, integers, and the names of policy structs (NS_<len><name>)
+        m = re.match(r'DF16_|DF16b|L[ib](\d+)E|NS_(\d+)|f', rest)
+        if not m:
+            rest = rest[1:]
+            continue
+        n = int(m.group(2)) if m.group(2) else 0
+        out.append(rest[m.end():m.end() + n] if m.group(2) else m.group(1) or dec[m.group(0)])
+        rest = rest[m.end() + n:]
     return base + ('<' + ','.join(out) + '>' if out else '')
 
 
