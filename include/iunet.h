@@ -34,7 +34,7 @@ int iunet_abi_version(void);
 /* ---- weight packing (host fp32 master weights -> MFMA fragment order) ---------------- */
 /* conv weights fp32 [Cout][Cin][taps] (torch Conv{2,3}d layout); optional per-cout scale
  * folds an eval-mode BatchNorm.  mode bit 0: data-gradient operator (channels transposed, taps
- * mirrored); mode bit 1: K16 fragment order for weight layout 1 (see iunet_conv3_pick_layout); mode bit 2: the compact K16 order (no padded filter column: layout 3 for taps = 27; for taps = 9 the cross-pair step of the 2-D split-precision conv).  dst: iunet_pack_conv3_elems(...) elements of `dtype`. */
+ * mirrored); mode bit 1: K16 fragment order (layout 2), always set: a mode without it is refused (negative status / count); mode bit 2: the compact K16 order (no padded filter column: layout 3; for taps = 9 also the cross-pair step of the 2-D split-precision conv).  So mode = 2, 3 (padded K16, its data-gradient form), 6, 7 (compact).  dst: iunet_pack_conv3_elems(...) elements of `dtype`. */
 long long iunet_pack_conv3_elems(int Cout, int Cin, int taps, int mode);
 int iunet_pack_conv3(int dtype, const void* w, const void* scale, void* dst, int Cout, int Cin, int taps, int mode,
                      void* stream);
@@ -47,7 +47,7 @@ int iunet_pack_first_conv(int dtype, const void* w, const void* scale, void* dst
 int iunet_pack_convT(int dtype, const void* w, void* dst, int Cin, int Cout, int npos, void* stream);
 
 /* All layers in one launch: `descs` = device array of n descriptors (struct layout: csrc/pack_batch.hip PackDesc,
- * mirrored by interactive_unet/_native.py; iunet_pack_desc_bytes() = its size).  kind 0/1 conv3 layout 0/1, 2 first
+ * mirrored by interactive_unet/_native.py; iunet_pack_desc_bytes() = its size).  kind 1 conv3 padded K16 (layout 2), 6 compact K16 (layout 3), 2 first
  * conv, 3 convT, 4 convT data-gradient; a non-NULL gamma folds BatchNorm (scale = gamma / sqrt(var + eps)) and writes
  * the folded bias.  Element mappings are identical to the per-layer entry points above.  A descriptor with a qscale
  * buffer (fp32 [Cout]) has its folded weights quantised to OCP e4m3 values x a per-output-channel power-of-two scale
@@ -59,14 +59,13 @@ int iunet_pack_batch(const void* descs, int n, int quant_max_cout, void* stream)
 /* ---- forward kernels (replace the smp conv stack under unet.py:65-69) ----------------- */
 /* 3^d conv, stride 1, pad 1, implicit GEMM on MFMA.  epi: 0 raw, 1 +bias, 2 +bias+ReLU.
  * stats (optional): fp32 [iunet_conv3_stats_parts(..., layout)][Cout][2] partial sum / sum of squares of
- * the raw output (BatchNorm batch statistics), reduced by the caller. */
+ * the raw output (BatchNorm batch statistics), reduced by the caller.  layout: 2 (wpk = the padded K16 operator, pack mode 2 / 3) or
+ * 3 (the compact one, pack mode 6 / 7, where iunet_conv3_compact_ok allows it); any other value is refused. */
 int iunet_conv3_fwd(int dtype, int nd, const void* x, long long x_sstride, void* y, long long y_sstride,
                     const void* wpk, const void* bias, void* stats, int N, int D, int H, int W, int Cin, int Cout,
                     int epi, int layout, void* stream);
-/* which kernel structure / weight layout serves this launch best: 0 = 32-channel chunks, weights through
- * registers (wpk packed with mode bit 1 clear); 1 = persistent LDS-fed Cout-32 structure (mode bit 1 set);
- * 2 = weight-stationary variant of 1 (same mode-bit-1 operator; 3-D, Cin <= 64: all weights of a Cout tile stay
- * in LDS for the whole launch).  Layout 1 or 2 is mandatory when Cout is not a multiple of 64. */
+/* Kept for callers of the first ABI, which had more than one kernel structure to choose from: always 2 (the padded K16 operator,
+ * conv3_v4.hip).  iunet_conv3_plan is the choice between layouts 2 and 3. */
 int iunet_conv3_pick_layout(int nd, int N, int D, int H, int W, int Cin, int Cout);
 /* 1 if a layout-2 launch of this shape walks its tiles in pairs (one weight stream per two tiles: 3-D, streamed weights, an even
  * number of tiles per workgroup), else 0.  Speed only: the results are the same bits either way.  Exposed for the tests. */
@@ -78,13 +77,22 @@ int iunet_conv3_tile_pairs(int nd, int N, int D, int H, int W, int Cin, int Cout
  * up to 64 input channels), else 0: use layout 2.  The answer does not depend on the grid: layouts
  * 2 and 3 add the taps in different orders, and a layer keeps one order whatever the number of blocks in a launch. */
 int iunet_conv3_compact_ok(int nd, int N, int D, int H, int W, int Cin, int Cout, int act, int bw);
+/* The launch policy of a 16-bit stage conv (Cin = the launch's input channels: the conv's output channels for a data gradient).
+ * iunet_conv3_packs_compact: 1 if a conv with this filter and input width packs the compact operator beside the padded K16 one (which
+ * every conv packs).  iunet_conv3_plan -> the layout (2 or 3) of a launch that asks for a fused input activation (act) and / or fused
+ * BatchNorm- / GroupNorm-backward sums (bw); have_compact: the compact operator was packed.  A fusion exists iff nd == 3 or
+ * Cin <= 64: *fused (may be NULL) = 1 if what was asked for is granted, 0 if the launch runs plain (then the caller applies the
+ * activation / reduces the sums in a pass of its own) or nothing was asked for.  Both refuse arguments no conv has (taps other than
+ * 9 / 27, nd other than 2 / 3, an empty grid, channel counts that are not positive multiples of 32) with a negative status. */
+int iunet_conv3_packs_compact(int taps, int Cin);
+int iunet_conv3_plan(int nd, int N, int D, int H, int W, int Cin, int Cout, int act, int bw, int have_compact, int* fused);
 /* iunet_conv3_fwd whose input is relu(in_scale[c] * x + in_shift[c]) (fp32 [Cin] each): in training the BatchNorm + ReLU of
- * the previous conv is applied by the loader waves instead of a separate pass over HBM.  Layout 2 only. */
+ * the previous conv is applied by the loader waves instead of a separate pass over HBM.  Layouts 2 and 3, where iunet_conv3_plan grants it. */
 int iunet_conv3_fwd_act(int dtype, int nd, const void* x, long long x_sstride, void* y, long long y_sstride,
                         const void* wpk, const void* bias, void* stats, const void* in_scale, const void* in_shift,
                         int N, int D, int H, int W, int Cin, int Cout, int epi, int layout, void* stream);
 int iunet_conv3_num_tiles(int nd, int N, int D, int H, int W);
-/* rows of partial sums a conv3_fwd launch writes: one per tile (layouts 0, 1) or one per workgroup (layout 2) */
+/* rows of partial sums a conv3_fwd launch writes: one per workgroup (layouts 2 and 3) */
 int iunet_conv3_stats_parts(int nd, int N, int D, int H, int W, int Cout, int layout);
 /* first conv reads the caller's tensor directly: in_dtype 0 f32, 1 f16, 2 u8 (x/255,
  * predict.py:30), 3 bf16; in_strides = element strides (n, c, d, h, w).  stats (optional): partial BatchNorm
@@ -342,7 +350,7 @@ int iunet_net_eval_step(iunet_net* net, const void* x, int in_dtype, const long 
  * e4m3 BYTES (half the weight bytes in HBM and LDS) and the product on v_mfma_f32_16x16x32_fp8_fp8; the 16-bit activations
  * in HBM are rounded to e4m3 (saturating at 448) on their way into LDS -- gfx950 has no mixed fp8 x bf16 MFMA. */
 /* w fp32 [Cout][Cin][taps] (x an optional eval-mode BatchNorm fold, as iunet_f32_pack_conv) -> dst: iunet_f8_pack_conv3_bytes
- * bytes (K16 fragment order of iunet_conv3_pick_layout's layouts 1 / 2, one byte per element), wscale fp32 [Cout]: the
+ * bytes (the padded K16 fragment order of layout 2, one byte per element), wscale fp32 [Cout]: the
  * power-of-two scale 2^k, k minimal with max |w'| / 2^k <= 448, each weight = e4m3(w' / scale); bias_out fp32 [Cout]. */
 /* Operator order of a layer's e4m3 bytes: 0 = K16 ([cob32][chunk16][column pair][dy][2][64 lanes][8 B], v_mfma_f32_16x16x32_fp8_fp8),
  * 1 = K128 (3-D layers with Cin % 32 == 0: per (32 Cout, 32 Cin) block [group 2][dy 3][m 2][half 2][64 lanes][16 B] +
@@ -531,7 +539,7 @@ int iunet_gn_relu_pool_fwd(int dtype, int nd, const void* y, long long y_ss, voi
                            const void* gamma, const void* beta, int groups, float eps, void* slab, void* scale, void* shift, void* mean,
                            void* invstd, int C, int N, int Do, int Ho, int Wo, void* stream);
 /* GroupNorm training without the statistics pass: the conv that produces y writes per-SAMPLE partial sums from its epilogue.
- * iunet_conv3_sample_stats_rows: rows per sample of such a launch on this grid and layout (2 or 3), 0 = not available (layouts 0 / 1,
+ * iunet_conv3_sample_stats_rows: rows per sample of such a launch on this grid and layout (2 or 3), 0 = not available (any other layout,
  * fewer than 8 bricks per sample): run iunet_gn_relu_fwd.  iunet_conv3_fwd_sample_stats = iunet_conv3_fwd (epi 0, no bias) + stats
  * [N][rows][Cout][2] = (sum, sum of squares) of the fp32 accumulators; its brick schedule is one sample's, walked once per sample.
  * iunet_gn_relu_fwd_rows / _pool_fwd_rows: iunet_gn_relu_fwd / _pool_fwd on that slab (rows > 0; rows = 0: their own statistics pass). */

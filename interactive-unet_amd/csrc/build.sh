@@ -8,8 +8,10 @@ mkdir -p "$OUT" "$HERE/obj"
 if [ "$1" = "--clean" ]; then rm -f "$HERE"/obj/*.o "$OUT/libiunet.so"; fi      # full rebuild (~30 s on 8 cores): what build() runs
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result -Wno-int-to-pointer-cast"
 pids=()
+objs=()                                         # the objects of the sources present (one left behind by a removed source is not linked)
 for f in "$HERE"/*.hip; do
   o="$HERE/obj/$(basename "${f%.hip}").o"
+  objs+=("$o")
   stale=0
   if [ ! -f "$o" ] || [ "$f" -nt "$o" ]; then stale=1; fi
   for h in "$HERE"/*.h; do                      # any shared header (common.h, pack_desc.h, x2_prep_desc.h ...) newer than the object
@@ -21,5 +23,5 @@ for f in "$HERE"/*.hip; do
   fi
 done
 for p in "${pids[@]}"; do wait "$p"; done
-hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libiunet.so" "$HERE"/obj/*.o
+hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libiunet.so" "${objs[@]}"
 echo "built $OUT/libiunet.so"

@@ -14,13 +14,12 @@ void iunet_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-// internal launchers (conv3_mfma.hip, pointwise.hip)
+// internal launchers (conv3_host_pack.hip, pointwise.hip)
 int iunet_conv3_launch(int dtype, int nd, const void* x, long long x_sstride, void* y, long long y_sstride,
                        const void* wpk, const float* bias, float* stats, int N, int D, int H, int W, int Cin,
                        int Cout, int epi, int layout, hipStream_t stream, const float* in_scale = nullptr,
                        const float* in_shift = nullptr, const void* bw_y = nullptr, long long bw_y_ss = 0,
                        const float* const* bw_par = nullptr);
-int iunet_conv3_pick(int nd, int N, int D, int H, int W, int Cin, int Cout);
 int iunet_conv3_v4_launch(int dtype, int nd, const void* x, long long x_sstride, void* y, long long y_sstride, const void* wpk,
                           const float* bias, float* stats, int N, int D, int H, int W, int Cin, int Cout, int epi,
                           const float* in_scale, const float* in_shift, hipStream_t stream, const void* bw_y, long long bw_y_ss,
@@ -84,7 +83,8 @@ int iunet_abi_version(void) { return 1; }
 
 int iunet_conv3_num_tiles(int nd, int N, int D, int H, int W) { return iunet_conv3_tiles(nd, N, D, H, W); }
 
-// rows of the statistics buffer a conv3_fwd launch with this layout writes (and bn_finalize must read)
+// rows of the statistics buffer a conv3_fwd launch writes (and bn_finalize must read): the same for layouts 2 and 3.  (A layout below 2,
+// which no launch accepts any more, keeps its old answer, the tile count of iunet_conv3_num_tiles.)
 int iunet_conv3_stats_parts(int nd, int N, int D, int H, int W, int Cout, int layout) {
   return layout >= 2 ? iunet_conv3_v4_stats_parts(nd, Cout) : iunet_conv3_tiles(nd, N, D, H, W);
 }
@@ -117,22 +117,41 @@ int iunet_pack_convT(int dtype, const void* w, void* dst, int Cin, int Cout, int
   return iunet_pack_convT_launch(dtype, (const float*)w, dst, Cin, Cout, npos, (hipStream_t)stream);
 }
 
-int iunet_conv3_pick_layout(int nd, int N, int D, int H, int W, int Cin, int Cout) {
-  return iunet_conv3_pick(nd, N, D, H, W, Cin, Cout);
-}
+// Kept for callers of the first ABI: every launch runs on layout 2 unless iunet_conv3_plan moves it to the compact operator (layout 3).
+int iunet_conv3_pick_layout(int, int, int, int, int, int, int) { return 2; }
 
 // can this launch run on layout 3 (compact operator, padding-free step: conv3_v4.hip NP)?  Fused BatchNorm-backward sums in 2-D on the
 // resident-weights variant only (Cin <= 64).  3-D:
 // streamed weights (Cin > 32), a fused input activation up to 192 input channels (LDS).  2-D (the cross-pair step): every channel
 // count, a fused input activation on the resident-weights variant only (Cin <= 64: the layers the training forward fuses).
-// IUNET_NO_COMPACT2D=1: A/B switch back to layouts 0 / 1 / 2 in 2-D.
 int iunet_conv3_compact_ok(int nd, int N, int D, int H, int W, int Cin, int Cout, int act, int bw) {
-  static const bool off2d = getenv("IUNET_NO_COMPACT2D") != nullptr;
-  static const bool no_bw2d = getenv("IUNET_NO_COMPACT2D_BW") != nullptr;      // A/B: the fused-sums data gradient back on layout 2
   if ((nd != 2 && nd != 3) || N < 1 || D < 1 || H < 1 || W < 1 || Cin < 32 || Cout < 32 || Cin % 32 || Cout % 32 || (bw && nd != 2)) return 0;
-  if (nd == 2) return !off2d && D == 1 && !((act || bw) && Cin > 64) && !(bw && no_bw2d);
+  if (nd == 2) return D == 1 && !((act || bw) && Cin > 64);
   if (Cin <= 32) return 0;
   return !(act && Cin > 192);        // independent of the grid: a layer keeps one summation order whatever the launch size
+}
+
+// The launch policy of the 16-bit stage conv (and of its data gradient, with the channel roles swapped), stated once:
+//   * which operators a conv of (taps, Cin) packs: the padded K16 one always, the compact one where a launch can use it;
+//   * a fusion (act: input activation in the loader waves; bw: BatchNorm- / GroupNorm-backward sums in the epilogue) exists iff
+//     nd == 3 or Cin <= 64.  A launch that asks for one elsewhere runs plain: *fused = 0 tells the caller, who then materialises the
+//     activation / runs its own reduction pass;
+//   * layout 3 (compact operator) iff it was packed and iunet_conv3_compact_ok says so for what the launch really does, else layout 2
+//     on the padded operator.
+// Both refuse arguments no conv has (negative status): a caller's slip is an error, not a quiet "layout 2".
+int iunet_conv3_packs_compact(int taps, int Cin) {
+  IUNET_REQUIRE(taps == 9 || taps == 27, "conv3_packs_compact: taps must be 9 or 27 (got %d)", taps);
+  IUNET_REQUIRE(Cin >= 32 && Cin % 32 == 0, "conv3_packs_compact: Cin must be a positive multiple of 32 (got %d)", Cin);
+  return taps == 9 || Cin > 32;
+}
+
+int iunet_conv3_plan(int nd, int N, int D, int H, int W, int Cin, int Cout, int act, int bw, int have_compact, int* fused) {
+  IUNET_REQUIRE(nd == 2 || nd == 3, "conv3_plan: nd must be 2 or 3 (got %d)", nd);
+  IUNET_REQUIRE_GRID("conv3_plan", N, D, H, W);
+  IUNET_REQUIRE(Cin >= 32 && Cout >= 32 && Cin % 32 == 0 && Cout % 32 == 0, "conv3_plan: channels must be positive multiples of 32 (%d, %d)", Cin, Cout);
+  const int f = (act || bw) && (nd == 3 || Cin <= 64);
+  if (fused) *fused = f;
+  return have_compact && iunet_conv3_compact_ok(nd, N, D, H, W, Cin, Cout, act && f, bw && f) ? 3 : 2;
 }
 
 int iunet_conv3_tile_pairs(int nd, int N, int D, int H, int W, int Cin, int Cout) {
@@ -147,7 +166,7 @@ int iunet_conv3_fwd(int dtype, int nd, const void* x, long long x_sstride, void*
   IUNET_REQUIRE(x && y && wpk, "conv3: null pointer");
   IUNET_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "conv3: bad shape %d %d %d %d", N, D, H, W);
   IUNET_REQUIRE(epi >= 0 && epi <= 2, "conv3: bad epilogue %d", epi);
-  IUNET_REQUIRE(layout >= 0 && layout <= 3, "conv3: layout must be 0, 1, 2 or 3 (got %d)", layout);
+  IUNET_REQUIRE(layout == 2 || layout == 3, "conv3: layout must be 2 or 3 (got %d)", layout);
   return iunet_conv3_launch(dtype, nd, x, x_sstride, y, y_sstride, wpk, (const float*)bias, (float*)stats, N, D, H, W,
                             Cin, Cout, epi, layout, (hipStream_t)stream);
 }
@@ -167,7 +186,7 @@ int iunet_conv3_fwd_act(int dtype, int nd, const void* x, long long x_sstride, v
 }
 
 // GroupNorm: the conv's statistics epilogue per SAMPLE.  iunet_conv3_sample_stats_rows: rows per sample that
-// iunet_conv3_fwd_sample_stats writes on this grid and layout (2 or 3), or 0 when the launch has no per-sample form (layouts 0 / 1; a
+// iunet_conv3_fwd_sample_stats writes on this grid and layout (2 or 3), or 0 when the launch has no per-sample form (a
 // grid with fewer than 8 bricks per sample: the caller runs its own statistics pass, iunet_gn_relu_fwd).  iunet_conv3_fwd_sample_stats =
 // iunet_conv3_fwd (epi 0, no bias) writing stats [N][rows][Cout][2] = (sum, sum of squares) of the fp32 accumulators: the slab of
 // iunet_gn_relu_fwd_rows / iunet_gn_relu_pool_fwd_rows.  The brick schedule is one sample's, walked once per sample.

@@ -9,7 +9,7 @@
 //     the way, else through registers with the BatchNorm + ReLU of the producing conv applied (iunet_conv3_wgrad_act);
 //   * 8 CONSUMER waves.  A k-step is one tile row of 32 pixels; the x fragment of halo row h at column shift dx serves the three filter
 //     rows (gradient rows h, h - 1, h - 2): per halo row a wave reads one gradient fragment and three x fragments for nine MFMAs
-//     (0.53 fragment reads per MFMA; the first form, conv3_wgrad_kernel<T, 2>: 0.7, two workgroups of 4 waves per CU with loads and
+//     (0.53 fragment reads per MFMA; the retired first form: 0.7, two workgroups of 4 waves per CU with loads and
 //     MFMAs in the same waves).  A wave owns a (16 co) x (16 ci) corner of the block with all three dx: 9 accumulators.
 // Two block shapes:
 //   * CO64 (Cout % 64 == 0): block = 64 co x 32 ci, tile 8 x 32 pixels; wave = (ci half, co quarter), every wave walks the whole tile.

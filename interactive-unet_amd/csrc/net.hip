@@ -54,9 +54,9 @@ int iunet_pack_first_conv(int, const void*, const void*, void*, int, int, int, v
 int iunet_pack_convT(int, const void*, void*, int, int, int, void*);
 long long iunet_pack_conv3_elems(int, int, int, int);
 long long iunet_pack_first_conv_elems(int, int, int);
-int iunet_conv3_pick_layout(int, int, int, int, int, int, int);
+int iunet_conv3_packs_compact(int, int);
+int iunet_conv3_plan(int, int, int, int, int, int, int, int, int, int, int*);
 int iunet_x2_pack_mode(int);
-int iunet_conv3_compact_ok(int, int, int, int, int, int, int, int, int);
 int iunet_first_conv_fwd(int, int, const void*, int, const long long*, void*, long long, const void*, const void*, void*, int, int, int,
                          int, int, int, int, void*);
 int iunet_conv3_fwd(int, int, const void*, long long, void*, long long, const void*, const void*, void*, int, int, int, int, int, int,
@@ -96,7 +96,7 @@ struct Param { std::string name; long long off, numel; };
 struct ConvOp {                       // one stage conv (or the first conv): where its parameters and packed operators live
   int ci, co, first;
   long long w, bn;                    // flat-parameter offsets: weight; gamma (beta, mean, var follow, co each)
-  long long pk[4];                    // packed-buffer byte offsets by layout (0, 1 = K16, 3 = compact; -1 = absent); x2: pk[1]; x2m: pk[1] = w_hi (K16), pk[0] = K128 bytes
+  long long pk[4];                    // packed-buffer byte offsets: pk[1] = the padded K16 operator (layout 2), pk[3] = the compact one (layout 3; -1 = absent); x2: pk[1]; x2m: pk[1] = w_hi (K16), pk[0] = K128 bytes
   long long aux;                      // x2: [oscale co | bias co] floats; 16-bit: [scale co | bias co]
 };
 struct UpOp { int ci, co; long long w, b, pk, aux; };
@@ -188,13 +188,9 @@ WsLayout ws_layout(const iunet_net* n, int N, int D, int H, int W) {
 // one 16-bit stage conv on the layout engine.Engine._conv3 picks (the U-Net path of iunet_net_forward)
 int conv16(const iunet_net* n, const ConvOp& op, const void* xp, long long x_ss, void* yp, long long y_ss, int N, int d, int h, int w, void* stream) {
   const float* aux = (const float*)(n->packed + op.aux);
-  int lay = 1;
-  if (op.pk[3] >= 0 && iunet_conv3_compact_ok(n->dim, N, d, h, w, op.ci, op.co, 0, 0)) lay = 3;
-  else {
-    lay = iunet_conv3_pick_layout(n->dim, N, d, h, w, op.ci, op.co);
-    if (lay == 0 && op.pk[0] < 0) lay = 1;
-  }
-  return iunet_conv3_fwd(n->mode, n->dim, xp, x_ss, yp, y_ss, n->packed + op.pk[lay == 2 ? 1 : lay], aux + op.co, nullptr, N, d, h, w, op.ci, op.co, 2, lay,
+  const int lay = iunet_conv3_plan(n->dim, N, d, h, w, op.ci, op.co, 0, 0, op.pk[3] >= 0, nullptr);
+  if (lay < 0) return lay;
+  return iunet_conv3_fwd(n->mode, n->dim, xp, x_ss, yp, y_ss, n->packed + op.pk[lay == 3 ? 3 : 1], aux + op.co, nullptr, N, d, h, w, op.ci, op.co, 2, lay,
                          stream);
 }
 
@@ -317,12 +313,7 @@ static int net_create(int dim, int levels, int base, int cin, int ncls, int mode
         op.pk[0] = pk_take(iunet_x2m_w8_bytes_nd(dim, co, op.ci));
       } else {
         op.pk[1] = pk_take(iunet_pack_conv3_elems(co, vci, n->taps, mode == 2 ? iunet_x2_pack_mode(dim) : 2) * 2);
-        if (mode != 2) {          // the layouts a 16-bit launch may pick (interactive_unet/_native.py: PackedConv)
-          const bool compact2d = n->taps == 9 && iunet_conv3_compact_ok(2, 1, 1, 16, 32, op.ci, co, 0, 0);      // (off: IUNET_NO_COMPACT2D)
-          if (co % 64 == 0 && n->taps == 9 && op.ci > 64 && !compact2d) op.pk[0] = pk_take(iunet_pack_conv3_elems(co, op.ci, n->taps, 0) * 2);
-          const char* nc = getenv("IUNET_NO_COMPACT");                                  // (the switch _native.PackedConv honours: ADVICE r3)
-          if (((n->taps == 27 && op.ci > 32) || compact2d) && !(nc && nc[0])) op.pk[3] = pk_take(iunet_pack_conv3_elems(co, op.ci, n->taps, 6) * 2);
-        }
+        if (mode != 2 && iunet_conv3_packs_compact(n->taps, op.ci) > 0) op.pk[3] = pk_take(iunet_pack_conv3_elems(co, op.ci, n->taps, 6) * 2);
       }
       op.aux = pk_take(2ll * co * 4);
       if (mode >= 2 && 3ll * co * op.ci * n->taps > max_virtual) max_virtual = 3ll * co * op.ci * n->taps;
@@ -422,7 +413,6 @@ int iunet_net_load(iunet_net* n, const void* flat_params, void* packed, void* st
       if (op.first) rc = iunet_pack_first_conv(n->mode, w, aux, K + op.pk[1], op.co, op.ci, n->taps, stream);
       else {
         rc = iunet_pack_conv3(n->mode, w, aux, K + op.pk[1], op.co, op.ci, n->taps, 2, stream);
-        if (!rc && op.pk[0] >= 0) rc = iunet_pack_conv3(n->mode, w, aux, K + op.pk[0], op.co, op.ci, n->taps, 0, stream);
         if (!rc && op.pk[3] >= 0) rc = iunet_pack_conv3(n->mode, w, aux, K + op.pk[3], op.co, op.ci, n->taps, 6, stream);
       }
       if (rc) return rc;
@@ -588,13 +578,7 @@ int iunet_net_forward(iunet_net* n, const void* x, int in_dtype, const long long
                                   n->act_scale, WS + L.gnslab, WS + L.gnsc, WS + L.gnsh, op.co, N, v, WS, stream);
     }
     if (x2) return iunet_x2_conv3_fwd_flag(dim, xp, x_ss, x_lo, yp, y_ss, y_lo, K + op.pk[1], aux, aux + op.co, N, d, h, w, op.ci, op.co, 2, WS, stream);
-    int lay = 1;
-    if (op.pk[3] >= 0 && iunet_conv3_compact_ok(dim, N, d, h, w, op.ci, op.co, 0, 0)) lay = 3;
-    else {
-      lay = iunet_conv3_pick_layout(dim, N, d, h, w, op.ci, op.co);
-      if (lay == 0 && op.pk[0] < 0) lay = 1;
-    }
-    return iunet_conv3_fwd(mode, dim, xp, x_ss, yp, y_ss, K + op.pk[lay == 2 ? 1 : lay], aux + op.co, nullptr, N, d, h, w, op.ci, op.co, 2, lay, stream);
+    return conv16(n, op, xp, x_ss, yp, y_ss, N, d, h, w, stream);
   };
   for (int l = 0; l < lv; ++l) {
     int d, h, w;

@@ -2,7 +2,7 @@
 // inference): the per-layer pack kernels are a few microseconds of work each behind ~5 us of launch latency,
 // ~150 launches per step.  A descriptor table in device memory (built once by the host: all pointers are
 // stable) drives one kernel; blockIdx.y selects the layer.  The element mappings are the ones of the per-layer
-// kernels (conv3_mfma.hip, pointwise.hip, train_misc.hip) -- tests/test_gpu_kernels.py checks bit equality.
+// kernels (conv3_host_pack.hip, pointwise.hip, train_misc.hip) -- tests/test_gpu_kernels.py checks bit equality.
 #include "common.h"
 #include "pack_desc.h"
 
@@ -63,18 +63,6 @@ __device__ __forceinline__ float elem(const PackDesc& d, long long i, int& oc) {
   const int lane = r & 63; r >>= 6;
   const int row = lane & 15, qq = lane >> 4;
   const float* w = d.w;
-  if (d.kind == 0) {                                   // [cob][chunk32][tap][MI][64][8]
-    const int CoutP = d.dgrad ? d.Cin : d.Cout, CinP = d.dgrad ? d.Cout : d.Cin;
-    const int MI = (CoutP % 64 == 0) ? 4 : 2, nchunk = CinP >> 5;
-    const int m = r % MI; r /= MI;
-    const int tap = r % d.taps; r /= d.taps;
-    const int chunk = r % nchunk, cob = r / nchunk;
-    const int co = cob * 16 * MI + 32 * (m >> 1) + 8 * (row >> 2) + 4 * (m & 1) + (row & 3);
-    const int ci = chunk * 32 + 8 * qq + j;
-    oc = co;
-    if (!d.dgrad) return mul_rn(w[((long long)co * d.Cin + ci) * d.taps + tap], fold_scale(d, co));
-    return w[((long long)ci * d.Cin + co) * d.taps + (d.taps - 1 - tap)];
-  }
   if (d.kind == 1) {                                   // [cob32][chunk16][column pair][dy][2][64][8]
     const int CinP = d.dgrad ? d.Cout : d.Cin;
     const int ncol = d.taps / 3, ncmb = (ncol + 1) / 2, nchunk = CinP >> 4;
@@ -123,43 +111,13 @@ __device__ __forceinline__ float elem(const PackDesc& d, long long i, int& oc) {
   }
 }
 
-// The 8 elements of one 16-byte granule (j = 0..7) differ in the input channel only: one index decode per granule, then 8 loads
-// at a fixed stride.  Returns false for a zero granule (the padded partner column of the K16 order).  kind 2 (first conv: k runs
-// over taps and channels) is decoded per element by elem().
-__device__ __forceinline__ bool granule(const PackDesc& d, int r, const float*& src, long long& stride, float& fs, int& oc) {
-  oc = 0; fs = 1.0f;
+// Transposed-conv kinds (3, 4): the 8 elements of one 16-byte granule (j = 0..7) differ in the input channel only: one index decode
+// per granule, then 8 loads at a fixed stride.  (The 3^d convs are packed a K16 block at a time, pack_k16_block / pack_k16c_block;
+// kind 2 -- first conv: k runs over taps and channels -- is decoded per element by elem().)
+__device__ __forceinline__ void granule(const PackDesc& d, int r, const float*& src, long long& stride, int& oc) {
+  oc = 0;
   const int lane = r & 63; r >>= 6;
   const int row = lane & 15, qq = lane >> 4;
-  if (d.kind == 0) {
-    const int CoutP = d.dgrad ? d.Cin : d.Cout, CinP = d.dgrad ? d.Cout : d.Cin;
-    const int MI = (CoutP % 64 == 0) ? 4 : 2, nchunk = CinP >> 5;
-    const int m = r % MI; r /= MI;
-    const int tap = r % d.taps; r /= d.taps;
-    const int chunk = r % nchunk, cob = r / nchunk;
-    const int co = cob * 16 * MI + 32 * (m >> 1) + 8 * (row >> 2) + 4 * (m & 1) + (row & 3);
-    const int ci = chunk * 32 + 8 * qq;
-    oc = co;
-    if (!d.dgrad) { src = d.w + ((long long)co * d.Cin + ci) * d.taps + tap; stride = d.taps; fs = fold_scale(d, co); }
-    else { src = d.w + ((long long)ci * d.Cin + co) * d.taps + (d.taps - 1 - tap); stride = (long long)d.Cin * d.taps; }
-    return true;
-  }
-  if (d.kind == 1) {
-    const int CinP = d.dgrad ? d.Cout : d.Cin;
-    const int ncol = d.taps / 3, ncmb = (ncol + 1) / 2, nchunk = CinP >> 4;
-    const int m = r & 1; r >>= 1;
-    const int dy = r % 3; r /= 3;
-    const int c = r % ncmb; r /= ncmb;
-    const int chunk = r % nchunk, cob = r / nchunk;
-    const int co = cob * 32 + 8 * (row >> 2) + 4 * m + (row & 3);
-    const int ci = chunk * 16 + 8 * (qq & 1);
-    const int col = 2 * c + (qq >> 1);
-    if (col >= ncol) return false;
-    const int tap = ((col / 3) * 3 + dy) * 3 + (col % 3);
-    oc = co;
-    if (!d.dgrad) { src = d.w + ((long long)co * d.Cin + ci) * d.taps + tap; stride = d.taps; fs = fold_scale(d, co); }
-    else { src = d.w + ((long long)ci * d.Cin + co) * d.taps + (d.taps - 1 - tap); stride = (long long)d.Cin * d.taps; }
-    return true;
-  }
   const int npos = d.taps;
   if (d.kind == 3) {
     const int nk = d.Cin >> 5;
@@ -170,7 +128,7 @@ __device__ __forceinline__ bool granule(const PackDesc& d, int r, const float*& 
     const int ci = ks * 32 + 8 * qq;
     oc = co;
     src = d.w + ((long long)ci * d.Cout + co) * npos + s; stride = (long long)d.Cout * npos;
-    return true;
+    return;
   }
   {
     const int nk = d.Cout >> 5;
@@ -180,7 +138,6 @@ __device__ __forceinline__ bool granule(const PackDesc& d, int r, const float*& 
     const int ci = cib * 32 + 8 * (row >> 2) + 4 * t + (row & 3);
     const int co = kc * 32 + 8 * qq;
     src = d.w + ((long long)ci * d.Cout + co) * npos + s; stride = npos;
-    return true;
   }
 }
 
@@ -375,6 +332,7 @@ __device__ __forceinline__ void pack_k16c_block(const PackDesc& d, int blk, floa
 
 // Tasks of one layer: a K16 block each for the 3^d convs, 1 024 granules (of 8 elements) each for the other kinds.
 __device__ __forceinline__ int pack_tasks(const PackDesc& d) {
+  if (d.kind < 1 || d.kind > 6) return 0;              // no such kind (0 was the retired layout-0 order): the row is skipped, nothing is written
   if (d.kind == 1 || d.kind == 5 || d.kind == 6) return ((d.dgrad ? d.Cin : d.Cout) >> 5) * ((d.dgrad ? d.Cout : d.Cin) >> 4);
   const long long gran = (d.total + 7) / 8;
   return (int)((gran + 1023) / 1024);
@@ -418,7 +376,6 @@ __global__ __launch_bounds__(256) void pack_batch_kernel(const PackDesc* __restr
       __syncthreads();                        // the tile is read to the end before the next task overwrites it
       continue;
     }
-    const bool fold = d.gamma != nullptr && !d.dgrad && d.kind <= 1;     // the kinds whose elem() multiplies by the folded scale
 #pragma unroll 1
     for (int k = 0; k < 4; ++k) {
       const long long g = (long long)local * 1024 + k * 256 + threadIdx.x;
@@ -429,18 +386,10 @@ __global__ __launch_bounds__(256) void pack_batch_kernel(const PackDesc* __restr
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = elem(d, g * 8 + j, oc);
       } else {
-        const float* src; long long stride; float fs;
-        if (granule(d, (int)g, src, stride, fs, oc)) {
+        const float* src; long long stride;
+        granule(d, (int)g, src, stride, oc);
 #pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = src[j * stride];
-          if (fold) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = mul_rn(v[j], fs);
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = 0.f;
-        }
+        for (int j = 0; j < 8; ++j) v[j] = src[j * stride];        // (kinds 3 and 4: no BatchNorm fold)
       }
       if (d.qscale) {
         const float sc = d.qscale[oc];

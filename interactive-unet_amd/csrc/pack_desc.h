@@ -10,9 +10,9 @@ struct PackDesc {                // mirrored by interactive_unet/_native.py: Pac
   void* dst;                     // packed operator
   long long total;               // elements of dst
   int Cout, Cin, taps;           // original operator dims (convT: Cin, Cout, npos in `taps`)
-  int kind;                      // 0 conv3 layout 0, 1 conv3 K16 (layout 1), 2 first conv, 3 convT fwd, 4 convT dgrad,
+  int kind;                      // 1 conv3 padded K16 (layout 2), 2 first conv, 3 convT fwd, 4 convT dgrad,  (0 is no kind any more: the builders of a table refuse it, the kernel skips such a row)
                                  // 5 conv3 K16 as OCP e4m3 bytes (conv3_f8.hip's operator; qscale = its per-channel scales, required),
-                                 // 6 conv3 compact K16 (3^3 only; conv3_v4.hip layout 3, conv3_mfma.hip: pack_conv3_k16c_kernel)
+                                 // 6 conv3 compact K16 (conv3_v4.hip layout 3, conv3_host_pack.hip: pack_conv3_k16c_kernel)
   int dgrad;                     // conv3 only: data-gradient operator
   int dtype;                     // 0 f16, 1 bf16
   float eps;

@@ -22,8 +22,8 @@ int iunet_pack_batch(const void*, int, int, void*);
 int iunet_pack_desc_bytes(void);
 long long iunet_pack_conv3_elems(int, int, int, int);
 long long iunet_pack_first_conv_elems(int, int, int);
-int iunet_conv3_pick_layout(int, int, int, int, int, int, int);
-int iunet_conv3_compact_ok(int, int, int, int, int, int, int, int, int);
+int iunet_conv3_packs_compact(int, int);
+int iunet_conv3_plan(int, int, int, int, int, int, int, int, int, int, int*);
 int iunet_conv3_num_tiles(int, int, int, int, int);
 int iunet_conv3_stats_parts(int, int, int, int, int, int, int);
 int iunet_first_conv_fwd(int, int, const void*, int, const long long*, void*, long long, const void*, const void*, void*, int, int, int,
@@ -108,8 +108,8 @@ struct TParam { std::string name; long long off, numel; };
 // one operator in the fragment order(s) its launches may need (interactive_unet/_native.py: PackedConv)
 struct TPack {
   int cout = 0, cin = 0, dg = 0;
-  long long buf[4] = {-1, -1, -1, -1};          // packed-buffer byte offsets of layouts 0, 1 (K16, also layout 2) and 3 (compact)
-  long long elems[4] = {0, 0, 0, 0};
+  long long buf[2] = {-1, -1};                  // packed-buffer byte offsets of the padded K16 operator (layout 2) and the compact one (layout 3; -1: not packed)
+  long long elems[2] = {0, 0};
 };
 
 struct TConv {
@@ -162,22 +162,16 @@ const TConv& conv_of(const iunet_train* n, bool dec, int l, int j) { return n->c
 
 void pack_alloc(TPack& p, int cout, int cin, int taps, int dg, long long& pk) {
   p.cout = cout; p.cin = cin; p.dg = dg;
-  const int out_ch = dg ? cin : cout, in_ch = dg ? cout : cin;
-  auto take = [&](int lay, int mode) { p.elems[lay] = iunet_pack_conv3_elems(cout, cin, taps, mode | dg); p.buf[lay] = pk; pk = align256(pk + p.elems[lay] * 2); };
-  take(1, 2);
-  const bool compact2d = taps == 9 && !env_on("IUNET_NO_COMPACT2D");
-  if (out_ch % 64 == 0 && taps == 9 && in_ch > 64 && !compact2d) take(0, 0);
-  if (((taps == 27 && in_ch > 32) || compact2d) && !env_on("IUNET_NO_COMPACT")) take(3, 6);
+  auto take = [&](int k, int mode) { p.elems[k] = iunet_pack_conv3_elems(cout, cin, taps, mode | dg); p.buf[k] = pk; pk = align256(pk + p.elems[k] * 2); };
+  take(0, 2);
+  if (iunet_conv3_packs_compact(taps, dg ? cout : cin) > 0) take(1, 6);
 }
 
-// (layout, packed-buffer offset) of a launch on this grid (PackedConv.pick)
-int pack_pick(const TPack& p, int nd, int N, int D, int H, int W, bool act, bool bw, long long* off) {
+// layout and packed-buffer offset of a launch on this grid; *fused: the fusion it asked for is granted (iunet_conv3_plan; PackedConv.pick)
+int pack_pick(const TPack& p, int nd, int N, int D, int H, int W, bool act, bool bw, long long* off, int* fused = nullptr) {
   const int in_ch = p.dg ? p.cout : p.cin, out_ch = p.dg ? p.cin : p.cout;
-  int lay = iunet_conv3_pick_layout(nd, N, D, H, W, in_ch, out_ch);
-  bw = bw && lay == 2;
-  if (p.buf[3] >= 0 && iunet_conv3_compact_ok(nd, N, D, H, W, in_ch, out_ch, act ? 1 : 0, bw ? 1 : 0)) { *off = p.buf[3]; return 3; }
-  if (lay == 0 && p.buf[0] < 0) lay = 1;
-  *off = p.buf[lay == 2 ? 1 : lay];
+  const int lay = iunet_conv3_plan(nd, N, D, H, W, in_ch, out_ch, act, bw, p.buf[1] >= 0, fused);      // (negative: arguments refused)
+  *off = p.buf[lay == 3];
   return lay;
 }
 
@@ -210,7 +204,7 @@ TWs ws_layout(const iunet_train* n, int N, int D, int H, int W) {
       max_stats = std::max(max_stats, (long long)iunet_conv3_num_tiles(dim, N, d, h, w) * c.co * 2);
       max_wslab = std::max(max_wslab, (long long)iunet_first_conv_wgrad_blocks(dim, N, d, h, w) * c.co * 112);
     } else {
-      const long long p0 = iunet_conv3_stats_parts(dim, N, d, h, w, c.co, 0), p2 = iunet_conv3_stats_parts(dim, N, d, h, w, c.co, 2);
+      const long long p0 = iunet_conv3_num_tiles(dim, N, d, h, w), p2 = iunet_conv3_stats_parts(dim, N, d, h, w, c.co, 2);      // (p0: the slab's size since the first ABI, kept)
       max_stats = std::max(max_stats, std::max(p0, p2) * c.co * 2);
       if (n->norm == 1)       // per-sample rows of the conv epilogue (layouts 2 and 3 share the grid)
         for (int lay = 2; lay <= 3; ++lay)
@@ -273,7 +267,7 @@ TWs ws_layout_nested(const iunet_train* n, int N, int D, int H, int W) {
       max_stats = std::max(max_stats, (long long)iunet_conv3_num_tiles(dim, N, d, h, w) * c.co * 2);
       max_wslab = std::max(max_wslab, (long long)iunet_first_conv_wgrad_blocks(dim, N, d, h, w) * c.co * 112);
     } else {
-      const long long p0 = iunet_conv3_stats_parts(dim, N, d, h, w, c.co, 0), p2 = iunet_conv3_stats_parts(dim, N, d, h, w, c.co, 2);
+      const long long p0 = iunet_conv3_num_tiles(dim, N, d, h, w), p2 = iunet_conv3_stats_parts(dim, N, d, h, w, c.co, 2);      // (p0: the slab's size since the first ABI, kept)
       max_stats = std::max(max_stats, std::max(p0, p2) * c.co * 2);
       max_wslab = std::max(max_wslab, iunet_conv3_wgrad_slab_floats(dim, N, d, h, w, c.ci, c.co));
     }
@@ -390,7 +384,7 @@ static int train_create(int dim, int levels, int base, int cin, int ncls, int dt
       } else {
         pack_alloc(c.fwd, co, c.ci, n->taps, 0, pk);
         pack_alloc(c.dgr, co, c.ci, n->taps, 1, pk);
-        for (int k = 0; k < 4; ++k) n->ndesc += (c.fwd.buf[k] >= 0) + (c.dgr.buf[k] >= 0);
+        for (int k = 0; k < 2; ++k) n->ndesc += (c.fwd.buf[k] >= 0) + (c.dgr.buf[k] >= 0);
       }
       n->conv.push_back(c);
     }
@@ -485,8 +479,8 @@ int iunet_train_bind(iunet_train* n, void* flat, void* grad, void* m, void* v, v
     descs.push_back(d);
   };
   auto pack_descs = [&](const TPack& p, const float* w) {
-    for (int lay : {3, 1, 0})
-      if (p.buf[lay] >= 0) desc(w, n->packed + p.buf[lay], p.elems[lay], p.cout, p.cin, n->taps, lay == 3 ? 6 : lay == 1 ? 1 : 0, p.dg);
+    for (int k : {1, 0})                       // descriptor kinds 6 (compact K16), 1 (padded K16)
+      if (p.buf[k] >= 0) desc(w, n->packed + p.buf[k], p.elems[k], p.cout, p.cin, n->taps, k == 1 ? 6 : 1, p.dg);
   };
   for (const TConv& c : n->conv) {
     if (c.first) desc(n->flat + c.w, n->packed + c.first_pk, c.first_elems, c.co, c.ci, n->taps, 2, 0);
@@ -565,6 +559,7 @@ int iunet_train_forward_backward_hooks(iunet_train* n, const void* x, int in_dty
     } else {
       long long woff;
       const int lay = pack_pick(c.fwd, dim, N, d, h, w, x_act >= 0, false, &woff);
+      if (lay < 0) return lay;
       nparts = iunet_conv3_stats_parts(dim, N, d, h, w, c.co, lay);
       if (n->norm == 1 && x_act < 0 && n->gn_conv_stats) gn_rows = iunet_conv3_sample_stats_rows(dt, dim, N, d, h, w, c.ci, c.co, lay);
       if (gn_rows > 0) rc = iunet_conv3_fwd_sample_stats(dt, dim, xp, x_ss, y, c.co * v, K + woff, F(L.stats), N, d, h, w, c.ci, c.co, lay, stream);
@@ -598,7 +593,12 @@ int iunet_train_forward_backward_hooks(iunet_train* n, const void* x, int in_dty
   };
   // input of a stage's second conv: conv1's raw output with its BatchNorm + ReLU applied by the consumers' loader waves, or the
   // materialised activation (train_engine.TrainEngine._conv2_input)
-  auto conv2_fused = [&](int l) { return n->fuse_act && (dim == 3 || n->ch[l] <= 64); };
+  auto conv2_fused = [&](int l) {
+    int d, h, w, fused = 0;
+    dims(l, d, h, w);
+    if (n->fuse_act && iunet_conv3_plan(dim, N, d, h, w, n->ch[l], n->ch[l], 1, 0, 0, &fused) < 0) return false;      // (refused: the conv launches will say why)
+    return fused != 0;
+  };
 
   if (n->nested) {
     // ---- U-Net++ forward (train_engine_nested.NestedTrainEngine.forward_train): the encoder writes X^{l,0} into slot 0 of its level
@@ -772,16 +772,17 @@ int iunet_train_forward_backward_hooks(iunet_train* n, const void* x, int in_dty
                                     c.co, stream);
     if (rc) return rc;
     long long woff;
-    const int lay = pack_pick(c.dgr, dim, N, d, h, w, false, feeds >= 0 && (n->fuse_bw || n->gn_bw), &woff);      // (GroupNorm: the per-sample form of the fused sums)
-    // (pack_pick keeps the request for the fused sums only where the launch has them: layout 2, or the compact operator in 2-D up to 64 channels)
-    if (feeds >= 0 && n->fuse_bw && (lay == 2 || (lay == 3 && iunet_conv3_compact_ok(dim, N, d, h, w, c.co, c.ci, 0, 1)))) {
+    int fused = 0;                               // the launch has the fused sums it asks for (GroupNorm: their per-sample form)
+    const int lay = pack_pick(c.dgr, dim, N, d, h, w, false, feeds >= 0 && (n->fuse_bw || n->gn_bw), &woff, &fused);
+    if (lay < 0) return lay;
+    if (fused && n->fuse_bw) {
       rc = iunet_conv3_dgrad_bnstats_lay(dt, dim, dy, c.co * v, dxp, dx_ss, K + woff, F(L.stats), WS + L.y[feeds], c.ci * v, F(L.mean[feeds]),
                                          F(L.invstd[feeds]), F(L.scale[feeds]), F(L.shift[feeds]), N, d, h, w, c.co, c.ci, lay, stream);
       bw_ready[feeds] = iunet_conv3_stats_parts(dim, N, d, h, w, c.ci, 2);
     } else {
       // GroupNorm: the same fusion per sample where the launch has that form (the parameters are [N][C] rows, the sums per sample)
       int gn_rows = 0;
-      if (n->norm == 1 && feeds >= 0 && n->gn_bw && (lay == 2 || (lay == 3 && dim == 2 && c.co <= 64)))
+      if (n->norm == 1 && fused && n->gn_bw)
         gn_rows = iunet_conv3_sample_stats_rows(dt, dim, N, d, h, w, c.co, c.ci, lay);
       if (gn_rows > 0) {
         rc = iunet_conv3_dgrad_sample_bnstats(dt, dim, dy, c.co * v, dxp, dx_ss, K + woff, F(L.stats), WS + L.y[feeds], c.ci * v, F(L.mean[feeds]),

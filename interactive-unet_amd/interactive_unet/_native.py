@@ -33,6 +33,8 @@ _SIGS = {
     'iunet_conv3_pick_layout': [c_int] * 7,
     'iunet_conv3_tile_pairs': [c_int] * 7,
     'iunet_conv3_compact_ok': [c_int] * 9,
+    'iunet_conv3_packs_compact': [c_int] * 2,
+    'iunet_conv3_plan': [c_int] * 10 + [_IP],
     'iunet_conv3_fwd_act': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     'iunet_first_conv_fwd': [c_int, c_int, c_void_p, c_int, ctypes.POINTER(c_ll), c_void_p, c_ll, c_void_p, c_void_p,
@@ -331,11 +333,18 @@ def check(status):
         raise NativeError(f'libiunet error {status}: {lib().iunet_last_error().decode()}')
 
 
+def answer(value):
+    """A non-negative answer of the library as it is; NativeError where it refused the arguments (negative)."""
+    if value < 0:
+        check(value)
+    return value
+
+
 def call(name, *args):
     check(getattr(lib(), name)(*args))
 
 
-def pack_conv3_elems(cout, cin, taps, mode=0):
+def pack_conv3_elems(cout, cin, taps, mode):
     return int(lib().iunet_pack_conv3_elems(cout, cin, taps, mode))
 
 
@@ -348,6 +357,8 @@ class PackDesc(ctypes.Structure):
 
 
 def make_desc(w, dst, cout, cin, taps, kind, dtype, dgrad=0, bn=None, bias_out=None, eps=1e-5, qscale=None):
+    if kind not in range(1, 7):
+        raise NativeError(f'pack descriptor kind {kind}: the kinds are 1 .. 6 (csrc/pack_desc.h)')
     d = PackDesc()
     d.w, d.dst, d.total = w.data_ptr(), dst.data_ptr(), dst.numel()
     d.Cout, d.Cin, d.taps, d.kind, d.dgrad, d.dtype, d.eps = cout, cin, taps, kind, int(dgrad), DTYPE_CODE[dtype], eps
@@ -412,52 +423,42 @@ class X2PrepTable:
 
 
 class PackedConv:
-    """A stage conv's weights in the fragment order(s) its launches may need: layout 1 (K16, the
-    LDS-fed Cout-32 structure) always, layout 0 also when Cout is a multiple of 64.  `dgrad`: the
-    data-gradient operator (roles of cin / cout swapped)."""
+    """A stage conv's weights in the fragment orders its launches may need: the padded K16 order (layout 2) always, the compact one
+    (layout 3) where iunet_conv3_packs_compact says a launch can use it.  `dgrad`: the data-gradient operator (roles of cin / cout
+    swapped).  The only place on the Python side that knows which operators are packed and which launch gets which (the rules
+    themselves: csrc/capi.hip, iunet_conv3_plan)."""
+    MODE = {2: 2, 3: 6}          # layout -> iunet_pack_conv3 mode
+    KIND = {2: 1, 3: 6}          # layout -> iunet_pack_batch descriptor kind
 
     def __init__(self, cout, cin, taps, dtype, device, dgrad=False):
         self.cout, self.cin, self.taps, self.dg = cout, cin, taps, int(bool(dgrad))
-        self.out_ch = cin if dgrad else cout
+        self.out_ch, self.in_ch = (cin, cout) if dgrad else (cout, cin)
         self.dt = DTYPE_CODE[dtype]
-        self.buf = {1: torch.empty(pack_conv3_elems(cout, cin, taps, 2 | self.dg), dtype=dtype, device=device)}
-        # layout 0 is only ever picked for 2-D launches with more than 64 input channels (iunet_conv3_pick_layout: every 3-D conv
-        # and the narrow 2-D ones run on the K16 operator): packing it for the others was half of the per-step pack work
-        in_ch = cout if dgrad else cin
-        # layout 3: the compact K16 order (the padding-free step of conv3_v4.hip: 3^3 filters with streamed weights, every 3^2 filter)
-        # beside the padded one, which the launches that do not qualify keep using (fused BatchNorm-backward sums)
-        compact2d = taps == 9 and not os.environ.get('IUNET_NO_COMPACT2D')
-        if self.out_ch % 64 == 0 and taps == 9 and in_ch > 64 and not compact2d:
-            self.buf[0] = torch.empty(pack_conv3_elems(cout, cin, taps, self.dg), dtype=dtype, device=device)
-        if ((taps == 27 and in_ch > 32) or compact2d) and not os.environ.get('IUNET_NO_COMPACT'):
-            self.buf[3] = torch.empty(pack_conv3_elems(cout, cin, taps, 6 | self.dg), dtype=dtype, device=device)
+        lays = (2, 3) if answer(lib().iunet_conv3_packs_compact(taps, self.in_ch)) else (2,)
+        self.buf = {lay: torch.empty(pack_conv3_elems(cout, cin, taps, self.MODE[lay] | self.dg), dtype=dtype, device=device) for lay in lays}
+        self._plans = {}
 
     def pack(self, w, scale=None):
         for lay, b in self.buf.items():
-            call('iunet_pack_conv3', self.dt, ptr(w), ptr(scale), ptr(b), self.cout, self.cin, self.taps,
-                 (6 if lay == 3 else 2 if lay == 1 else 0) | self.dg, stream())
+            call('iunet_pack_conv3', self.dt, ptr(w), ptr(scale), ptr(b), self.cout, self.cin, self.taps, self.MODE[lay] | self.dg, stream())
 
     def descs(self, w, bn=None, bias_out=None, eps=1e-5, qscale=None):
         """Descriptors of all layouts for iunet_pack_batch (the first one also writes the folded bias)."""
-        out = []
-        for k, (lay, b) in enumerate(sorted(self.buf.items(), reverse=True)):
-            out.append(make_desc(w, b, self.cout, self.cin, self.taps, 6 if lay == 3 else 1 if lay == 1 else 0, b.dtype, self.dg, bn,
-                                 bias_out if k == 0 else None, eps, qscale))
-        return out
+        return [make_desc(w, b, self.cout, self.cin, self.taps, self.KIND[lay], b.dtype, self.dg, bn, bias_out if k == 0 else None, eps, qscale)
+                for k, (lay, b) in enumerate(sorted(self.buf.items(), reverse=True))]
 
     def pick(self, nd, N, D, H, W, act=False, bw=False):
-        """(layout, buffer) for a launch on this grid.  act: the launch applies a fused input activation (iunet_conv3_fwd_act);
-        bw: it accumulates the BatchNorm-backward sums (iunet_conv3_dgrad_bnstats)."""
-        in_ch = self.cout if self.dg else self.cin
-        lay = lib().iunet_conv3_pick_layout(nd, N, D, H, W, in_ch, self.out_ch)
-        # the fused sums exist where layout 2 is the grid's choice (and, in 2-D, on the compact operator of those launches): a launch that
-        # asks for them elsewhere (2-D, more than 64 input channels) runs plain, so it may as well run on the compact operator
-        bw = bool(bw) and lay == 2
-        if 3 in self.buf and lib().iunet_conv3_compact_ok(nd, N, D, H, W, in_ch, self.out_ch, int(bool(act)), int(bw)):
-            return 3, self.buf[3]
-        if lay == 0 and 0 not in self.buf:
-            lay = 1
-        return lay, self.buf[1 if lay == 2 else lay]      # layout 2 runs on the K16 operator of layout 1
+        """(layout, buffer, fused) of a launch on this grid.  act: the launch wants a fused input activation (iunet_conv3_fwd_act);
+        bw: it wants to accumulate the BatchNorm- / GroupNorm-backward sums (iunet_conv3_dgrad_bnstats_lay / _sample_bnstats).  fused:
+        the launch has what was asked for; False (where something was asked for): it runs plain, the caller applies the activation /
+        reduces the sums in a pass of its own."""
+        key = (nd, N, D, H, W, bool(act), bool(bw))
+        plan = self._plans.get(key)          # the answer depends on the key alone: a step asks the library once per shape, not per launch
+        if plan is None:
+            fused = c_int(0)
+            lay = answer(lib().iunet_conv3_plan(nd, N, D, H, W, self.in_ch, self.out_ch, int(key[5]), int(key[6]), int(3 in self.buf), ctypes.byref(fused)))
+            plan = self._plans[key] = (lay, self.buf[lay], bool(fused.value))
+        return plan
 
 
 def ptr(t):

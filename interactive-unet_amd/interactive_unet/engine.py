@@ -286,22 +286,20 @@ class Engine:
                         nv.IN_DTYPE_CODE[x.dtype], nv.ll_array(xs), nv.ptr(y), b * v, nv.ptr(pk), None, nv.ptr(st),
                         1, d[0], d[1], d[2], a, b, 0, s)
             elif j == 1:
-                lay, wpk = pk.pick(self.dim, 1, *d)
+                lay, wpk, _ = pk.pick(self.dim, 1, *d)
                 nparts = L.iunet_conv3_stats_parts(self.dim, 1, *d, b, lay)
                 nv.call('iunet_conv3_fwd', self.dt, self.dim, src, a * v, nv.ptr(y), b * v, nv.ptr(wpk), None, nv.ptr(st),
                         1, d[0], d[1], d[2], a, b, 0, lay, s)
             else:
                 scA, shA = ws['gnA'][0], ws['gnA'][1]
-                lay, wpk = pk.pick(self.dim, 1, *d, act=True)
-                if lay in (2, 3):            # conv1's GroupNorm + ReLU in this conv's loader waves
-                    nparts = L.iunet_conv3_stats_parts(self.dim, 1, *d, b, lay)
+                lay, wpk, fused = pk.pick(self.dim, 1, *d, act=True)
+                nparts = L.iunet_conv3_stats_parts(self.dim, 1, *d, b, lay)
+                if fused:                    # conv1's GroupNorm + ReLU in this conv's loader waves
                     nv.call('iunet_conv3_fwd_act', self.dt, self.dim, nv.ptr(ws['rawA']), a * v, nv.ptr(y), b * v, nv.ptr(wpk), None,
                             nv.ptr(st), nv.ptr(scA), nv.ptr(shA), 1, d[0], d[1], d[2], a, b, 0, lay, s)
-                else:                        # layouts without the fused input activation: materialise it (in place of the raw output)
+                else:                        # no fused input activation here: materialise it (in place of the raw output), plain launch
                     nv.call('iunet_bn_relu_fwd', self.dt, nv.ptr(ws['rawA']), a * v, nv.ptr(ws['rawA']), a * v, nv.ptr(scA), nv.ptr(shA),
                             a, 1, v, s)
-                    lay, wpk = pk.pick(self.dim, 1, *d)
-                    nparts = L.iunet_conv3_stats_parts(self.dim, 1, *d, b, lay)
                     nv.call('iunet_conv3_fwd', self.dt, self.dim, nv.ptr(ws['rawA']), a * v, nv.ptr(y), b * v, nv.ptr(wpk), None,
                             nv.ptr(st), 1, d[0], d[1], d[2], a, b, 0, lay, s)
             nv.call('iunet_gn_finalize', nv.ptr(st), nparts, b, self.groups, v, nv.ptr(gamma), nv.ptr(beta), BN_EPS,
@@ -344,7 +342,7 @@ class Engine:
     def _conv3(self, x_ptr, x_ss, y_ptr, y_ss, name, N, dims, ci, co, s, ws=None, xf=0, yf=0):
         pk, bias = self.packed[name][0], self.packed[name][1]
         if self.norm == 'group':
-            lay, wpk = pk.pick(self.dim, N, dims[0], dims[1], dims[2])
+            lay, wpk, _ = pk.pick(self.dim, N, dims[0], dims[1], dims[2])
             nv.call('iunet_conv3_fwd', self.dt, self.dim, x_ptr, x_ss, nv.ptr(ws['raw']), co * _vox(dims), nv.ptr(wpk), None, None,
                     N, dims[0], dims[1], dims[2], ci, co, 0, lay, s)
             self._group_norm(name, ws, y_ptr, y_ss, N, dims, co, s)
@@ -370,7 +368,7 @@ class Engine:
                     nv.ptr(bias), N, dims[0], dims[1], dims[2], ci, co, 2, nv.ptr(self._f8_ws) if need else None, s)
             return
         assert not (xf or yf)
-        lay, wpk = pk.pick(self.dim, N, dims[0], dims[1], dims[2])
+        lay, wpk, _ = pk.pick(self.dim, N, dims[0], dims[1], dims[2])
         nv.call('iunet_conv3_fwd', self.dt, self.dim, x_ptr, x_ss, y_ptr, y_ss, nv.ptr(wpk), nv.ptr(bias), None,
                 N, dims[0], dims[1], dims[2], ci, co, 2, lay, s)
 

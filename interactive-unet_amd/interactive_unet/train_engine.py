@@ -53,7 +53,7 @@ class TrainEngine:
                 int(self.dynamic_scale), nv.stream())
         self.pg = process_group
         # the BatchNorm + ReLU between the two convs of a stage is applied by the consumers while they stage their input
-        # wherever the second conv runs on layout 2 (3-D: always; 2-D: up to 64 channels) -- see _conv2_input
+        # wherever the second conv has that fusion (PackedConv.pick: 3-D always, 2-D up to 64 channels) -- see _conv2_input
         # (IUNET_NO_ACT_FUSION=1: materialise it, for A/B runs)
         self.fuse_act = not os.environ.get('IUNET_NO_ACT_FUSION')
         # GroupNorm variant: statistics per (sample, group) -- the per-channel fusions of the BatchNorm path (activation applied in
@@ -245,7 +245,7 @@ class TrainEngine:
                     max_stats = max(max_stats, lib.iunet_conv3_num_tiles(self.dim, N, *d) * b * 2)
                     max_wslab = max(max_wslab, lib.iunet_first_conv_wgrad_blocks(self.dim, N, *d) * b * 112)
                 else:
-                    max_stats = max(max_stats, max(lib.iunet_conv3_stats_parts(self.dim, N, *d, b, lay) for lay in (0, 2)) * b * 2)
+                    max_stats = max(max_stats, max(lib.iunet_conv3_num_tiles(self.dim, N, *d), lib.iunet_conv3_stats_parts(self.dim, N, *d, b, 2)) * b * 2)
                     if self.gn:          # per-sample rows of the conv epilogue
                         max_stats = max(max_stats, max(lib.iunet_conv3_sample_stats_rows(self.dt, self.dim, N, *d, a, b, lay) for lay in (2, 3)) * N * b * 2)
                     max_wslab = max(max_wslab, lib.iunet_conv3_wgrad_slab_floats(self.dim, N, *d, a, b))
@@ -305,7 +305,7 @@ class TrainEngine:
                     self._P(y), co * v, nv.ptr(w), None, None if (self.gn and not gn_rows) else nv.ptr(stats), N, d[0], d[1], d[2], ci, co, 0, s)
         else:
             pk, _ = self.pk[name]
-            lay, w = pk.pick(self.dim, N, *d, act=x_act is not None)
+            lay, w, _ = pk.pick(self.dim, N, *d, act=x_act is not None)
             nparts = nv.lib().iunet_conv3_stats_parts(self.dim, N, *d, co, lay)
             probe = self.probe if (self.probe is not None and self.probe['name'] == name) else None
             if probe is not None:
@@ -353,10 +353,10 @@ class TrainEngine:
                     nv.ptr(ws['shift.' + name]), co, N, v, s)
 
     def _conv2_input(self, ws, stage, l, N):
-        """(x_ptr, x_act, z1_ptr) of a stage's second conv.  Where that conv runs on layout 2, conv1's BatchNorm + ReLU output is never written --
+        """(x_ptr, x_act, z1_ptr) of a stage's second conv.  Where that conv has the fused input activation, conv1's BatchNorm + ReLU output is never written --
         conv2 and its weight gradient read conv1's raw output and apply scale / shift / ReLU in their loader waves
         (one tensor write and one read less per stage, and no bn_relu_fwd launch)."""
-        if self.fuse_act and (self.dim == 3 or self.ch[l] <= 64):
+        if self.fuse_act and self.pk[f'{stage}.conv2'][0].pick(self.dim, N, *ws['dims'][l], act=True)[2]:
             return self._P(ws[f'y.{stage}.conv1']), f'{stage}.conv1', None
         z1 = ws[f'z.{stage}.conv1']
         return self._P(z1), None, self._P(z1)
@@ -494,12 +494,12 @@ class TrainEngine:
                         nv.ptr(gw), 1.0, nv.ptr(ws['scale.' + x_act]), nv.ptr(ws['shift.' + x_act]),
                         N, d[0], d[1], d[2], ci, co, s)
             _, pkd = self.pk[name]
-            lay, wd = pkd.pick(self.dim, N, *d, bw=feeds is not None and (self.fuse_bw or self.gn_bw))      # (GroupNorm: the per-sample form of the fused sums)
+            # fused: the launch has the fused sums it asks for (GroupNorm: their per-sample form)
+            lay, wd, fused = pkd.pick(self.dim, N, *d, bw=feeds is not None and (self.fuse_bw or self.gn_bw))
             gn_rows = 0
-            if self.gn and feeds is not None and self.gn_bw and (lay == 2 or (lay == 3 and self.dim == 2 and co <= 64)):
+            if self.gn and fused and self.gn_bw:
                 gn_rows = nv.lib().iunet_conv3_sample_stats_rows(self.dt, self.dim, N, d[0], d[1], d[2], co, ci, lay)
-            # (pick keeps the request for the fused sums only where the launch has them: layout 2, or the compact operator in 2-D up to 64 channels)
-            if feeds is not None and self.fuse_bw and (lay == 2 or (lay == 3 and nv.lib().iunet_conv3_compact_ok(self.dim, N, d[0], d[1], d[2], co, ci, 0, 1))):
+            if fused and self.fuse_bw:
                 nv.call('iunet_conv3_dgrad_bnstats_lay', self.dt, self.dim, self._P(dy), co * v, dx_ptr, dx_ss, nv.ptr(wd),
                         nv.ptr(ws['stats']), self._P(ws['y.' + feeds]), ci * v, nv.ptr(ws['mean.' + feeds]),
                         nv.ptr(ws['invstd.' + feeds]), nv.ptr(ws['scale.' + feeds]), nv.ptr(ws['shift.' + feeds]),
@@ -852,7 +852,7 @@ class EncoderTrainEngine(TrainEngine):
                     mx['stats'] = max(mx['stats'], lib.iunet_conv3_num_tiles(self.dim, N, *d) * b * 2)
                     mx['wslab'] = max(mx['wslab'], lib.iunet_first_conv_wgrad_blocks(self.dim, N, *d) * b * 112)
                 else:
-                    mx['stats'] = max(mx['stats'], max(lib.iunet_conv3_stats_parts(self.dim, N, *d, b, lay) for lay in (0, 2)) * b * 2)
+                    mx['stats'] = max(mx['stats'], max(lib.iunet_conv3_num_tiles(self.dim, N, *d), lib.iunet_conv3_stats_parts(self.dim, N, *d, b, 2)) * b * 2)
                     mx['wslab'] = max(mx['wslab'], lib.iunet_conv3_wgrad_slab_floats(self.dim, N, *d, a, b))
             ws[f'x{l}'] = self._act(N, ch[l], v)                      # X^l
             if self.skip_grad:

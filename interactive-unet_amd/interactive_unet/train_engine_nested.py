@@ -90,7 +90,7 @@ class NestedTrainEngine(TrainEngine):
                     max_stats = max(max_stats, lib.iunet_conv3_num_tiles(self.dim, N, *d) * b * 2)
                     max_wslab = max(max_wslab, lib.iunet_first_conv_wgrad_blocks(self.dim, N, *d) * b * 112)
                 else:
-                    max_stats = max(max_stats, max(lib.iunet_conv3_stats_parts(self.dim, N, *d, b, lay) for lay in (0, 2)) * b * 2)
+                    max_stats = max(max_stats, max(lib.iunet_conv3_num_tiles(self.dim, N, *d), lib.iunet_conv3_stats_parts(self.dim, N, *d, b, 2)) * b * 2)
                     max_wslab = max(max_wslab, lib.iunet_conv3_wgrad_slab_floats(self.dim, N, *d, a, b))
                 max_bn = max(max_bn, lib.iunet_bn_bwd_num_parts(N, v) * b * 2)
         for l in range(L):

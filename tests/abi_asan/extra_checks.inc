@@ -12,6 +12,18 @@ static int extra_checks() {
   EXPECT(iunet_conv3_fwd(0, 3, buf, 0, buf, 0, buf, nullptr, nullptr, 1, 0, 4, 4, 32, 32, 2, 0, nullptr) < 0);
   EXPECT(iunet_conv3_fwd(0, 3, buf, 0, buf, 0, buf, nullptr, nullptr, 1, 4, 4, 4, 32, 32, 5, 0, nullptr) < 0 && std::strstr(iunet_last_error(), "epilogue"));
   EXPECT(iunet_conv3_fwd(0, 3, buf, 0, buf, 0, buf, nullptr, nullptr, 1, 4, 4, 4, 32, 32, 2, 9, nullptr) < 0 && std::strstr(iunet_last_error(), "layout"));
+  // the retired kernel structures: layouts 0 / 1 and the pack modes without the K16 bit are refused with otherwise valid arguments
+  EXPECT(iunet_conv3_fwd(0, 3, buf, 0, buf, 0, buf, nullptr, nullptr, 1, 4, 4, 4, 32, 32, 0, 0, nullptr) < 0 && std::strstr(iunet_last_error(), "layout"));
+  EXPECT(iunet_conv3_fwd(0, 3, buf, 0, buf, 0, buf, nullptr, nullptr, 1, 4, 4, 4, 32, 32, 0, 1, nullptr) < 0 && std::strstr(iunet_last_error(), "layout"));
+  EXPECT(iunet_pack_conv3(0, buf, nullptr, buf, 32, 32, 9, 0, nullptr) < 0 && std::strstr(iunet_last_error(), "mode"));
+  EXPECT(iunet_pack_conv3_elems(32, 32, 9, 1) < 0 && std::strstr(iunet_last_error(), "mode") && iunet_pack_conv3_elems(32, 32, 9, 6) == 32 * 32 * 9);
+  // the launch policy (host arithmetic): a fusion exists iff nd == 3 or Cin <= 64; the compact operator where it was packed and qualifies
+  { int f = -1;
+    EXPECT(iunet_conv3_pick_layout(2, 1, 1, 64, 64, 128, 128) == 2 && iunet_conv3_packs_compact(9, 256) == 1 && iunet_conv3_packs_compact(27, 32) == 0);
+    EXPECT(iunet_conv3_plan(2, 1, 1, 64, 64, 128, 64, 0, 1, 1, &f) == 3 && f == 0);     // 2-D, more than 64 input channels: plain on layout 3
+    EXPECT(iunet_conv3_plan(2, 1, 1, 64, 64, 64, 64, 0, 1, 1, &f) == 3 && f == 1);
+    EXPECT(iunet_conv3_plan(3, 1, 8, 8, 16, 64, 64, 0, 1, 1, &f) == 2 && f == 1);       // 3-D: the fused sums on the padded operator
+    EXPECT(iunet_conv3_plan(3, 1, 8, 8, 16, 64, 64, 1, 0, 1, &f) == 3 && f == 1 && iunet_conv3_plan(3, 1, 8, 8, 16, 64, 64, 0, 0, 0, nullptr) == 2); }
   EXPECT(iunet_first_conv_fwd(0, 2, buf, 9, st, buf, 0, buf, nullptr, nullptr, 1, 1, 8, 8, 1, 32, 1, nullptr) < 0);
   EXPECT(iunet_first_conv_fwd(0, 2, buf, 0, st, buf, 0, buf, nullptr, nullptr, 1, 3, 8, 8, 1, 32, 1, nullptr) < 0);       // 2-D needs D == 1
   EXPECT(iunet_maxpool_fwd(0, 2, buf, 0, buf, 0, 12, 1, 1, 4, 4, nullptr) < 0);                                        // C % 8

@@ -37,6 +37,13 @@ def test_error_reporting_without_gpu():
     assert rc < 0 and b'dtype' in l.iunet_last_error()
     with pytest.raises(nv.NativeError):
         nv.check(rc)
+    # the retired kernel structures are refused by name, after the checks above and before any launch
+    buf = (nv.c_int * 16)()
+    for lay in (0, 1):
+        rc = l.iunet_conv3_fwd(0, 3, buf, 0, buf, 0, buf, None, None, 1, 4, 4, 4, 32, 32, 0, lay, None)
+        assert rc < 0 and b'layout' in l.iunet_last_error(), lay
+    rc = l.iunet_pack_conv3(0, buf, None, buf, 32, 32, 9, 0, None)
+    assert rc < 0 and b'mode' in l.iunet_last_error()
 
 
 def test_zoom_table_host_function_matches_oracle():

@@ -1,6 +1,5 @@
 """Parity of the native training kernels and of a whole optimisation step against torch
 CPU autograd on the oracle network and the reference-pinned loss oracle."""
-import os
 
 import numpy as np
 import pytest
@@ -453,8 +452,6 @@ def test_conv3_fwd_and_wgrad_with_fused_input_activation(nv, nd, cin, big, lay):
     z = torch.empty_like(yb)
     nv.call('iunet_bn_relu_fwd', dt, nv.ptr(yb), cin * vox, nv.ptr(z), cin * vox, nv.ptr(scale), nv.ptr(shift), cin, N, vox, s)
     pm = 6 if lay == 3 else 2
-    if lay == 3 and os.environ.get('IUNET_NO_COMPACT2D'):
-        pytest.skip('A/B switch IUNET_NO_COMPACT2D: no layout 3 in 2-D')
     assert lay == 2 or nv.lib().iunet_conv3_compact_ok(nd, N, D, H, W, cin, cout, 1, 0) == 1
     wpk = torch.empty(nv.pack_conv3_elems(cout, cin, taps, pm), dtype=T, device='cuda')
     nv.call('iunet_pack_conv3', dt, nv.ptr(w), None, nv.ptr(wpk), cout, cin, taps, pm, s)
@@ -502,8 +499,6 @@ def test_dgrad_with_fused_batchnorm_backward_sums(nv, nd, cin, lay):
     shape = (6, 12, 20) if nd == 3 else (40, 72)
     D, H, W = shape if nd == 3 else (1,) + shape
     taps, vox = 3 ** nd, D * H * W
-    if lay == 3 and (os.environ.get('IUNET_NO_COMPACT2D') or os.environ.get('IUNET_NO_COMPACT2D_BW')):
-        pytest.skip('A/B switch: no fused sums on layout 3')
     assert nv.lib().iunet_conv3_compact_ok(nd, N, D, H, W, cin, cout, 0, 1) == int(nd == 2)
     assert nv.lib().iunet_conv3_compact_ok(2, N, 1, H, W, 128, cout, 0, 1) == 0          # beyond 64 channels: the plain compact launch
     dy = torch.randn((N, cin) + shape, generator=g)

@@ -21,7 +21,7 @@ def main():
     ap.add_argument('--wgrad', type=int, default=1)
     ap.add_argument('--only', default='', help='e.g. 0:64:32 = level:cin:cout')
     ap.add_argument('--iters', type=int, default=10)
-    ap.add_argument('--layout', type=int, default=-1, help='-1 = library policy, 0 / 1 / 2 / 3 = force a kernel structure (3: compact operator, padding-free step)')
+    ap.add_argument('--layout', type=int, default=-1, help='-1 = library policy, 2 / 3 = force the padded K16 operator / the compact one (padding-free step)')
     ap.add_argument('--base', type=int, default=32, help='channels at level 0 (64: the C5 network)')
     ap.add_argument('--levels', type=int, default=4)
     ap.add_argument('--f8', type=int, default=0, help='1: also time the fp8 matrix-core kernel (conv3_f8.hip / conv3_f8k.hip) on each shape; 2: with e4m3 activation planes in and out (3-D, the engine\'s format between fp8 convs)')
@@ -49,11 +49,9 @@ def main():
         w = torch.randn(cout, cin, *([3] * nd), device='cuda') * 0.05
         if a.layout >= 0:
             lay = a.layout
-        elif nv.lib().iunet_conv3_compact_ok(nd, a.n, D, S, S, cin, cout, 0, 0):
-            lay = 3                                    # what PackedConv.pick chooses for a plain launch (compact operator)
-        else:
-            lay = nv.lib().iunet_conv3_pick_layout(nd, a.n, D, S, S, cin, cout)
-        pm = 6 if lay == 3 else 2 * (lay > 0)            # layout 3: the compact K16 order (pack mode bit 2)
+        else:                                          # what PackedConv.pick chooses for a plain launch
+            lay = nv.answer(nv.lib().iunet_conv3_plan(nd, a.n, D, S, S, cin, cout, 0, 0, nv.answer(nv.lib().iunet_conv3_packs_compact(taps, cin)), None))
+        pm = 6 if lay == 3 else 2                        # layout 3: the compact K16 order (pack mode bit 2)
         wpk = torch.empty(nv.pack_conv3_elems(cout, cin, taps, pm), dtype=T, device='cuda')
         bias = torch.zeros(cout, device='cuda')
         nv.call('iunet_pack_conv3', dt, nv.ptr(w), None, nv.ptr(wpk), cout, cin, taps, pm, nv.stream())
