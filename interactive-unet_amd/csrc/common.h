@@ -11,6 +11,7 @@
 #include <stdint.h>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 typedef _Float16 f16;
 typedef __bf16 bf16;
@@ -54,6 +55,53 @@ __device__ __forceinline__ V8T<T> bn_relu8(V8T<T> v, const float* sc, const floa
 #pragma unroll
   for (int j = 0; j < 8; ++j) o[j] = bn_relu1<T>(v[j], sc, sh, c0 + j);
   return o;
+}
+
+// ---- backward of z = relu(norm(y)), per element: the rounding contract of the bit-for-bit tests, written once.  Used by the
+// norm_bwd_* / norm_pool_bwd kernels and the head_bn_* kernels (train_pointwise.hip) and the BW epilogue of conv3_v4_kernel
+// (conv3_v4.hip); first_wgrad_kernel's loader (train_misc.hip) sits at its register cap and keeps the same arithmetic written out.
+template <typename T> __device__ __forceinline__ float rounded(float v) { return to_f32<T>(from_f32<T>(v)); }
+// the stored activation round_T(scale * y + shift), and the same as fp32 (RELU: clamped first -- the value bn_relu1 stores; the mask z > 0 does not
+// need the clamp)
+template <typename T, bool RELU = false>
+__device__ __forceinline__ T norm_z_stored(float sc, float yv, float sh) {
+  const float a = fmaf(sc, yv, sh);
+  return from_f32<T>(RELU ? fmaxf(a, 0.f) : a);
+}
+template <typename T, bool RELU = false>
+__device__ __forceinline__ float norm_z(float sc, float yv, float sh) { return to_f32<T>(norm_z_stored<T, RELU>(sc, yv, sh)); }
+// the masked gradient dz' = dz where the ReLU passed, and xhat
+__device__ __forceinline__ float norm_masked(float zv, float dz) { return zv > 0.f ? dz : 0.f; }
+__device__ __forceinline__ float norm_xhat(float yv, float mu, float is) { return (yv - mu) * is; }
+// pass 1: s1 += dz', s2 += dz' xhat associated as (dz' (y - mean)) invstd.  (The pool form adds dz' * xhat with xhat rounded first: its sums
+// have always differed from the three-kernel sequence's in the last bits, and both are kept as they are.)
+__device__ __forceinline__ void norm_bwd_sums(float d, float yv, float mu, float is, float& s1, float& s2) {
+  s1 += d;
+  s2 += d * (yv - mu) * is;
+}
+// pass 2: dy = a (dz' - c1 - xhat c2) with the coefficients of bn_bwd_finalize_kernel; GN: a dz' - c1 - xhat c2 with those of
+// gn_bwd_finalize_kernel (a group's statistics depend on every channel of it, so a channel with gamma = 0 still has a gradient)
+template <bool GN>
+__device__ __forceinline__ float norm_bwd_dy(float a, float d, float c1, float xh, float c2) {
+  return GN ? a * d - c1 - xh * c2 : a * (d - c1 - xh * c2);
+}
+
+// ---- launch dispatch: returns f(T(), integral_constant<int, nd>(), bool_constant<flag>()) for dtype 0 (f16) / 1 (bf16) (/ 2 (float)
+// where WITH_F32), nd 2 / 3 and one boolean template flag; the caller has checked dtype and nd
+template <bool WITH_F32 = false, typename F>
+inline auto iunet_dispatch(int dtype, int nd, bool flag, F&& f) {
+  auto with_t = [&](auto t) {
+    auto with_nd = [&](auto ndc) {
+      if (flag) return f(t, ndc, std::true_type());
+      return f(t, ndc, std::false_type());
+    };
+    if (nd == 3) return with_nd(std::integral_constant<int, 3>());
+    return with_nd(std::integral_constant<int, 2>());
+  };
+  if (dtype == 0) return with_t(f16());
+  if constexpr (WITH_F32)
+    if (dtype == 2) return with_t(float());
+  return with_t(bf16());
 }
 
 // Eval-mode BatchNorm folded into an operator: row c is scaled by bn_fold_scale, the bias is bn_fold_bias of that scale

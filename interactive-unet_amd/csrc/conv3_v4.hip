@@ -84,7 +84,7 @@ struct ConvV4Params {
   int dbg;                                    // profiling only (IUNET_V4_DBG): 2 no MFMA phase, 4 no stores, 64 halo tiles through registers always
   // Data-gradient launches: this launch's output IS the gradient dz of the producer layer's activation z = relu(bn(yp)).  With
   // bw_y set, the epilogue also reads yp at its output voxels and accumulates the BatchNorm-backward sums of that layer --
-  // s1 = sum dz', s2 = sum dz' * xhat, dz' = dz where z > 0 (the arithmetic of bn_bwd_reduce_kernel on the STORED, rounded dz)
+  // s1 = sum dz', s2 = sum dz' * xhat, dz' = dz where z > 0 (the arithmetic of norm_bwd_reduce_kernel, common.h: norm_bwd_sums, on the STORED, rounded dz)
   // -- into `stats` ([workgroups][Cout][2], as the forward statistics): the separate reduction pass over dz and yp goes away.
   const void* bw_y; long long bw_y_ss;
   const float* bw_mean; const float* bw_invstd; const float* bw_scale; const float* bw_shift;      // [Cout] of the producer layer
@@ -666,10 +666,8 @@ __global__ __launch_bounds__((V4Tile<ND, SMALL>::NCW * 64 + v4_loader_threads(ND
             const float mu = j < 4 ? m0[j & 3] : m1[j & 3], is = j < 4 ? i0[j & 3] : i1[j & 3];
             const float sc = j < 4 ? c0[j & 3] : c1[j & 3], sh = j < 4 ? h0[j & 3] : h1[j & 3];
             const float yy = to_f32<T>(bw_yv[n][j]);
-            const float zz = to_f32<T>(from_f32<T>(fmaf(sc, yy, sh)));       // the stored activation (bn_bwd_reduce_kernel)
-            const float d = zz > 0.f ? to_f32<T>(o[j]) : 0.f;                // the stored gradient
-            s_sum[j] += d;
-            s_sq[j] += d * (yy - mu) * is;
+            // (the stored activation masks the stored gradient: norm_bwd_reduce_kernel's arithmetic)
+            norm_bwd_sums(norm_masked(norm_z<T>(sc, yy, sh), to_f32<T>(o[j])), yy, mu, is, s_sum[j], s_sq[j]);
           }
         }
         if (ok && !(p.dbg & 4)) *(V8*)(yout + (long long)(cob * 4 + q) * plane_stride + (((long long)gz * p.H + gy) * p.W + gx) * 8) = o;

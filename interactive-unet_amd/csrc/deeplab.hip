@@ -620,7 +620,7 @@ int iunet_dl_conv_fwd(int dtype, int nd, const void* x, long long x_ss, void* y,
   p.cols = (long long)N * D * H * W; p.epi = epi;
   g.lda = Kw; g.psb = (const float*)psb; g.psb_scale = psb_scale;
   const dim3 grid(dl_fwd_blocks(N, D, H, W, Cout), (Cout + GG_COG - 1) / GG_COG);
-  gg_dispatch(dtype, nd, in_scale != nullptr, [&](auto t, auto, auto act) {
+  iunet_dispatch(dtype, nd, in_scale != nullptr, [&](auto t, auto, auto act) {
     hipLaunchKernelGGL((gg_fwd_kernel<decltype(t), act.value, DlFwdGather>), grid, dim3(256), 0, (hipStream_t)stream, p, g);
   });
   IUNET_CHECK_HIP(hipGetLastError());
@@ -658,7 +658,7 @@ int iunet_dl_wgrad(int dtype, int nd, int rate, const void* x, long long x_ss, i
   const long long nchunks = (p.cols + 31) / 32;
   p.chunks_per_split = (nchunks + splits - 1) / splits;
   const dim3 grid(splits, (Cout + 63) / 64, (p.K + 63) / 64);
-  gg_dispatch(dtype, nd, x_scale != nullptr, [&](auto t, auto, auto act) {
+  iunet_dispatch(dtype, nd, x_scale != nullptr, [&](auto t, auto, auto act) {
     hipLaunchKernelGGL((gg_wgrad_kernel<decltype(t), act.value, DlWgGather>), grid, dim3(256), 0, (hipStream_t)stream, p, g);
   });
   IUNET_CHECK_HIP(hipGetLastError());

@@ -17,8 +17,6 @@
 //   lane(k_l, k_ok)                           what is invariant per thread for its 8 operator columns k_l .. k_l + 7
 //   column<T, ACT>(lane, n, r, D, H, W)       the 8 gathered B values of column (n, r)
 #pragma once
-#include <type_traits>
-
 #include "common.h"
 
 namespace {
@@ -285,24 +283,6 @@ inline int gg_wgrad_splits(long long cols, long long per_split_floats) {
   if (s < 1) s = 1;
   while (s > 1 && s * per_split_floats > (8ll << 20)) s >>= 1;
   return (int)s;
-}
-
-// ---- launch dispatch: returns f(T(), integral_constant<int, nd>(), bool_constant<act>()) for dtype 0 (f16) / 1 (bf16) (/ 2 (float) where
-// WITH_F32), nd 2 / 3, act; the caller has checked dtype and nd
-template <bool WITH_F32 = false, typename F>
-inline auto gg_dispatch(int dtype, int nd, bool act, F&& f) {
-  auto with_t = [&](auto t) {
-    auto with_nd = [&](auto ndc) {
-      if (act) return f(t, ndc, std::true_type());
-      return f(t, ndc, std::false_type());
-    };
-    if (nd == 3) return with_nd(std::integral_constant<int, 3>());
-    return with_nd(std::integral_constant<int, 2>());
-  };
-  if (dtype == 0) return with_t(f16());
-  if constexpr (WITH_F32)
-    if (dtype == 2) return with_t(float());
-  return with_t(bf16());
 }
 
 }  // namespace

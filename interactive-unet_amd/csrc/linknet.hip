@@ -342,7 +342,7 @@ int iunet_lk_conv_fwd(int dtype, int nd, int kind, const void* x, long long x_ss
   p.cols = (long long)N * D * H * W; p.epi = epi;
   const LkData g{(int)lk_kpad(p.K), skip, skip_ss};
   const dim3 grid(lk_fwd_blocks(nd, kind, N, D, H, W, Cout), (Cout + GG_COG - 1) / GG_COG, lk_classes(nd, kind));
-  gg_dispatch(dtype, nd, in_scale != nullptr, [&](auto t, auto ndc, auto act) {
+  iunet_dispatch(dtype, nd, in_scale != nullptr, [&](auto t, auto ndc, auto act) {
     auto launch = [&](auto pol) {
       hipLaunchKernelGGL((gg_fwd_kernel<decltype(t), act.value, decltype(pol)>), grid, dim3(256), 0, (hipStream_t)stream, p, pol);
     };
@@ -374,7 +374,7 @@ int iunet_lk_wgrad(int dtype, int nd, int kind, const void* x, long long x_ss, c
   p.K = lk_taps(nd, kind) * Cin; p.cols = (long long)N * D * H * W; p.kgroups = (p.K + 63) / 64;
   const int splits = lk_wgrad_splits(nd, kind, N, D, H, W, Cin, Cout), ncls = lk_classes(nd, kind);
   const dim3 grid(splits, (Cout / 16) * p.kgroups, ncls);
-  gg_dispatch(dtype, nd, x_scale != nullptr, [&](auto t, auto ndc, auto act) {
+  iunet_dispatch(dtype, nd, x_scale != nullptr, [&](auto t, auto ndc, auto act) {
     if (kind == 0) hipLaunchKernelGGL((lk_wgrad_kernel<decltype(t), ndc.value, 0, act.value>), grid, dim3(256), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((lk_wgrad_kernel<decltype(t), ndc.value, 1, act.value>), grid, dim3(256), 0, (hipStream_t)stream, p);
   });

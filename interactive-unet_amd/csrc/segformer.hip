@@ -542,7 +542,7 @@ int iunet_sf_gemm(int dtype, int nd, int nsrc, const void* const* x, const long 
   const dim3 grid((unsigned)iunet_sf_stats_parts(N, D, H, W));
   const size_t es = dtype == 2 ? 4 : 2, ld = dtype == 2 ? SF_LD32 : SF_LD16;
   const size_t lds = (size_t)(SF_COLS + Cout) * ld * es;
-  const int rl = gg_dispatch<true>(dtype, nd, act, [&](auto t, auto ndc, auto a) -> int {
+  const int rl = iunet_dispatch<true>(dtype, nd, act, [&](auto t, auto ndc, auto a) -> int {
     if (lds > 65536) IUNET_SET_MAX_LDS((sf_gemm_kernel<decltype(t), ndc.value, a.value>), (int)lds);
     hipLaunchKernelGGL((sf_gemm_kernel<decltype(t), ndc.value, a.value>), grid, dim3(256), lds, (hipStream_t)stream, p);
     return IUNET_OK;
@@ -578,7 +578,7 @@ int iunet_sf_wgrad(int dtype, int nd, int nsrc, const void* const* x, const long
   const long long nchunks = (p.cols + 31) / 32;
   p.chunks_per_split = (nchunks + splits - 1) / splits;
   const dim3 grid(splits, (Cout + 63) / 64, (p.K + 63) / 64);
-  gg_dispatch(dtype, nd, act, [&](auto t, auto ndc, auto a) {
+  iunet_dispatch(dtype, nd, act, [&](auto t, auto ndc, auto a) {
     hipLaunchKernelGGL((gg_wgrad_kernel<decltype(t), a.value, SfResample<ndc.value>>), grid, dim3(256), 0, (hipStream_t)stream, p,
                        SfResample<ndc.value>{src});
   });

@@ -389,7 +389,7 @@ struct FirstWgradParams {
   const void* x; long long sN, sC, sD, sH, sW; int in_dtype;
   const void* dy; long long dy_ss;
   // optional BatchNorm + ReLU backward applied while staging: `dy` is then the gradient of the activation (dz), `yraw` the
-  // conv's raw output, and the operand is a * (dz * mask - c1 - xhat * c2) rounded as bn_bwd_apply_kernel stores it
+  // conv's raw output, and the operand is a * (dz * mask - c1 - xhat * c2) rounded as norm_bwd_apply_kernel stores it (common.h: norm_bwd_dy)
   const void* yraw; long long y_ss;
   const float* mean; const float* invstd; const float* coef; const float* scale; const float* shift;
   float* slab;     // [nb][Cout][KKP]
@@ -498,7 +498,8 @@ __global__ __launch_bounds__(256, 2) void first_wgrad_kernel(FirstWgradParams p)
     for (int it = 0; it < YIT; ++it) {
       const int idx = tid + it * 256, pl = idx / NVOX, pix = idx - pl * NVOX;
       u32x4 v = yr[it];
-      if (p.yraw != nullptr && ((oky >> it) & 1u)) {      // dy = a * (dz * [z > 0] - c1 - xhat * c2) as bn_bwd_apply_kernel; outside the image: 0
+      if (p.yraw != nullptr && ((oky >> it) & 1u)) {      // dy as norm_bwd_apply_kernel stores it; outside the image: 0.  Written out here -- it mirrors
+                                                          // common.h's norm_z / norm_masked / norm_xhat / norm_bwd_dy<false>; through the helpers the 3-D forms spill 4-8 B more
         const V8 g = __builtin_bit_cast(V8, v), yy = __builtin_bit_cast(V8, yw[it]);
         V8 o;
         // the 7 per-channel constants of this plane's 8 channels: broadcast LDS reads (one global load per constant and

@@ -4,6 +4,7 @@
 // per-block partial slabs summed in a fixed order (deterministic, no float atomics).
 #include "common.h"
 #include "loss_terms.h"
+#include "../../include/iunet.h"
 
 namespace {
 
@@ -130,20 +131,78 @@ __global__ __launch_bounds__(256) void bn_relu_pool_fwd_kernel(const T* __restri
   *(V8T<T>*)(pooled + n * p_ss + (long long)pl * ovox * 8 + r * 8) = o;
 }
 
-// BN+ReLU backward, pass 1: per-channel s1 = sum(dyh), s2 = sum(dyh * xhat), dyh = dz * (z > 0).
-// grid (chunks, planes, N); slab [(n*chunks + chunk)][C][2]
+// ------------------------------------------------------------------ backward of z = relu(norm(y)): one kernel family
+// Two passes over y and the upstream gradient dz -- pass 1: per-channel s1 = sum dz', s2 = sum dz' xhat (dz' = dz where z > 0); a finalize
+// kernel (BatchNorm: bn_bwd_finalize_kernel, GroupNorm: gn_bwd_finalize_kernel); pass 2: dy -- or the same two passes with the max-pool
+// backward folded in.  Where dz comes from is a POLICY, template argument and by-value kernel parameter (as the gather of gg_fwd_kernel);
+// the arithmetic per element is common.h's norm_z / norm_masked / norm_xhat / norm_bwd_sums / norm_bwd_dy.  A policy has
+//   Held<T>, load<T>(n, off, h)   what a thread keeps of the 8 channels at element `off` of sample n while its loads are in flight
+//   at<T>(h, j)                   channel j of it in fp32
+//   ROUNDED                       at() is a value of T already.  Otherwise dz = round_T(at()), the value a materialised dz tensor would hold;
+//                                 the pool form adds the max-pool route to the UNROUNDED at() and rounds once, as maxpool_bwd_kernel stored it
+//   has_z(), load_z<T>(n, off)    the stored activation z, where there is one (otherwise the ReLU mask z > 0 is recomputed from y: one
+//                                 tensor read less per pass)
+// One gradient tensor (the pool form's dskip), with the optional stored z
+struct OneSrc {
+  static constexpr bool ROUNDED = true;
+  template <typename T> using Held = V8T<T>;
+  const void* dz; long long dz_ss;
+  const void* z; long long z_ss;      // z NULL: not stored
+  template <typename T> __device__ __forceinline__ void load(int n, long long off, V8T<T>& h) const { h = *(const V8T<T>*)((const T*)dz + n * dz_ss + off); }
+  template <typename T> static __device__ __forceinline__ float at(const V8T<T>& h, int j) { return to_f32<T>(h[j]); }
+  __device__ __forceinline__ bool has_z() const { return z != nullptr; }
+  template <typename T> __device__ __forceinline__ V8T<T> load_z(int n, long long off) const { return *(const V8T<T>*)((const T*)z + n * z_ss + off); }
+};
+
+// A sum of up to 8 tensors (U-Net++).  In the nested network a stage output feeds every later node of its level and the transposed conv
+// above it: its gradient is a sum of up to 8 NHWC8c tensors (slot slices of the consumers' data gradients).  The sum is formed in fp32 in
+// source order while the two passes read, rounded once to T, and never written.  With one source it gives the bits of OneSrc.
+struct SumSrcs {
+  static constexpr int MAX = 8;
+  static constexpr bool ROUNDED = false;
+  template <typename T> using Held = float[8];
+  const void* p[MAX];          // source k: sample n, element e at p[k] + n * ss[k] + e (in T elements)
+  long long ss[MAX];
+  int k;                       // 1 .. MAX
+  template <typename T> __device__ __forceinline__ void load(int n, long long off, float (&h)[8]) const;
+  template <typename T> static __device__ __forceinline__ float at(const float (&h)[8], int j) { return h[j]; }
+  static constexpr __device__ bool has_z() { return false; }
+  template <typename T> __device__ __forceinline__ V8T<T> load_z(int, long long) const { return V8T<T>{}; }      // (never reached)
+};
+
+// acc[j] = sum_k src_k[n * ss_k + off + j] in fp32, k in order
 template <typename T>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict__ dz, long long dz_ss,
-                                                            const T* __restrict__ z, long long z_ss,
-                                                            const T* __restrict__ y, long long y_ss,
-                                                            const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                            const float* __restrict__ scale, const float* __restrict__ shift,
-                                                            int C, long long vox, int per_block, float* __restrict__ slab,
-                                                            int pss = 0 /* per-sample stride of mean / invstd / scale / shift (GroupNorm: C) */) {
+__device__ __forceinline__ void sum_srcs(const SumSrcs& s, int n, long long off, float (&acc)[8]) {
+  const V8T<T> g0 = *(const V8T<T>*)((const T*)s.p[0] + n * s.ss[0] + off);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = to_f32<T>(g0[j]);
+#pragma unroll
+  for (int k = 1; k < SumSrcs::MAX; ++k) {
+    if (k >= s.k) break;
+    const V8T<T> g = *(const V8T<T>*)((const T*)s.p[k] + n * s.ss[k] + off);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] += to_f32<T>(g[j]);
+  }
+}
+template <typename T> __device__ __forceinline__ void SumSrcs::load(int n, long long off, float (&h)[8]) const { sum_srcs<T>(*this, n, off, h); }
+
+// dz of channel j as the non-pool passes take it: round_T of the policy's value (no conversion round trip where it is a T already)
+template <typename T, typename Src>
+__device__ __forceinline__ float src_dz(const typename Src::template Held<T>& h, int j) {
+  const float s = Src::template at<T>(h, j);
+  return Src::ROUNDED ? s : rounded<T>(s);
+}
+
+// pass 1.  grid (chunks, planes, N); slab [(n*chunks + chunk)][C][2]
+template <typename T, typename Src>
+__global__ __launch_bounds__(256) void norm_bwd_reduce_kernel(Src src, const T* __restrict__ y, long long y_ss,
+                                                              const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                              const float* __restrict__ scale, const float* __restrict__ shift,
+                                                              int C, long long vox, int per_block, float* __restrict__ slab,
+                                                              int pss /* per-sample stride of mean / invstd / scale / shift (GroupNorm: C; BatchNorm: 0) */) {
   const int pl = blockIdx.y, n = blockIdx.z;
   const long long v0 = (long long)blockIdx.x * per_block;
   const long long v1 = min(v0 + per_block, vox);
-  // the ReLU mask (z > 0) is recomputed from y when z is not given: one tensor read less per pass
   float s1[8], s2[8], mu[8], is[8], sc[8], sh[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
@@ -154,20 +213,17 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict_
   const long long po = (long long)pl * vox * 8;
 #pragma unroll 4
   for (long long v = v0 + threadIdx.x; v < v1; v += 256) {        // unrolled: 8 x 16 B in flight per thread
-    const V8T<T> g = *(const V8T<T>*)(dz + n * dz_ss + po + v * 8);
+    typename Src::template Held<T> g;
+    src.template load<T>(n, po + v * 8, g);
     const V8T<T> yy = *(const V8T<T>*)(y + n * y_ss + po + v * 8);
     V8T<T> zz;
-    if (z) zz = *(const V8T<T>*)(z + n * z_ss + po + v * 8);
+    if (src.has_z()) zz = src.template load_z<T>(n, po + v * 8);
     else {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) zz[j] = from_f32<T>(fmaf(sc[j], to_f32<T>(yy[j]), sh[j]));
+      for (int j = 0; j < 8; ++j) zz[j] = norm_z_stored<T>(sc[j], to_f32<T>(yy[j]), sh[j]);
     }
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float d = to_f32<T>(zz[j]) > 0.f ? to_f32<T>(g[j]) : 0.f;
-      s1[j] += d;
-      s2[j] += d * (to_f32<T>(yy[j]) - mu[j]) * is[j];
-    }
+    for (int j = 0; j < 8; ++j) norm_bwd_sums(norm_masked(to_f32<T>(zz[j]), src_dz<T, Src>(g, j)), to_f32<T>(yy[j]), mu[j], is[j], s1[j], s2[j]);
   }
   __shared__ float red[4 * 16];
   const long long part = (long long)n * gridDim.x + blockIdx.x;
@@ -177,20 +233,19 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict_
   block_reduce_store<16>(vals, red, slab + (part * C + pl * 8) * 2);
 }
 
-// BatchNorm + ReLU backward of an encoder stage's second conv with the max-pool backward folded in: the gradient of the
-// stage output is dz = dskip + route(dpool) (dskip = the decoder's gradient of the skip connection, route = to the first
-// maximum of each 2^d window of z = relu(bn(y)), recomputed from y) and is never written.  One thread per pooled voxel
-// and channel plane.  PASS 1: per-channel sums (as bn_bwd_reduce_kernel), PASS 2: dy (as bn_bwd_apply_kernel).
-// Every value is rounded where the three-kernel sequence maxpool_bwd -> reduce -> apply rounds it.
-template <typename T, int ND, int PASS, bool GN = false>
-__global__ __launch_bounds__(256) void bn_pool_bwd_kernel(const T* __restrict__ dskip, long long ds_ss,
-                                                          const T* __restrict__ dpool, long long dp_ss,
-                                                          const T* __restrict__ y, long long y_ss, T* __restrict__ dy,
-                                                          long long dy_ss, const float* __restrict__ mean,
-                                                          const float* __restrict__ invstd, const float* __restrict__ coef,
-                                                          const float* __restrict__ scale, const float* __restrict__ shift,
-                                                          int C, int Do, int Ho, int Wo, int per_block, float* __restrict__ slab,
-                                                          int pss = 0 /* per-sample stride of the per-channel parameters (GroupNorm: C) */) {
+// Both passes of an encoder stage's second conv with the max-pool backward folded in: the gradient of the stage output is
+// dz = src + route(dpool) (src = the decoder's gradient of the skip connection, route = to the first maximum of each 2^d window of
+// z = relu(norm(y)), recomputed from y) and is never written.  One thread per pooled voxel and channel plane.  PASS 1: the sums of
+// norm_bwd_reduce_kernel, PASS 2: the dy of norm_bwd_apply_kernel.  Every value is rounded where the three-kernel sequence
+// maxpool_bwd -> reduce -> apply rounds it.
+template <typename T, int ND, int PASS, typename Src, bool GN>
+__global__ __launch_bounds__(256) void norm_pool_bwd_kernel(Src src, const T* __restrict__ dpool, long long dp_ss,
+                                                            const T* __restrict__ y, long long y_ss, T* __restrict__ dy,
+                                                            long long dy_ss, const float* __restrict__ mean,
+                                                            const float* __restrict__ invstd, const float* __restrict__ coef,
+                                                            const float* __restrict__ scale, const float* __restrict__ shift,
+                                                            int C, int Do, int Ho, int Wo, int per_block, float* __restrict__ slab,
+                                                            int pss /* per-sample stride of the per-channel parameters (GroupNorm: C; BatchNorm: 0) */) {
   constexpr int NW = ND == 3 ? 8 : 4;
   const int pl = blockIdx.y, n = blockIdx.z;
   const long long ovox = (long long)Do * Ho * Wo;
@@ -206,7 +261,8 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_kernel(const T* __restrict__ 
   const long long r0 = (long long)blockIdx.x * per_block, r1 = min(r0 + per_block, ovox);
   for (long long r = r0 + threadIdx.x; r < r1; r += 256) {
     const int ox = (int)(r % Wo), oy = (int)((r / Wo) % Ho), oz = (int)(r / ((long long)Wo * Ho));
-    V8T<T> yy[NW], gs[NW];
+    V8T<T> yy[NW];
+    typename Src::template Held<T> gs[NW];
     long long off[NW];
 #pragma unroll
     for (int s = 0; s < NW; ++s) {
@@ -214,7 +270,7 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_kernel(const T* __restrict__ 
       const int zz = ND == 3 ? oz * 2 + a : 0;
       off[s] = ipl + (((long long)zz * Hi + oy * 2 + b) * Wi + ox * 2 + c) * 8;
       yy[s] = *(const V8T<T>*)(y + n * y_ss + off[s]);
-      gs[s] = *(const V8T<T>*)(dskip + n * ds_ss + off[s]);
+      src.template load<T>(n, off[s], gs[s]);
     }
     const V8T<T> gp = *(const V8T<T>*)(dpool + n * dp_ss + (long long)pl * ovox * 8 + r * 8);
     int best[8];
@@ -224,7 +280,7 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_kernel(const T* __restrict__ 
       float m = 0.f;
 #pragma unroll
       for (int s = 0; s < NW; ++s) {
-        zv[s][j] = to_f32<T>(from_f32<T>(fmaxf(fmaf(sc[j], to_f32<T>(yy[s][j]), sh[j]), 0.f)));     // z as bn_relu_fwd stored it
+        zv[s][j] = norm_z<T, true>(sc[j], to_f32<T>(yy[s][j]), sh[j]);                                    // z as bn_relu_fwd_kernel stored it
         if (s == 0) { m = zv[0][j]; best[j] = 0; } else if (zv[s][j] > m) { m = zv[s][j]; best[j] = s; }   // first maximum
       }
     }
@@ -234,11 +290,10 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_kernel(const T* __restrict__ 
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         // dz as maxpool_bwd_kernel (add_skip) stored it, then the ReLU mask
-        const float dz = to_f32<T>(from_f32<T>(to_f32<T>(gs[s][j]) + (best[j] == s ? to_f32<T>(gp[j]) : 0.f)));
-        const float d = zv[s][j] > 0.f ? dz : 0.f;
-        const float xh = (to_f32<T>(yy[s][j]) - mu[j]) * is[j];
+        const float d = norm_masked(zv[s][j], rounded<T>(Src::template at<T>(gs[s], j) + (best[j] == s ? to_f32<T>(gp[j]) : 0.f)));
+        const float xh = norm_xhat(to_f32<T>(yy[s][j]), mu[j], is[j]);
         if (PASS == 1) { s1[j] += d; s2[j] += d * xh; }
-        else o[j] = from_f32<T>(GN ? ca[j] * d - c1[j] - xh * c2[j] : ca[j] * (d - c1[j] - xh * c2[j]));      // (GN: bn_bwd_apply_kernel's GroupNorm form)
+        else o[j] = from_f32<T>(norm_bwd_dy<GN>(ca[j], d, c1[j], xh, c2[j]));
       }
       if (PASS == 2) *(V8T<T>*)(dy + n * dy_ss + off[s]) = o;
     }
@@ -283,18 +338,14 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
   }
 }
 
-// pass 2: dy = a * (dyh - c1 - xhat * c2); plane = grid dimension (wave-uniform constants), two items per thread
-// GN (GroupNorm form): coef = (gamma invstd, invstd m1, invstd m2) and dy = a dz' - b1 - xhat b2 -- the statistics of a GROUP depend on
-// every channel of it, so a channel with gamma = 0 still has the gradient -invstd (m1 + xhat m2), which the BatchNorm factorisation
-// a (dz' - c1 - xhat c2) (a = gamma invstd) cannot express.
-template <typename T, bool GN = false>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__ dz, long long dz_ss, const T* __restrict__ z,
-                                                           long long z_ss, const T* __restrict__ y, long long y_ss,
-                                                           T* __restrict__ dy, long long dy_ss, const float* __restrict__ mean,
-                                                           const float* __restrict__ invstd, const float* __restrict__ coef,
-                                                           const float* __restrict__ scale, const float* __restrict__ shift,
-                                                           int planes, long long vox,
-                                                           int pss = 0 /* per-sample stride of the per-channel parameters (GroupNorm: C) */) {
+// pass 2: dy (norm_bwd_dy); plane = grid dimension (wave-uniform constants), two items per thread
+template <typename T, typename Src, bool GN>
+__global__ __launch_bounds__(256) void norm_bwd_apply_kernel(Src src, const T* __restrict__ y, long long y_ss,
+                                                             T* __restrict__ dy, long long dy_ss, const float* __restrict__ mean,
+                                                             const float* __restrict__ invstd, const float* __restrict__ coef,
+                                                             const float* __restrict__ scale, const float* __restrict__ shift,
+                                                             long long vox,
+                                                             int pss /* per-sample stride of the per-channel parameters (GroupNorm: C; BatchNorm: 0) */) {
   const int pl = blockIdx.y, n = blockIdx.z;
   const long long v0 = (long long)blockIdx.x * 512 + threadIdx.x;
   float mu[8], is[8], ca[8], c1[8], c2[8], sc[8], sh[8];
@@ -305,14 +356,15 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
     sc[j] = scale[c]; sh[j] = shift[c];
   }
   const long long base = (long long)pl * vox * 8;
-  V8T<T> g[2], yy[2], zz[2];
+  typename Src::template Held<T> g[2];
+  V8T<T> yy[2], zz[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const long long v = v0 + u * 256;
     if (v < vox) {
-      g[u] = *(const V8T<T>*)(dz + n * dz_ss + base + v * 8);
+      src.template load<T>(n, base + v * 8, g[u]);
       yy[u] = *(const V8T<T>*)(y + n * y_ss + base + v * 8);
-      if (z) zz[u] = *(const V8T<T>*)(z + n * z_ss + base + v * 8);
+      if (src.has_z()) zz[u] = src.template load_z<T>(n, base + v * 8);
     }
   }
 #pragma unroll
@@ -323,10 +375,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float yv = to_f32<T>(yy[u][j]);
-      const float zv = z ? to_f32<T>(zz[u][j]) : to_f32<T>(from_f32<T>(fmaf(sc[j], yv, sh[j])));
-      const float d = zv > 0.f ? to_f32<T>(g[u][j]) : 0.f;
-      const float xh = (yv - mu[j]) * is[j];
-      o[j] = from_f32<T>(GN ? ca[j] * d - c1[j] - xh * c2[j] : ca[j] * (d - c1[j] - xh * c2[j]));
+      const float zv = src.has_z() ? to_f32<T>(zz[u][j]) : norm_z<T>(sc[j], yv, sh[j]);
+      o[j] = from_f32<T>(norm_bwd_dy<GN>(ca[j], norm_masked(zv, src_dz<T, Src>(g[u], j)), c1[j], norm_xhat(yv, mu[j], is[j]), c2[j]));
     }
     *(V8T<T>*)(dy + n * dy_ss + base + v * 8) = o;
   }
@@ -396,7 +446,7 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
   }
 }
 
-// backward finalize.  slab [(n * chunks + chunk)][C][2] = (s1, s2) of bn_bwd_reduce_kernel run per sample with that sample's
+// backward finalize.  slab [(n * chunks + chunk)][C][2] = (s1, s2) of norm_bwd_reduce_kernel run per sample with that sample's
 // mean / invstd: s1 = sum dz', s2 = sum dz' * xhat (dz' = dz where relu passed).  One block of 256 threads per GROUP (C <= 1024):
 //   dgamma[c] = sum_n s2, dbeta[c] = sum_n s1;
 //   per (n, group): m1 = sum_c gamma_c s1 / M, m2 = sum_c gamma_c s2 / M, M = channels per group x voxels;
@@ -737,16 +787,16 @@ __global__ __launch_bounds__(256) void head_loss_bwd_kernel(HeadLossParams p) {
 }
 
 // [r5] The head's backward AND the BatchNorm + ReLU backward of the last stage conv in two passes over that conv's raw output y -- the
-// head's input gradient dz is never written.  The three-kernel sequence it replaces (head_loss_bwd_kernel -> bn_bwd_reduce_kernel ->
-// bn_bwd_apply_kernel, with head_act) read y three times and wrote / read dz 1 + 2 times: 1.88 GB per C3 step at level 0 against 0.8.
+// head's input gradient dz is never written.  The three-kernel sequence it replaces (head_loss_bwd_kernel -> norm_bwd_reduce_kernel ->
+// norm_bwd_apply_kernel, with head_act) read y three times and wrote / read dz 1 + 2 times: 1.88 GB per C3 step at level 0 against 0.8.
 // A workgroup walks 64 voxels at a time, wave pl its channel plane pl (C0 = 32: four waves; every per-channel constant is wave-uniform,
 // i.e. lives in scalar registers): z = relu(bn(y)) as bn_relu_fwd would have stored it, the plane's share of the logits -> LDS, one
 // barrier, the four shares summed in a fixed order (the same bits in all four waves), softmax and loss gradient per lane, dz = W^T dl
 // for the wave's 8 channels ROUNDED to T as head_loss_bwd_kernel stored it.  (A quad of lanes per voxel with the planes across the quad
 // kept the constants in 72 vector registers per lane: 3 waves per SIMD, 260 + 236 us for the two passes at 2 x 128^3.)
-//   PASS 1: s1 += dz', s2 += dz' xhat (bn_bwd_reduce_kernel's arithmetic), dW += dl z, db += dl -- 16 + 8 NCLS + NCLS partial sums
+//   PASS 1: s1 += dz', s2 += dz' xhat (norm_bwd_reduce_kernel's arithmetic), dW += dl z, db += dl -- 16 + 8 NCLS + NCLS partial sums
 //           per lane -> one BatchNorm row [C][2] and one head row [planes][NCLS][8] + [NCLS] per 2 048 voxels;
-//   PASS 2: dy = a (dz' - c1 - xhat c2) (bn_bwd_apply_kernel's arithmetic) with the coefficients of bn_bwd_finalize_kernel.
+//   PASS 2: dy = a (dz' - c1 - xhat c2) (norm_bwd_apply_kernel's arithmetic) with the coefficients of bn_bwd_finalize_kernel.
 // The logits add their 32 terms plane by plane (head_loss_fwd_kernel adds them in channel order): the gradient is that of a logit one
 // rounding away from the forward's.
 struct HeadBnBwdParams {
@@ -844,7 +894,7 @@ __global__ __launch_bounds__(PL * 64, HBB_OCC) void head_bn_bwd_kernel(HeadBnBwd
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         yv[u][j] = to_f32<T>(yy[u][j]);
-        zv[u][j] = to_f32<T>(from_f32<T>(fmaxf(fmaf(sc[j], yv[u][j], sh[j]), 0.f)));      // z as bn_relu_fwd_kernel would have stored it (head_act)
+        zv[u][j] = norm_z<T, true>(sc[j], yv[u][j], sh[j]);      // z as bn_relu_fwd_kernel would have stored it (head_act)
 #pragma unroll
         for (int k = 0; k < NCLS; ++k) part[k] = fmaf(zv[u][j], W[k][j], part[k]);
       }
@@ -890,16 +940,13 @@ __global__ __launch_bounds__(PL * 64, HBB_OCC) void head_bn_bwd_kernel(HeadBnBwd
         float a = 0.f;
 #pragma unroll
         for (int k = 0; k < NCLS; ++k) a = fmaf(dl[k], W[k][j], a);
-        const float dz = to_f32<T>(from_f32<T>(a));                    // the gradient head_loss_bwd_kernel stored
-        const float d = zv[u][j] > 0.f ? dz : 0.f;
+        const float d = norm_masked(zv[u][j], rounded<T>(a));          // (rounded: the gradient head_loss_bwd_kernel stored)
         if (PASS == 1) {
-          acc[2 * j] += d;
-          acc[2 * j + 1] += d * (yv[u][j] - mu[j]) * is[j];
+          norm_bwd_sums(d, yv[u][j], mu[j], is[j], acc[2 * j], acc[2 * j + 1]);
 #pragma unroll
           for (int k = 0; k < NCLS; ++k) acc[16 + k * 8 + j] = fmaf(dl[k], zv[u][j], acc[16 + k * 8 + j]);
         } else {
-          const float xh = (yv[u][j] - mu[j]) * is[j];
-          o[j] = from_f32<T>(ca[j] * (d - c1[j] - xh * c2[j]));
+          o[j] = from_f32<T>(norm_bwd_dy<false>(ca[j], d, c1[j], norm_xhat(yv[u][j], mu[j], is[j]), c2[j]));
         }
       }
       if (PASS == 1) {
@@ -931,7 +978,7 @@ __global__ __launch_bounds__(PL * 64, HBB_OCC) void head_bn_bwd_kernel(HeadBnBwd
 
 // PASS 2 without the head: dy = a (dz' - c1 - xhat c2) with dz = W^T dl from the logit gradients PASS 1 left (8 NCLS bytes per voxel
 // instead of the logits, the softmax and the loss terms again).  Plane = grid dimension (wave-uniform constants), two voxels per thread.
-template <typename T, int NCLS, int PL, bool GN = false>      // GN: bn_bwd_apply_kernel's GroupNorm form (a d - c1 - xhat c2, per-sample rows)
+template <typename T, int NCLS, int PL, bool GN = false>      // GN: norm_bwd_apply_kernel's GroupNorm form (a d - c1 - xhat c2, per-sample rows)
 __global__ __launch_bounds__(256) void head_bn_apply_kernel(HeadBnBwdParams p) {
   constexpr int C0 = PL * 8;
   const int pl = blockIdx.y, n = blockIdx.z;
@@ -965,14 +1012,11 @@ __global__ __launch_bounds__(256) void head_bn_apply_kernel(HeadBnBwdParams p) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float yv = to_f32<T>(yy[u][j]);
-      const float zv = to_f32<T>(from_f32<T>(fmaxf(fmaf(sc[j], yv, sh[j]), 0.f)));
       float a = 0.f;
 #pragma unroll
       for (int k = 0; k < NCLS; ++k) a = fmaf(dl[u][k], W[k][j], a);
-      const float dz = to_f32<T>(from_f32<T>(a));
-      const float d = zv > 0.f ? dz : 0.f;
-      const float xh = (yv - mu[j]) * is[j];
-      o[j] = from_f32<T>(GN ? ca[j] * d - c1[j] - xh * c2[j] : ca[j] * (d - c1[j] - xh * c2[j]));
+      const float d = norm_masked(norm_z<T, true>(sc[j], yv, sh[j]), rounded<T>(a));
+      o[j] = from_f32<T>(norm_bwd_dy<GN>(ca[j], d, c1[j], norm_xhat(yv, mu[j], is[j]), c2[j]));
     }
     *(V8T<T>*)((T*)p.dy + n * p.dy_ss + po + v * 8) = o;
   }
@@ -1248,198 +1292,9 @@ __global__ void head_grad_scatter_kernel(const float* __restrict__ t, float* __r
   }
 }
 
-// ------------------------------------------------------------------ BatchNorm + ReLU backward with a summed upstream gradient (U-Net++)
-// In the nested network a stage output feeds every later node of its level and the transposed conv above it: its gradient is a sum
-// of up to 8 NHWC8c tensors (slot slices of the consumers' data gradients).  The sum is formed in fp32 in source order while the two
-// passes read, rounded once to T (the value a materialised dz tensor would hold), and never written.  The kernels below are
-// bn_bwd_reduce_kernel / bn_bwd_apply_kernel (z = NULL) and bn_pool_bwd_kernel with that sum in place of their single dz load, line
-// for line: with one source they give the same bits.
-struct SumSrcs {
-  static constexpr int MAX = 8;
-  const void* p[MAX];          // source k: sample n, element e at p[k] + n * ss[k] + e (in T elements)
-  long long ss[MAX];
-  int k;                       // 1 .. MAX
-};
-
-// acc[j] = sum_k src_k[n * ss_k + off + j] in fp32, k in order
-template <typename T>
-__device__ __forceinline__ void sum_srcs(const SumSrcs& s, int n, long long off, float (&acc)[8]) {
-  const V8T<T> g0 = *(const V8T<T>*)((const T*)s.p[0] + n * s.ss[0] + off);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = to_f32<T>(g0[j]);
-#pragma unroll
-  for (int k = 1; k < SumSrcs::MAX; ++k) {
-    if (k >= s.k) break;
-    const V8T<T> g = *(const V8T<T>*)((const T*)s.p[k] + n * s.ss[k] + off);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] += to_f32<T>(g[j]);
-  }
-}
-
-// pass 1 (bn_bwd_reduce_kernel): grid (chunks, planes, N); slab [(n*chunks + chunk)][C][2]
-template <typename T>
-__global__ __launch_bounds__(256) void bn_sum_bwd_reduce_kernel(SumSrcs src, const T* __restrict__ y, long long y_ss,
-                                                                const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                                const float* __restrict__ scale, const float* __restrict__ shift,
-                                                                int C, long long vox, int per_block, float* __restrict__ slab) {
-  const int pl = blockIdx.y, n = blockIdx.z;
-  const long long v0 = (long long)blockIdx.x * per_block;
-  const long long v1 = min(v0 + per_block, vox);
-  float s1[8], s2[8], mu[8], is[8], sc[8], sh[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = pl * 8 + j;
-    s1[j] = 0.f; s2[j] = 0.f; mu[j] = mean[c]; is[j] = invstd[c];
-    sc[j] = scale[c]; sh[j] = shift[c];
-  }
-  const long long po = (long long)pl * vox * 8;
-#pragma unroll 4
-  for (long long v = v0 + threadIdx.x; v < v1; v += 256) {
-    float g[8];
-    sum_srcs<T>(src, n, po + v * 8, g);
-    const V8T<T> yy = *(const V8T<T>*)(y + n * y_ss + po + v * 8);
-    V8T<T> zz;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) zz[j] = from_f32<T>(fmaf(sc[j], to_f32<T>(yy[j]), sh[j]));
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float d = to_f32<T>(zz[j]) > 0.f ? to_f32<T>(from_f32<T>(g[j])) : 0.f;
-      s1[j] += d;
-      s2[j] += d * (to_f32<T>(yy[j]) - mu[j]) * is[j];
-    }
-  }
-  __shared__ float red[4 * 16];
-  const long long part = (long long)n * gridDim.x + blockIdx.x;
-  float vals[16];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { vals[2 * j] = s1[j]; vals[2 * j + 1] = s2[j]; }
-  block_reduce_store<16>(vals, red, slab + (part * C + pl * 8) * 2);
-}
-
-// pass 2 (bn_bwd_apply_kernel): dy = a (dz' - c1 - xhat c2); grid (vox / 512, planes, N), two items per thread
-template <typename T>
-__global__ __launch_bounds__(256) void bn_sum_bwd_apply_kernel(SumSrcs src, const T* __restrict__ y, long long y_ss,
-                                                               T* __restrict__ dy, long long dy_ss, const float* __restrict__ mean,
-                                                               const float* __restrict__ invstd, const float* __restrict__ coef,
-                                                               const float* __restrict__ scale, const float* __restrict__ shift,
-                                                               long long vox) {
-  const int pl = blockIdx.y, n = blockIdx.z;
-  const long long v0 = (long long)blockIdx.x * 512 + threadIdx.x;
-  float mu[8], is[8], ca[8], c1[8], c2[8], sc[8], sh[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = pl * 8 + j;
-    mu[j] = mean[c]; is[j] = invstd[c]; ca[j] = coef[c * 3]; c1[j] = coef[c * 3 + 1]; c2[j] = coef[c * 3 + 2];
-    sc[j] = scale[c]; sh[j] = shift[c];
-  }
-  const long long base = (long long)pl * vox * 8;
-  float g[2][8];
-  V8T<T> yy[2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const long long v = v0 + u * 256;
-    if (v < vox) {
-      sum_srcs<T>(src, n, base + v * 8, g[u]);
-      yy[u] = *(const V8T<T>*)(y + n * y_ss + base + v * 8);
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const long long v = v0 + u * 256;
-    if (v >= vox) continue;
-    V8T<T> o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float yv = to_f32<T>(yy[u][j]);
-      const float zv = to_f32<T>(from_f32<T>(fmaf(sc[j], yv, sh[j])));
-      const float d = zv > 0.f ? to_f32<T>(from_f32<T>(g[u][j])) : 0.f;
-      const float xh = (yv - mu[j]) * is[j];
-      o[j] = from_f32<T>(ca[j] * (d - c1[j] - xh * c2[j]));
-    }
-    *(V8T<T>*)(dy + n * dy_ss + base + v * 8) = o;
-  }
-}
-
-// both passes with the max-pool route of dpool added (bn_pool_bwd_kernel): dz = round_T(sum_k src_k + route(dpool)); one thread per
-// pooled voxel and channel plane
-template <typename T, int ND, int PASS>
-__global__ __launch_bounds__(256) void bn_sum_pool_bwd_kernel(SumSrcs src, const T* __restrict__ dpool, long long dp_ss,
-                                                              const T* __restrict__ y, long long y_ss, T* __restrict__ dy,
-                                                              long long dy_ss, const float* __restrict__ mean,
-                                                              const float* __restrict__ invstd, const float* __restrict__ coef,
-                                                              const float* __restrict__ scale, const float* __restrict__ shift,
-                                                              int C, int Do, int Ho, int Wo, int per_block, float* __restrict__ slab) {
-  constexpr int NW = ND == 3 ? 8 : 4;
-  const int pl = blockIdx.y, n = blockIdx.z;
-  const long long ovox = (long long)Do * Ho * Wo;
-  const int Di = ND == 3 ? Do * 2 : 1, Hi = Ho * 2, Wi = Wo * 2;
-  const long long ipl = (long long)pl * Di * Hi * Wi * 8;
-  float mu[8], is[8], sc[8], sh[8], ca[8], c1[8], c2[8], s1[8], s2[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = pl * 8 + j;
-    mu[j] = mean[c]; is[j] = invstd[c]; sc[j] = scale[c]; sh[j] = shift[c]; s1[j] = 0.f; s2[j] = 0.f;
-    if (PASS == 2) { ca[j] = coef[c * 3]; c1[j] = coef[c * 3 + 1]; c2[j] = coef[c * 3 + 2]; }
-  }
-  const long long r0 = (long long)blockIdx.x * per_block, r1 = min(r0 + per_block, ovox);
-  for (long long r = r0 + threadIdx.x; r < r1; r += 256) {
-    const int ox = (int)(r % Wo), oy = (int)((r / Wo) % Ho), oz = (int)(r / ((long long)Wo * Ho));
-    V8T<T> yy[NW];
-    float gs[NW][8];
-    long long off[NW];
-#pragma unroll
-    for (int s = 0; s < NW; ++s) {
-      const int a = ND == 3 ? (s >> 2) : 0, b = (s >> 1) & 1, c = s & 1;
-      const int zz = ND == 3 ? oz * 2 + a : 0;
-      off[s] = ipl + (((long long)zz * Hi + oy * 2 + b) * Wi + ox * 2 + c) * 8;
-      yy[s] = *(const V8T<T>*)(y + n * y_ss + off[s]);
-      sum_srcs<T>(src, n, off[s], gs[s]);
-    }
-    const V8T<T> gp = *(const V8T<T>*)(dpool + n * dp_ss + (long long)pl * ovox * 8 + r * 8);
-    int best[8];
-    float zv[NW][8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float m = 0.f;
-#pragma unroll
-      for (int s = 0; s < NW; ++s) {
-        zv[s][j] = to_f32<T>(from_f32<T>(fmaxf(fmaf(sc[j], to_f32<T>(yy[s][j]), sh[j]), 0.f)));
-        if (s == 0) { m = zv[0][j]; best[j] = 0; } else if (zv[s][j] > m) { m = zv[s][j]; best[j] = s; }   // first maximum
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < NW; ++s) {
-      V8T<T> o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float dz = to_f32<T>(from_f32<T>(gs[s][j] + (best[j] == s ? to_f32<T>(gp[j]) : 0.f)));
-        const float d = zv[s][j] > 0.f ? dz : 0.f;
-        const float xh = (to_f32<T>(yy[s][j]) - mu[j]) * is[j];
-        if (PASS == 1) { s1[j] += d; s2[j] += d * xh; }
-        else o[j] = from_f32<T>(ca[j] * (d - c1[j] - xh * c2[j]));
-      }
-      if (PASS == 2) *(V8T<T>*)(dy + n * dy_ss + off[s]) = o;
-    }
-  }
-  if (PASS == 1) {
-    __shared__ float red[4 * 16];
-    const long long part = (long long)n * gridDim.x + blockIdx.x;
-    float vals[16];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { vals[2 * j] = s1[j]; vals[2 * j + 1] = s2[j]; }
-    block_reduce_store<16>(vals, red, slab + (part * C + pl * 8) * 2);
-  }
-}
-
-
 }  // namespace
 
 #define DT_OK(dt) IUNET_REQUIRE((dt) == 0 || (dt) == 1, "dtype must be 0 (f16) or 1 (bf16), got %d", (dt))
-#define LAUNCH_T(kern, grid, ...)                                                              \
-  do {                                                                                         \
-    if (dtype == 0) hipLaunchKernelGGL((kern<f16>), grid, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);  \
-    else hipLaunchKernelGGL((kern<bf16>), grid, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); \
-  } while (0)
 
 // (declared in loss_terms.h)
 int iunet_loss_finalize_launch(const float* slab, int nparts, int ncls, int kind, int has_weight, double nvox_total, float* out4,
@@ -1449,6 +1304,125 @@ int iunet_loss_finalize_launch(const float* slab, int nparts, int ncls, int kind
   return IUNET_OK;
 }
 
+static const int BN_BWD_PER_BLOCK = 2048;       // (measured at level 0 of C3: 8192 -> 139 us, 2048 -> 122 us, 1024 -> 147 us)
+static const int BN_POOL_PER_BLOCK = 8192;      // input voxels per workgroup of the pooled variant's first pass (its 2^d windows make 2048 slower)
+// rows a pooled first pass writes per sample (fewer than iunet_bn_bwd_num_parts: the slab of the unpooled passes holds them)
+static int norm_pool_chunks(int nd, long long ovox) {
+  const int per_block = BN_POOL_PER_BLOCK / (nd == 3 ? 8 : 4);
+  return (int)((ovox + per_block - 1) / per_block);
+}
+
+// z = relu(scale * y + shift), and the same with the 2^d max-pool of z ((Do, Ho, Wo) = pooled grid); pss: per-sample stride of scale / shift
+static int norm_relu_fwd_launch(int dtype, const void* y, long long y_ss, void* z, long long z_ss, const void* scale, const void* shift, int C,
+                                int N, long long vox, int pss, void* stream) {
+  const dim3 grid((unsigned)((vox + 511) / 512), C / 8, N);
+  iunet_dispatch(dtype, 2, false, [&](auto t, auto, auto) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(bn_relu_fwd_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)y, y_ss, (T*)z, z_ss, (const float*)scale,
+                       (const float*)shift, C / 8, vox, pss);
+  });
+  IUNET_CHECK_HIP(hipGetLastError());
+  return IUNET_OK;
+}
+static int norm_relu_pool_fwd_launch(int dtype, int nd, const void* y, long long y_ss, void* z, long long z_ss, void* pooled, long long p_ss,
+                                     const void* scale, const void* shift, int C, int N, int Do, int Ho, int Wo, int pss, void* stream) {
+  const long long ovox = (long long)Do * Ho * Wo;
+  const dim3 grid((unsigned)((ovox + 255) / 256), C / 8, N);
+  iunet_dispatch(dtype, nd, false, [&](auto t, auto ndc, auto) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((bn_relu_pool_fwd_kernel<T, ndc.value>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)y, y_ss, (T*)z, z_ss,
+                       (T*)pooled, p_ss, (const float*)scale, (const float*)shift, Do, Ho, Wo, pss);
+  });
+  IUNET_CHECK_HIP(hipGetLastError());
+  return IUNET_OK;
+}
+
+// The GroupNorm + ReLU forward: statistics pass unless the slab already holds `rows` rows per sample, gn_finalize_kernel, then one
+// normalise pass (z NULL: none; pooled non-NULL: the pass that also writes the 2^d max-pool on the (Do, Ho, Wo) grid).  The callers have
+// checked the arguments.
+static int gn_relu_fwd_seq(int dtype, int nd, const void* y, long long y_ss, void* z, long long z_ss, void* pooled, long long p_ss,
+                           const void* gamma, const void* beta, int groups, float eps, void* slab, int rows, void* scale, void* shift,
+                           void* mean, void* invstd, int C, int N, long long vox, int Do, int Ho, int Wo, void* stream) {
+  const int per_block = BN_BWD_PER_BLOCK;
+  const int chunks = rows > 0 ? rows : (int)((vox + per_block - 1) / per_block);
+  if (rows <= 0) {
+    const dim3 g1(chunks, C / 8, N);
+    iunet_dispatch(dtype, 2, false, [&](auto t, auto, auto) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(gn_stats_kernel<T>, g1, dim3(256), 0, (hipStream_t)stream, (const T*)y, y_ss, C, vox, per_block, (float*)slab);
+    });
+  }
+  hipLaunchKernelGGL(gn_finalize_kernel, dim3(groups, N), dim3(256), 0, (hipStream_t)stream, (const float*)slab, chunks, C, groups,
+                     (double)vox, (const float*)gamma, (const float*)beta, eps, (float*)scale, (float*)shift, (float*)mean, (float*)invstd);
+  // one launch over the samples: sample n reads its row of scale / shift
+  if (pooled) return norm_relu_pool_fwd_launch(dtype, nd, y, y_ss, z, z_ss, pooled, p_ss, scale, shift, C, N, Do, Ho, Wo, C, stream);
+  if (z) return norm_relu_fwd_launch(dtype, y, y_ss, z, z_ss, scale, shift, C, N, vox, C, stream);
+  IUNET_CHECK_HIP(hipGetLastError());
+  return IUNET_OK;
+}
+
+// pass 1b of either norm: dgamma, dbeta and the coefficients of pass 2 from the slab of pass 1 -- `chunks` rows per sample (BatchNorm
+// sums all `nparts` rows, however they are split over the samples)
+static void norm_bwd_finalize(int groups, const void* slab, int chunks, int nparts, int C, int N, long long vox, const void* gamma,
+                              const void* invstd, void* dgamma, void* dbeta, void* coef, void* stream) {
+  if (groups > 0)      // the rows are [sample][chunk][C][2]
+    hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(groups), dim3(1024), 0, (hipStream_t)stream, (const float*)slab, chunks, C, groups, N,
+                       (double)vox, (const float*)gamma, (const float*)invstd, (float*)dgamma, (float*)dbeta, (float*)coef);
+  else
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, (const float*)slab, nparts, C,
+                       (double)N * (double)vox, (const float*)gamma, (const float*)invstd, (float*)dgamma, (float*)dbeta, (float*)coef);
+}
+
+// The backward of z = relu(norm(y)) as every entry point below runs it: pass 1 unless the slab already holds its rows, the finalize,
+// pass 2 unless dy is NULL.  The gradient source is the policy `src` (OneSrc / SumSrcs); the callers have checked the arguments.
+struct NormBwd {
+  int dtype;
+  const void* y; long long y_ss;
+  void* dy; long long dy_ss;           // dy NULL: sums and coefficients only (the consumer applies pass 2 while staging)
+  const void *mean, *invstd, *gamma, *scale, *shift;
+  void *dgamma, *dbeta, *slab, *coef;
+  int C, N; long long vox;
+  int groups;                          // 0: BatchNorm ([C] parameters); > 0: GroupNorm ([N][C] rows of them)
+  int rows;                            // > 0: pass 1 has been done -- the slab holds `rows` rows (BatchNorm: in all; GroupNorm: per sample)
+  // the max-pool form (dpool non-NULL): `src` is the skip gradient on y's grid, dpool the gradient on the pooled grid (Do, Ho, Wo)
+  int nd; const void* dpool; long long dp_ss; int Do, Ho, Wo;
+};
+template <typename Src>
+static int norm_relu_bwd(const Src& src, const NormBwd& a, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  const bool pool = a.dpool != nullptr;
+  const long long ovox = (long long)a.Do * a.Ho * a.Wo;
+  const int per_block = pool ? BN_POOL_PER_BLOCK / (a.nd == 3 ? 8 : 4) : BN_BWD_PER_BLOCK;      // (pooled) voxels per workgroup of pass 1
+  const int chunks = a.rows > 0 ? a.rows : pool ? norm_pool_chunks(a.nd, ovox) : (int)((a.vox + per_block - 1) / per_block);
+  const dim3 g1(chunks, a.C / 8, a.N), g2((unsigned)(pool ? (ovox + 255) / 256 : (a.vox + 511) / 512), a.C / 8, a.N);
+  const int pss = a.groups > 0 ? a.C : 0;
+  const float *mean = (const float*)a.mean, *invstd = (const float*)a.invstd, *scale = (const float*)a.scale, *shift = (const float*)a.shift;
+  return iunet_dispatch(a.dtype, a.nd, a.groups > 0, [&](auto t, auto ndc, auto gn) -> int {
+    using T = decltype(t);
+    if constexpr (gn.value && !std::is_same_v<Src, OneSrc>) {      // (not built: nothing launches a summed gradient under GroupNorm)
+      iunet_set_error("norm_relu_bwd: GroupNorm takes one gradient tensor");
+      return IUNET_ERR_UNSUPPORTED;
+    } else {
+      auto pool_pass = [&](auto pass, dim3 grid, int pb) {
+        hipLaunchKernelGGL((norm_pool_bwd_kernel<T, ndc.value, pass.value, Src, gn.value>), grid, dim3(256), 0, st, src, (const T*)a.dpool,
+                           a.dp_ss, (const T*)a.y, a.y_ss, (T*)a.dy, a.dy_ss, mean, invstd, (const float*)a.coef, scale, shift, a.C, a.Do, a.Ho,
+                           a.Wo, pb, (float*)a.slab, pss);
+      };
+      if (a.rows > 0) {}
+      else if (pool) pool_pass(std::integral_constant<int, 1>(), g1, per_block);
+      else hipLaunchKernelGGL((norm_bwd_reduce_kernel<T, Src>), g1, dim3(256), 0, st, src, (const T*)a.y, a.y_ss, mean, invstd, scale, shift,
+                              a.C, a.vox, per_block, (float*)a.slab, pss);
+      norm_bwd_finalize(a.groups, a.slab, chunks, a.rows > 0 ? a.rows : chunks * a.N, a.C, a.N, a.vox, a.gamma, a.invstd, a.dgamma, a.dbeta,
+                        a.coef, stream);
+      if (a.dy == nullptr) {}
+      else if (pool) pool_pass(std::integral_constant<int, 2>(), g2, 256);
+      else hipLaunchKernelGGL((norm_bwd_apply_kernel<T, Src, gn.value>), g2, dim3(256), 0, st, src, (const T*)a.y, a.y_ss, (T*)a.dy, a.dy_ss,
+                              mean, invstd, (const float*)a.coef, scale, shift, a.vox, pss);
+      IUNET_CHECK_HIP(hipGetLastError());
+      return IUNET_OK;
+    }
+  });
+}
 extern "C" {
 
 int iunet_bn_finalize(const void* slab, int nparts, int C, double count, const void* gamma, const void* beta,
@@ -1465,11 +1439,7 @@ int iunet_bn_finalize(const void* slab, int nparts, int C, double count, const v
 int iunet_bn_relu_fwd(int dtype, const void* y, long long y_ss, void* z, long long z_ss, const void* scale,
                       const void* shift, int C, int N, long long vox, void* stream) {
   DT_OK(dtype);
-  dim3 grid((unsigned)((vox + 511) / 512), C / 8, N);
-  if (dtype == 0) hipLaunchKernelGGL(bn_relu_fwd_kernel<f16>, grid, dim3(256), 0, (hipStream_t)stream, (const f16*)y, y_ss, (f16*)z, z_ss, (const float*)scale, (const float*)shift, C / 8, vox);
-  else hipLaunchKernelGGL(bn_relu_fwd_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)y, y_ss, (bf16*)z, z_ss, (const float*)scale, (const float*)shift, C / 8, vox);
-  IUNET_CHECK_HIP(hipGetLastError());
-  return IUNET_OK;
+  return norm_relu_fwd_launch(dtype, y, y_ss, z, z_ss, scale, shift, C, N, vox, 0, stream);
 }
 
 // bn_relu_fwd and the 2^d max-pool of its output in one pass; (Do, Ho, Wo) = pooled grid, y / z on the 2x grid
@@ -1479,17 +1449,8 @@ int iunet_bn_relu_pool_fwd(int dtype, int nd, const void* y, long long y_ss, voi
   DT_OK(dtype);
   IUNET_REQUIRE(y && z && pooled && scale && shift, "bn_relu_pool_fwd: null pointer");
   IUNET_REQUIRE(nd == 2 || nd == 3, "bn_relu_pool_fwd: nd must be 2 or 3");
-  const long long ovox = (long long)Do * Ho * Wo;
-  dim3 grid((unsigned)((ovox + 255) / 256), C / 8, N);
-#define BRP(TT, NDV) hipLaunchKernelGGL((bn_relu_pool_fwd_kernel<TT, NDV>), grid, dim3(256), 0, (hipStream_t)stream, (const TT*)y, y_ss, (TT*)z, z_ss, (TT*)pooled, p_ss, (const float*)scale, (const float*)shift, Do, Ho, Wo)
-  if (dtype == 0) { if (nd == 3) BRP(f16, 3); else BRP(f16, 2); } else { if (nd == 3) BRP(bf16, 3); else BRP(bf16, 2); }
-#undef BRP
-  IUNET_CHECK_HIP(hipGetLastError());
-  return IUNET_OK;
+  return norm_relu_pool_fwd_launch(dtype, nd, y, y_ss, z, z_ss, pooled, p_ss, scale, shift, C, N, Do, Ho, Wo, 0, stream);
 }
-
-static const int BN_BWD_PER_BLOCK = 2048;       // (measured at level 0 of C3: 8192 -> 139 us, 2048 -> 122 us, 1024 -> 147 us)
-static const int BN_POOL_PER_BLOCK = 8192;      // input voxels per workgroup of the pooled variant's first pass (its 2^d windows make 2048 slower)
 
 int iunet_bn_bwd_num_parts(int N, long long vox) {
   const int per_block = BN_BWD_PER_BLOCK;
@@ -1502,19 +1463,8 @@ int iunet_bn_relu_bwd(int dtype, const void* dz, long long dz_ss, const void* z,
                       long long vox, void* stream) {
   DT_OK(dtype);
   IUNET_REQUIRE(dz && y && slab && coef && scale && shift, "bn_relu_bwd: null pointer");      // dy NULL: sums + coefficients only
-  const int per_block = BN_BWD_PER_BLOCK;
-  const int chunks = (int)((vox + per_block - 1) / per_block);
-  dim3 g1(chunks, C / 8, N);
-  if (dtype == 0) hipLaunchKernelGGL(bn_bwd_reduce_kernel<f16>, g1, dim3(256), 0, (hipStream_t)stream, (const f16*)dz, dz_ss, (const f16*)z, z_ss, (const f16*)y, y_ss, (const float*)mean, (const float*)invstd, (const float*)scale, (const float*)shift, C, vox, per_block, (float*)slab);
-  else hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16>, g1, dim3(256), 0, (hipStream_t)stream, (const bf16*)dz, dz_ss, (const bf16*)z, z_ss, (const bf16*)y, y_ss, (const float*)mean, (const float*)invstd, (const float*)scale, (const float*)shift, C, vox, per_block, (float*)slab);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, (const float*)slab, chunks * N, C,
-                     (double)N * (double)vox, (const float*)gamma, (const float*)invstd, (float*)dgamma, (float*)dbeta, (float*)coef);
-  if (dy == nullptr) { IUNET_CHECK_HIP(hipGetLastError()); return IUNET_OK; }      // the consumer applies pass 2 while staging
-  dim3 g2((unsigned)((vox + 511) / 512), C / 8, N);
-  if (dtype == 0) hipLaunchKernelGGL(bn_bwd_apply_kernel<f16>, g2, dim3(256), 0, (hipStream_t)stream, (const f16*)dz, dz_ss, (const f16*)z, z_ss, (const f16*)y, y_ss, (f16*)dy, dy_ss, (const float*)mean, (const float*)invstd, (const float*)coef, (const float*)scale, (const float*)shift, C / 8, vox);
-  else hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16>, g2, dim3(256), 0, (hipStream_t)stream, (const bf16*)dz, dz_ss, (const bf16*)z, z_ss, (const bf16*)y, y_ss, (bf16*)dy, dy_ss, (const float*)mean, (const float*)invstd, (const float*)coef, (const float*)scale, (const float*)shift, C / 8, vox);
-  IUNET_CHECK_HIP(hipGetLastError());
-  return IUNET_OK;
+  return norm_relu_bwd(OneSrc{dz, dz_ss, z, z_ss},
+                       NormBwd{dtype, y, y_ss, dy, dy_ss, mean, invstd, gamma, scale, shift, dgamma, dbeta, slab, coef, C, N, vox, 0, 0}, stream);
 }
 
 // iunet_bn_relu_bwd whose first pass has already been done: `slab` holds nparts rows [C][2] of (sum dz', sum dz' * xhat) written by
@@ -1527,14 +1477,8 @@ int iunet_bn_relu_bwd_apply(int dtype, const void* dz, long long dz_ss, const vo
   DT_OK(dtype);
   IUNET_REQUIRE(dz && y && slab && coef && scale && shift && mean && invstd && gamma && dgamma && dbeta, "bn_relu_bwd_apply: null pointer");
   IUNET_REQUIRE(C > 0 && C % 8 == 0 && N > 0 && vox > 0 && nparts > 0, "bn_relu_bwd_apply: C %d, N %d, %lld voxels, %d rows", C, N, vox, nparts);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, (const float*)slab, nparts, C,
-                     (double)N * (double)vox, (const float*)gamma, (const float*)invstd, (float*)dgamma, (float*)dbeta, (float*)coef);
-  if (dy == nullptr) { IUNET_CHECK_HIP(hipGetLastError()); return IUNET_OK; }
-  dim3 g2((unsigned)((vox + 511) / 512), C / 8, N);
-  if (dtype == 0) hipLaunchKernelGGL(bn_bwd_apply_kernel<f16>, g2, dim3(256), 0, (hipStream_t)stream, (const f16*)dz, dz_ss, (const f16*)nullptr, 0LL, (const f16*)y, y_ss, (f16*)dy, dy_ss, (const float*)mean, (const float*)invstd, (const float*)coef, (const float*)scale, (const float*)shift, C / 8, vox);
-  else hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16>, g2, dim3(256), 0, (hipStream_t)stream, (const bf16*)dz, dz_ss, (const bf16*)nullptr, 0LL, (const bf16*)y, y_ss, (bf16*)dy, dy_ss, (const float*)mean, (const float*)invstd, (const float*)coef, (const float*)scale, (const float*)shift, C / 8, vox);
-  IUNET_CHECK_HIP(hipGetLastError());
-  return IUNET_OK;
+  return norm_relu_bwd(OneSrc{dz, dz_ss, nullptr, 0}, NormBwd{dtype, y, y_ss, dy, dy_ss, mean, invstd, gamma, scale, shift, dgamma, dbeta,
+                                                              (void*)slab, coef, C, N, vox, 0, nparts}, stream);
 }
 
 /* ---- GroupNorm + ReLU (north_star "GroupNorm/BN") ------------------------------------------------------- */
@@ -1551,20 +1495,8 @@ int iunet_gn_relu_fwd_rows(int dtype, const void* y, long long y_ss, void* z, lo
   IUNET_REQUIRE(y && gamma && beta && slab && scale && shift && mean && invstd, "gn_relu_fwd: null pointer");      // z NULL: statistics -> scale / shift only (the consumer applies them: iunet_head_loss_fwd_act_ps)
   IUNET_REQUIRE(C > 0 && C % 8 == 0 && N > 0 && vox > 0 && rows >= 0, "gn_relu_fwd: C %d (multiple of 8), N %d, %lld voxels, %d rows", C, N, vox, rows);
   IUNET_REQUIRE(groups > 0 && C % groups == 0, "gn_relu_fwd: %d channels do not split into %d groups", C, groups);
-  const int per_block = BN_BWD_PER_BLOCK;
-  const int chunks = rows > 0 ? rows : (int)((vox + per_block - 1) / per_block);
-  dim3 g1(chunks, C / 8, N);
-  if (rows > 0) {}
-  else if (dtype == 0) hipLaunchKernelGGL(gn_stats_kernel<f16>, g1, dim3(256), 0, (hipStream_t)stream, (const f16*)y, y_ss, C, vox, per_block, (float*)slab);
-  else hipLaunchKernelGGL(gn_stats_kernel<bf16>, g1, dim3(256), 0, (hipStream_t)stream, (const bf16*)y, y_ss, C, vox, per_block, (float*)slab);
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(groups, N), dim3(256), 0, (hipStream_t)stream, (const float*)slab, chunks, C, groups,
-                     (double)vox, (const float*)gamma, (const float*)beta, eps, (float*)scale, (float*)shift, (float*)mean, (float*)invstd);
-  dim3 g2((unsigned)((vox + 511) / 512), C / 8, N);        // one launch over the samples: sample n reads its row of scale / shift
-  if (z == nullptr) {}
-  else if (dtype == 0) hipLaunchKernelGGL(bn_relu_fwd_kernel<f16>, g2, dim3(256), 0, (hipStream_t)stream, (const f16*)y, y_ss, (f16*)z, z_ss, (const float*)scale, (const float*)shift, C / 8, vox, C);
-  else hipLaunchKernelGGL(bn_relu_fwd_kernel<bf16>, g2, dim3(256), 0, (hipStream_t)stream, (const bf16*)y, y_ss, (bf16*)z, z_ss, (const float*)scale, (const float*)shift, C / 8, vox, C);
-  IUNET_CHECK_HIP(hipGetLastError());
-  return IUNET_OK;
+  return gn_relu_fwd_seq(dtype, 0, y, y_ss, z, z_ss, nullptr, 0, gamma, beta, groups, eps, slab, rows, scale, shift, mean, invstd, C, N, vox,
+                         0, 0, 0, stream);
 }
 
 int iunet_gn_relu_fwd(int dtype, const void* y, long long y_ss, void* z, long long z_ss, const void* gamma, const void* beta,
@@ -1590,9 +1522,6 @@ int iunet_gn_finalize(const void* stats, int nparts, int C, int groups, long lon
 
 // backward of z = relu(group_norm(y)): dy, dgamma, dbeta from dz and y; scale / shift / mean / invstd [N][C] from the forward;
 // slab as above, coef: N * C * 3 floats of scratch.  C <= 1024.
-int iunet_gn_relu_bwd_rows(int dtype, const void* dz, long long dz_ss, const void* y, long long y_ss, void* dy, long long dy_ss,
-                           const void* gamma, int groups, const void* scale, const void* shift, const void* mean, const void* invstd,
-                           void* dgamma, void* dbeta, void* slab, int rows, void* coef, int C, int N, long long vox, void* stream);
 int iunet_gn_relu_bwd(int dtype, const void* dz, long long dz_ss, const void* y, long long y_ss, void* dy, long long dy_ss,
                       const void* gamma, int groups, const void* scale, const void* shift, const void* mean, const void* invstd,
                       void* dgamma, void* dbeta, void* slab, void* coef, int C, int N, long long vox, void* stream) {
@@ -1607,27 +1536,12 @@ int iunet_gn_relu_bwd_rows(int dtype, const void* dz, long long dz_ss, const voi
   IUNET_REQUIRE(dz && y && dy && gamma && scale && shift && mean && invstd && dgamma && dbeta && slab && coef, "gn_relu_bwd: null pointer");
   IUNET_REQUIRE(C > 0 && C % 8 == 0 && C <= 1024 && N > 0 && vox > 0, "gn_relu_bwd: C %d (multiple of 8, <= 1024), N %d, %lld voxels", C, N, vox);
   IUNET_REQUIRE(groups > 0 && C % groups == 0, "gn_relu_bwd: %d channels do not split into %d groups", C, groups);
-  const int per_block = BN_BWD_PER_BLOCK;
-  const int chunks = rows > 0 ? rows : (int)((vox + per_block - 1) / per_block);
-  dim3 g1(chunks, C / 8, N), g2((unsigned)((vox + 511) / 512), C / 8, N);      // one launch over the samples: sample n reads its rows of the parameters
-  const float *mu = (const float*)mean, *is = (const float*)invstd, *sc = (const float*)scale, *sh = (const float*)shift;
-  if (rows > 0) {}
-  else if (dtype == 0) hipLaunchKernelGGL(bn_bwd_reduce_kernel<f16>, g1, dim3(256), 0, (hipStream_t)stream, (const f16*)dz, dz_ss, (const f16*)nullptr, 0LL, (const f16*)y, y_ss, mu, is, sc, sh, C, vox, per_block, (float*)slab, C);
-  else hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16>, g1, dim3(256), 0, (hipStream_t)stream, (const bf16*)dz, dz_ss, (const bf16*)nullptr, 0LL, (const bf16*)y, y_ss, mu, is, sc, sh, C, vox, per_block, (float*)slab, C);
-  hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(groups), dim3(1024), 0, (hipStream_t)stream, (const float*)slab, chunks, C, groups, N,
-                     (double)vox, (const float*)gamma, (const float*)invstd, (float*)dgamma, (float*)dbeta, (float*)coef);
-  const float* cf = (const float*)coef;
-  if (dtype == 0) hipLaunchKernelGGL((bn_bwd_apply_kernel<f16, true>), g2, dim3(256), 0, (hipStream_t)stream, (const f16*)dz, dz_ss, (const f16*)nullptr, 0LL, (const f16*)y, y_ss, (f16*)dy, dy_ss, mu, is, cf, sc, sh, C / 8, vox, C);
-  else hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16, true>), g2, dim3(256), 0, (hipStream_t)stream, (const bf16*)dz, dz_ss, (const bf16*)nullptr, 0LL, (const bf16*)y, y_ss, (bf16*)dy, dy_ss, mu, is, cf, sc, sh, C / 8, vox, C);
-  IUNET_CHECK_HIP(hipGetLastError());
-  return IUNET_OK;
+  return norm_relu_bwd(OneSrc{dz, dz_ss, nullptr, 0}, NormBwd{dtype, y, y_ss, dy, dy_ss, mean, invstd, gamma, scale, shift, dgamma, dbeta, slab,
+                                                              coef, C, N, vox, groups, rows}, stream);
 }
 
 // iunet_gn_relu_fwd whose normalise pass also writes the 2^d max-pool of z (encoder stages: the pool would re-read z right away):
 // statistics pass + finalize + ONE pass that writes z and the pooled tensor ((Do, Ho, Wo) grid, p_ss elements per sample).
-int iunet_gn_relu_pool_fwd_rows(int dtype, int nd, const void* y, long long y_ss, void* z, long long z_ss, void* pooled, long long p_ss,
-                                const void* gamma, const void* beta, int groups, float eps, void* slab, int rows, void* scale, void* shift,
-                                void* mean, void* invstd, int C, int N, int Do, int Ho, int Wo, void* stream);
 int iunet_gn_relu_pool_fwd(int dtype, int nd, const void* y, long long y_ss, void* z, long long z_ss, void* pooled, long long p_ss,
                            const void* gamma, const void* beta, int groups, float eps, void* slab, void* scale, void* shift, void* mean,
                            void* invstd, int C, int N, int Do, int Ho, int Wo, void* stream) {
@@ -1644,20 +1558,8 @@ int iunet_gn_relu_pool_fwd_rows(int dtype, int nd, const void* y, long long y_ss
   IUNET_REQUIRE(C > 0 && C % 8 == 0 && N > 0 && Do > 0 && Ho > 0 && Wo > 0, "gn_relu_pool_fwd: bad shape");
   IUNET_REQUIRE(groups > 0 && C % groups == 0, "gn_relu_pool_fwd: %d channels do not split into %d groups", C, groups);
   const long long ovox = (long long)Do * Ho * Wo, vox = ovox * (nd == 3 ? 8 : 4);
-  const int per_block = BN_BWD_PER_BLOCK;
-  const int chunks = rows > 0 ? rows : (int)((vox + per_block - 1) / per_block);
-  dim3 g1(chunks, C / 8, N);
-  if (rows > 0) {}
-  else if (dtype == 0) hipLaunchKernelGGL(gn_stats_kernel<f16>, g1, dim3(256), 0, (hipStream_t)stream, (const f16*)y, y_ss, C, vox, per_block, (float*)slab);
-  else hipLaunchKernelGGL(gn_stats_kernel<bf16>, g1, dim3(256), 0, (hipStream_t)stream, (const bf16*)y, y_ss, C, vox, per_block, (float*)slab);
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(groups, N), dim3(256), 0, (hipStream_t)stream, (const float*)slab, chunks, C, groups,
-                     (double)vox, (const float*)gamma, (const float*)beta, eps, (float*)scale, (float*)shift, (float*)mean, (float*)invstd);
-  dim3 grid((unsigned)((ovox + 255) / 256), C / 8, N);
-#define GRP(TT, NDV) hipLaunchKernelGGL((bn_relu_pool_fwd_kernel<TT, NDV>), grid, dim3(256), 0, (hipStream_t)stream, (const TT*)y, y_ss, (TT*)z, z_ss, (TT*)pooled, p_ss, (const float*)scale, (const float*)shift, Do, Ho, Wo, C)
-  if (dtype == 0) { if (nd == 3) GRP(f16, 3); else GRP(f16, 2); } else { if (nd == 3) GRP(bf16, 3); else GRP(bf16, 2); }
-#undef GRP
-  IUNET_CHECK_HIP(hipGetLastError());
-  return IUNET_OK;
+  return gn_relu_fwd_seq(dtype, nd, y, y_ss, z, z_ss, pooled, p_ss, gamma, beta, groups, eps, slab, rows, scale, shift, mean, invstd, C, N, vox,
+                         Do, Ho, Wo, stream);
 }
 
 // iunet_maxpool_bwd (add_skip) + iunet_gn_relu_bwd of an encoder stage's second conv in two passes instead of three (the GroupNorm form of
@@ -1672,22 +1574,9 @@ int iunet_gn_relu_pool_bwd(int dtype, int nd, const void* dskip, long long ds_ss
   IUNET_REQUIRE(C > 0 && C % 8 == 0 && C <= 1024 && N > 0 && Do > 0 && Ho > 0 && Wo > 0, "gn_relu_pool_bwd: bad shape");
   IUNET_REQUIRE(groups > 0 && C % groups == 0, "gn_relu_pool_bwd: %d channels do not split into %d groups", C, groups);
   const long long ovox = (long long)Do * Ho * Wo, vox = ovox * (nd == 3 ? 8 : 4);
-  const int per_block = BN_POOL_PER_BLOCK / (nd == 3 ? 8 : 4);
-  const int chunks = (int)((ovox + per_block - 1) / per_block);
-  IUNET_REQUIRE(chunks * N <= iunet_bn_bwd_num_parts(N, vox), "gn_relu_pool_bwd: slab part count");
-  dim3 g1(chunks, C / 8, N), g2((unsigned)((ovox + 255) / 256), C / 8, N);
-#define GPB(TT, NDV, PASSV, GRID, PB) hipLaunchKernelGGL((bn_pool_bwd_kernel<TT, NDV, PASSV, true>), GRID, dim3(256), 0, (hipStream_t)stream, \
-    (const TT*)dskip, ds_ss, (const TT*)dpool, dp_ss, (const TT*)y, y_ss, (TT*)dy, dy_ss, (const float*)mean, (const float*)invstd, \
-    (const float*)coef, (const float*)scale, (const float*)shift, C, Do, Ho, Wo, PB, (float*)slab, C)
-  if (dtype == 0) { if (nd == 3) GPB(f16, 3, 1, g1, per_block); else GPB(f16, 2, 1, g1, per_block); }
-  else { if (nd == 3) GPB(bf16, 3, 1, g1, per_block); else GPB(bf16, 2, 1, g1, per_block); }
-  hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(groups), dim3(1024), 0, (hipStream_t)stream, (const float*)slab, chunks, C, groups, N,
-                     (double)vox, (const float*)gamma, (const float*)invstd, (float*)dgamma, (float*)dbeta, (float*)coef);
-  if (dtype == 0) { if (nd == 3) GPB(f16, 3, 2, g2, 256); else GPB(f16, 2, 2, g2, 256); }
-  else { if (nd == 3) GPB(bf16, 3, 2, g2, 256); else GPB(bf16, 2, 2, g2, 256); }
-#undef GPB
-  IUNET_CHECK_HIP(hipGetLastError());
-  return IUNET_OK;
+  IUNET_REQUIRE(norm_pool_chunks(nd, ovox) * N <= iunet_bn_bwd_num_parts(N, vox), "gn_relu_pool_bwd: slab part count");
+  return norm_relu_bwd(OneSrc{dskip, ds_ss, nullptr, 0}, NormBwd{dtype, y, y_ss, dy, dy_ss, mean, invstd, gamma, scale, shift, dgamma, dbeta, slab,
+                                                                 coef, C, N, vox, groups, 0, nd, dpool, dp_ss, Do, Ho, Wo}, stream);
 }
 
 // iunet_maxpool_bwd (add_skip) + iunet_bn_relu_bwd of an encoder stage's second conv in two passes instead of three: dskip is
@@ -1701,22 +1590,9 @@ int iunet_bn_relu_pool_bwd(int dtype, int nd, const void* dskip, long long ds_ss
   IUNET_REQUIRE(dskip && dpool && y && dy && slab && coef && scale && shift, "bn_relu_pool_bwd: null pointer");
   IUNET_REQUIRE(nd == 2 || nd == 3, "bn_relu_pool_bwd: nd must be 2 or 3");
   const long long ovox = (long long)Do * Ho * Wo, vox = ovox * (nd == 3 ? 8 : 4);
-  const int per_block = BN_POOL_PER_BLOCK / (nd == 3 ? 8 : 4);             // pooled voxels per workgroup (fewer parts than bn_relu_bwd's slab holds)
-  const int chunks = (int)((ovox + per_block - 1) / per_block);
-  IUNET_REQUIRE(chunks * N <= iunet_bn_bwd_num_parts(N, vox), "bn_relu_pool_bwd: slab part count");
-  dim3 g1(chunks, C / 8, N), g2((unsigned)((ovox + 255) / 256), C / 8, N);
-#define BPB(TT, NDV, PASSV, GRID, PB) hipLaunchKernelGGL((bn_pool_bwd_kernel<TT, NDV, PASSV>), GRID, dim3(256), 0, (hipStream_t)stream, \
-    (const TT*)dskip, ds_ss, (const TT*)dpool, dp_ss, (const TT*)y, y_ss, (TT*)dy, dy_ss, (const float*)mean, (const float*)invstd, \
-    (const float*)coef, (const float*)scale, (const float*)shift, C, Do, Ho, Wo, PB, (float*)slab)
-  if (dtype == 0) { if (nd == 3) BPB(f16, 3, 1, g1, per_block); else BPB(f16, 2, 1, g1, per_block); }
-  else { if (nd == 3) BPB(bf16, 3, 1, g1, per_block); else BPB(bf16, 2, 1, g1, per_block); }
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, (const float*)slab, chunks * N, C,
-                     (double)N * (double)vox, (const float*)gamma, (const float*)invstd, (float*)dgamma, (float*)dbeta, (float*)coef);
-  if (dtype == 0) { if (nd == 3) BPB(f16, 3, 2, g2, 256); else BPB(f16, 2, 2, g2, 256); }
-  else { if (nd == 3) BPB(bf16, 3, 2, g2, 256); else BPB(bf16, 2, 2, g2, 256); }
-#undef BPB
-  IUNET_CHECK_HIP(hipGetLastError());
-  return IUNET_OK;
+  IUNET_REQUIRE(norm_pool_chunks(nd, ovox) * N <= iunet_bn_bwd_num_parts(N, vox), "bn_relu_pool_bwd: slab part count");
+  return norm_relu_bwd(OneSrc{dskip, ds_ss, nullptr, 0}, NormBwd{dtype, y, y_ss, dy, dy_ss, mean, invstd, gamma, scale, shift, dgamma, dbeta, slab,
+                                                                 coef, C, N, vox, 0, 0, nd, dpool, dp_ss, Do, Ho, Wo}, stream);
 }
 
 int iunet_maxpool_bwd(int dtype, int nd, const void* z, long long z_ss, const void* dpool, long long dp_ss, void* dz,
@@ -1930,12 +1806,7 @@ static int head_norm_bwd_impl(int dtype, const void* y, long long y_ss, int C0, 
     default: hipLaunchKernelGGL((head_bn_bwd_kernel<TT, 4, 1, PLN>), grid, dim3(PLN * 64), 0, (hipStream_t)stream, p); break; }
   if (dtype == 0) { if (C0 == 32) { HBB(f16, 4) } else { HBB(f16, 8) } } else { if (C0 == 32) { HBB(bf16, 4) } else { HBB(bf16, 8) } }
 #undef HBB
-  if (groups > 0)      // the rows of pass 1 are [sample][chunk][C0][2]: gn_bwd_finalize_kernel's slab
-    hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(groups), dim3(1024), 0, (hipStream_t)stream, (const float*)bnslab, chunks, C0, groups, N,
-                       (double)vox, (const float*)gamma, (const float*)invstd, (float*)dgamma, (float*)dbeta, (float*)bncoef);
-  else
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C0), dim3(256), 0, (hipStream_t)stream, (const float*)bnslab, chunks * N, C0,
-                       (double)N * (double)vox, (const float*)gamma, (const float*)invstd, (float*)dgamma, (float*)dbeta, (float*)bncoef);
+  norm_bwd_finalize(groups, bnslab, chunks, chunks * N, C0, N, vox, gamma, invstd, dgamma, dbeta, bncoef, stream);
   dim3 g2((unsigned)((vox + 511) / 512), C0 / 8, N);
 #define HBA(TT, PLN, GNV) switch (ncls) { case 2: hipLaunchKernelGGL((head_bn_apply_kernel<TT, 2, PLN, GNV>), g2, dim3(256), 0, (hipStream_t)stream, p); break; \
     case 3: hipLaunchKernelGGL((head_bn_apply_kernel<TT, 3, PLN, GNV>), g2, dim3(256), 0, (hipStream_t)stream, p); break; \
@@ -2015,44 +1886,14 @@ int iunet_bn_relu_sum_bwd(int dtype, int nd, int K, const void* const* srcs, con
   }
   IUNET_REQUIRE(al(y) && y_ss % 8 == 0 && y_ss >= C * vox && (!dy || (al(dy) && dy_ss % 8 == 0 && dy_ss >= C * vox)),
                 "bn_relu_sum_bwd: y / dy alignment or sample stride");
+  NormBwd a{dtype, y, y_ss, dy, dy_ss, mean, invstd, gamma, scale, shift, dgamma, dbeta, slab, coef, C, N, vox, 0, 0, nd};
   if (dpool) {
     IUNET_REQUIRE(H % 2 == 0 && W % 2 == 0 && (nd == 2 || D % 2 == 0), "bn_relu_sum_bwd: odd grid %d x %d x %d under a max-pool", D, H, W);
-    const int Do = nd == 3 ? D / 2 : 1, Ho = H / 2, Wo = W / 2;
-    const long long ovox = (long long)Do * Ho * Wo;
-    IUNET_REQUIRE(al(dpool) && dp_ss % 8 == 0 && dp_ss >= C * ovox, "bn_relu_sum_bwd: dpool alignment or sample stride");
-    const int per_block = BN_POOL_PER_BLOCK / (nd == 3 ? 8 : 4);
-    const int chunks = (int)((ovox + per_block - 1) / per_block);
-    dim3 g1(chunks, C / 8, N), g2((unsigned)((ovox + 255) / 256), C / 8, N);
-#define BSP(TT, NDV, PASSV, GRID, PB) hipLaunchKernelGGL((bn_sum_pool_bwd_kernel<TT, NDV, PASSV>), GRID, dim3(256), 0, (hipStream_t)stream, \
-    s, (const TT*)dpool, dp_ss, (const TT*)y, y_ss, (TT*)dy, dy_ss, (const float*)mean, (const float*)invstd, \
-    (const float*)coef, (const float*)scale, (const float*)shift, C, Do, Ho, Wo, PB, (float*)slab)
-    if (dtype == 0) { if (nd == 3) BSP(f16, 3, 1, g1, per_block); else BSP(f16, 2, 1, g1, per_block); }
-    else { if (nd == 3) BSP(bf16, 3, 1, g1, per_block); else BSP(bf16, 2, 1, g1, per_block); }
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, (const float*)slab, chunks * N, C,
-                       (double)N * (double)vox, (const float*)gamma, (const float*)invstd, (float*)dgamma, (float*)dbeta, (float*)coef);
-    if (dtype == 0) { if (nd == 3) BSP(f16, 3, 2, g2, 256); else BSP(f16, 2, 2, g2, 256); }
-    else { if (nd == 3) BSP(bf16, 3, 2, g2, 256); else BSP(bf16, 2, 2, g2, 256); }
-#undef BSP
-    IUNET_CHECK_HIP(hipGetLastError());
-    return IUNET_OK;
+    a.Do = nd == 3 ? D / 2 : 1; a.Ho = H / 2; a.Wo = W / 2;
+    IUNET_REQUIRE(al(dpool) && dp_ss % 8 == 0 && dp_ss >= C * ((long long)a.Do * a.Ho * a.Wo), "bn_relu_sum_bwd: dpool alignment or sample stride");
+    a.dpool = dpool; a.dp_ss = dp_ss;
   }
-  const int per_block = BN_BWD_PER_BLOCK;
-  const int chunks = (int)((vox + per_block - 1) / per_block);
-  dim3 g1(chunks, C / 8, N);
-#define BSR(TT) hipLaunchKernelGGL(bn_sum_bwd_reduce_kernel<TT>, g1, dim3(256), 0, (hipStream_t)stream, s, (const TT*)y, y_ss, \
-    (const float*)mean, (const float*)invstd, (const float*)scale, (const float*)shift, C, vox, per_block, (float*)slab)
-  if (dtype == 0) BSR(f16); else BSR(bf16);
-#undef BSR
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, (const float*)slab, chunks * N, C,
-                     (double)N * (double)vox, (const float*)gamma, (const float*)invstd, (float*)dgamma, (float*)dbeta, (float*)coef);
-  if (dy == nullptr) { IUNET_CHECK_HIP(hipGetLastError()); return IUNET_OK; }
-  dim3 g2((unsigned)((vox + 511) / 512), C / 8, N);
-#define BSA(TT) hipLaunchKernelGGL(bn_sum_bwd_apply_kernel<TT>, g2, dim3(256), 0, (hipStream_t)stream, s, (const TT*)y, y_ss, \
-    (TT*)dy, dy_ss, (const float*)mean, (const float*)invstd, (const float*)coef, (const float*)scale, (const float*)shift, vox)
-  if (dtype == 0) BSA(f16); else BSA(bf16);
-#undef BSA
-  IUNET_CHECK_HIP(hipGetLastError());
-  return IUNET_OK;
+  return norm_relu_bwd(s, a, stream);
 }
 
 }  // extern "C"
