@@ -1,0 +1,143 @@
+"""Placement of a kernel test's device operands inside larger, sentinel-filled allocations.
+
+The networks never hand a kernel a tight, exactly sized buffer: an activation is a half of a concat buffer, a gradient a slot of
+a multi-slot buffer, the sample stride is anything that keeps 16-byte alignment.  A kernel test that allocates through this module
+gives every operand a PLACEMENT -- `lead` elements into an allocation, samples `ss` elements apart -- and afterwards checks that
+  (a) the logical contents are what the reference says (`Operand.logical`),
+  (b) every element outside the logical extents of the samples still holds the sentinel bits (`Operand.check_outside`),
+  (c) an input's whole allocation is bit-identical to what it was before the call (`Operand.check_unchanged`).
+The sentinel is a NaN of the element type (0x7FA5 in f16 and bf16, 0x7FA5A5A5 in fp32; 0xA5 for bytes), so a halo load that strays
+into the gap between two samples shows in the result even when it meets a zero weight, and an output element nobody wrote is a NaN
+in the comparison.  Nothing here provokes a fault: every access a correct or a stride-confused kernel makes stays inside the
+allocation as long as it stays within one sample stride of the operand, which is what the bands at both ends are for.
+
+No GPU is needed to import this module; the device is only touched when an Operand is created with device='cuda'."""
+import torch
+
+SENTINEL = {torch.float16: 0x7FA5, torch.bfloat16: 0x7FA5, torch.float32: 0x7FA5A5A5, torch.uint8: 0xA5}
+INT_VIEW = {torch.float16: torch.int16, torch.bfloat16: torch.int16, torch.float32: torch.int32, torch.uint8: torch.uint8}
+BAND = 8 * 256            # sentinel elements in front of the first and behind the last sample, whatever the placement
+
+PLACEMENTS = ('tight', 'gap', 'upper', 'lower')
+
+
+def placement(kind, per):
+    """(ss, lead) of a placement for an operand of `per` = C * vox elements per sample.  Strides stay multiples of 8 elements
+    (16 bytes in the 16-bit types): all the blocked layout and the networks guarantee."""
+    if kind == 'tight':
+        return per, 0
+    if kind == 'gap':
+        return per + 8 * 37, 8 * 5
+    if kind == 'upper':       # the second half of a two-slot (concat) buffer
+        return 2 * per, per
+    if kind == 'lower':       # its mirror image
+        return 2 * per, 0
+    raise ValueError(f'unknown placement {kind!r}: {PLACEMENTS}')
+
+
+def bits(t):
+    """The integer view on which every comparison of this module is made (NaN payloads compare like any other bits)."""
+    return t.contiguous().view(INT_VIEW[t.dtype])
+
+
+def sentinel_filled(n, dtype, device='cpu'):
+    iv = INT_VIEW[dtype]
+    s = SENTINEL[dtype]
+    if iv == torch.int16 and s >= 1 << 15:
+        s -= 1 << 16
+    return torch.full((n,), s, dtype=iv, device=device).view(dtype)
+
+
+class Operand:
+    """N samples of `per` elements each, placed in one allocation: [band | lead | sample 0 | ... ] with samples `ss` apart.
+    data: a CPU tensor of N * per elements (an input), or None (an output or scratch: the logical extents hold the sentinel
+    too, so an unwritten element is a NaN).  `t` is the device view that starts at sample 0: pass its pointer and `ss`."""
+
+    def __init__(self, N, per, dtype, place='tight', data=None, device='cuda', name='operand', band=BAND):
+        self.N, self.per, self.dtype, self.place, self.name, self.band = N, int(per), dtype, place, name, band
+        self.ss, self.lead = placement(place, self.per)
+        self.total = band + N * self.ss + band
+        host = sentinel_filled(self.total, dtype)
+        self.inside = torch.zeros(self.total, dtype=torch.bool)
+        for n in range(N):
+            a = self.start(n)
+            self.inside[a:a + self.per] = True
+            if data is not None:
+                host[a:a + self.per] = data.reshape(N, self.per)[n].to(dtype)
+        self.is_input = data is not None
+        self.before = bits(host).clone()
+        self.buf = host.to(device)
+        self.t = self.buf[band + self.lead:]
+
+    def start(self, n):
+        return self.band + self.lead + n * self.ss
+
+    def host(self):
+        return self.buf.cpu()
+
+    def logical(self):
+        """The operand's contents, [N, per] on the CPU."""
+        h = self.host()
+        return torch.stack([h[self.start(n):self.start(n) + self.per] for n in range(self.N)])
+
+    def _where(self, i):
+        """Offset i of the allocation relative to the nearest sample."""
+        n = min(range(self.N), key=lambda k: min(abs(i - self.start(k)), abs(i - (self.start(k) + self.per - 1))))
+        rel = i - self.start(n)
+        side = 'before the start' if rel < 0 else 'past the end'
+        d = -rel if rel < 0 else rel - self.per + 1
+        return f'{d} elements {side} of sample {n} (allocation offset {i}, ss {self.ss}, lead {self.lead}, per {self.per})'
+
+    def check_outside(self):
+        """(b): nothing outside the samples' logical extents was written."""
+        now = bits(self.host())
+        bad = (now != self.before) & ~self.inside
+        if bool(bad.any()):
+            i = int(bad.nonzero()[0])
+            raise AssertionError(f'{self.name} [{self.place}]: {int(bad.sum())} sentinel elements overwritten, the first {self._where(i)}: '
+                                 f'bits {int(now[i]) & 0xFFFFFFFF:#x}')
+
+    def check_unchanged(self):
+        """(c): an input is bit-identical to what it was before the call, gaps and bands included."""
+        now = bits(self.host())
+        bad = now != self.before
+        if bool(bad.any()):
+            i = int(bad.nonzero()[0])
+            what = 'inside' if bool(self.inside[i]) else 'outside'
+            raise AssertionError(f'{self.name} [{self.place}]: input modified ({int(bad.sum())} elements), the first {what} the samples, '
+                                 f'{self._where(i)}')
+
+    def check(self):
+        if self.is_input:
+            self.check_unchanged()
+        else:
+            self.check_outside()
+
+
+def scratch(nelems, dtype=torch.float32, device='cuda', name='scratch'):
+    """Scratch of exactly the size the library reports, sentinel-filled (a NaN: a row the entry point leaves unwritten shows in what
+    is reduced from it), with a band behind and in front that check_outside() watches."""
+    return Operand(1, nelems, dtype, 'tight', None, device, name)
+
+
+class StridedInput:
+    """A caller's planar tensor [N, C, D, H, W] as a strided view of a larger one (row, plane, channel and sample pitch larger than
+    the extents), the way the first conv reads it; the surroundings hold the sentinel and the whole thing is an input."""
+
+    def __init__(self, x, pad=(1, 2, 3, 5), device='cuda', name='x'):
+        N, C, D, H, W = x.shape
+        pc, pd, ph, pw = pad
+        big = sentinel_filled(N * (C + pc) * (D + pd) * (H + ph) * (W + pw) + 2 * 64, x.dtype)
+        body = big[64:-64].view(N, C + pc, D + pd, H + ph, W + pw)
+        body[:, :C, :D, :H, :W] = x
+        self.name = name
+        self.before = bits(big).clone()
+        self.buf = big.to(device)
+        self.t = self.buf[64:]
+        self.strides = tuple(body.stride())
+
+    def check(self):
+        now = bits(self.buf.cpu())
+        bad = now != self.before
+        if bool(bad.any()):
+            raise AssertionError(f'{self.name}: strided input modified, first at allocation offset {int(bad.nonzero()[0])}')

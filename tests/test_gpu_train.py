@@ -249,12 +249,18 @@ def test_head_loss_act_variants_equal_the_materialised_path(nv, C0, ncls, dtype)
     assert res[0][2].float().abs().max() > 0
 
 
-def _head_loss_case(nv, kind, weighted, C0, ncls, shape):
+def _head_loss_case(nv, kind, weighted, C0, ncls, shape, dtype=torch.float16, N=2, places=None, act=False, dx_check=None):
+    """Fused head + softmax + loss, forward and backward, against torch autograd on the CPU and oracle/metrics_ref.py.
+    places: None = plain, exactly sized buffers and an fp32 reference (the tests of this file); else placement rows of tests/arena.py
+    for x and dx (the first row all tight): the reference is float64, every row must give the bits of the first, bands and inputs are
+    checked.  act: the _act entry points on the raw tensor y with (in_scale, in_shift); the head sees round(relu(in_scale y + in_shift)).
+    dx_check(got, ref): the assertion on the 16-bit dx (default: 2e-3 of its maximum)."""
     from interactive_unet.train_engine import LOSS_KINDS
+    from tests.arena import Operand, bits, scratch
     g = torch.Generator().manual_seed(16)
-    N = 2
+    ft = torch.float32 if places is None else torch.float64
     vox = shape[0] * shape[1]
-    x = torch.randn((N, C0) + shape, generator=g).half().float()
+    x = torch.randn((N, C0) + shape, generator=g).to(dtype).to(ft)
     w = torch.randn(ncls, C0, generator=g) * 0.3
     b = torch.randn(ncls, generator=g) * 0.1
     lab = torch.randint(0, ncls, (N,) + shape, generator=g)
@@ -264,42 +270,77 @@ def _head_loss_case(nv, kind, weighted, C0, ncls, shape):
         wt = (torch.rand((N, 1) + shape, generator=g) > 0.3).float().repeat(1, ncls, 1, 1) * \
             (0.5 + torch.rand((N, 1) + shape, generator=g)).repeat(1, ncls, 1, 1)
         y = y * (wt > 0)
+    raw = x
+    if act:
+        in_scale, in_shift = 0.5 + torch.rand(C0, generator=g), 0.4 * torch.randn(C0, generator=g)
+        x = F.relu(in_scale.to(ft).view(1, -1, 1, 1) * raw + in_shift.to(ft).view(1, -1, 1, 1)).to(dtype).to(ft)
     xr = x.clone().requires_grad_(True)
-    wr, br = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+    wr, br = w.to(ft).clone().requires_grad_(True), b.to(ft).clone().requires_grad_(True)
     logits = F.conv2d(xr, wr.view(ncls, C0, 1, 1), bias=br)
     p = torch.softmax(logits, 1)
     want = metrics_ref.loss(kind, p.detach().numpy(), y.numpy(), None if wt is None else wt.numpy(), axes=(0, 2, 3))
     gp = torch.tensor(metrics_ref.loss_grad(kind, p.detach().numpy(), y.numpy(), None if wt is None else wt.numpy(),
-                                            axes=(0, 2, 3))).float()
+                                            axes=(0, 2, 3))).to(ft)
     p.backward(gp)
     dev = 'cuda'
-    xb = blocked(x, torch.float16).to(dev)
+    code = nv.DTYPE_CODE[dtype]
     wd, bd, yd = w.to(dev), b.to(dev), y.to(dev).contiguous()
     wtd = None if wt is None else wt.to(dev).contiguous()
+    sd, hd = (in_scale.to(dev), in_shift.to(dev)) if act else (None, None)
     nparts = nv.lib().iunet_head_loss_num_parts(N, vox)
-    lslab = torch.empty(nparts * ncls * 8, device=dev)
-    out4, coef = torch.empty(4, device=dev), torch.empty(ncls * 3, device=dev)
-    nv.call('iunet_head_loss_fwd', 0, nv.ptr(xb), C0 * vox, C0, nv.ptr(wd), nv.ptr(bd), ncls, nv.ptr(yd), nv.ptr(wtd), 0,
-            LOSS_KINDS[kind], nv.ptr(lslab), nv.ptr(out4), nv.ptr(coef), N, vox, nv.stream())
-    dx = torch.empty_like(xb)
     nparts_b = nv.lib().iunet_head_loss_bwd_num_parts(N, vox, ncls, C0)
-    hslab = torch.empty(nparts_b * ncls * (C0 + 1), device=dev)
-    nv.call('iunet_head_loss_bwd', 0, nv.ptr(xb), C0 * vox, C0, nv.ptr(wd), nv.ptr(bd), ncls, nv.ptr(yd), nv.ptr(wtd), 0,
-            nv.ptr(coef), 1.0, nv.ptr(dx), C0 * vox, nv.ptr(hslab), N, vox, nv.stream())
-    htmp = torch.empty(ncls * (C0 + 1), device=dev)
-    nv.call('iunet_reduce_slab', nv.ptr(hslab), nparts_b, ncls * (C0 + 1), nv.ptr(htmp), 1.0, 0, nv.stream())
-    torch.cuda.synchronize()
-    o = out4.cpu()
+    first = None
+    for row, pl in enumerate(places or [None]):
+        if places is None:
+            xb = blocked(raw, dtype).to(dev)
+            x_t, x_ss, dx, dx_ss = xb, C0 * vox, torch.empty_like(xb), C0 * vox
+            lslab, out4, coef = torch.empty(nparts * ncls * 8, device=dev), torch.empty(4, device=dev), torch.empty(ncls * 3, device=dev)
+            hslab, htmp = torch.empty(nparts_b * ncls * (C0 + 1), device=dev), torch.empty(ncls * (C0 + 1), device=dev)
+            ops = []
+        else:
+            pl = {k: 'tight' for k in places[-1]} if row == 0 else pl
+            xo = Operand(N, C0 * vox, dtype, pl['x'], blocked(raw.float(), dtype), name='x')
+            dxo = Operand(N, C0 * vox, dtype, pl['dx'], None, name='dx')
+            sc = [scratch(n, name=k) for k, n in (('loss slab', nparts * ncls * 8), ('out4', 4), ('coef', ncls * 3),
+                                                  ('dW slab', nparts_b * ncls * (C0 + 1)), ('dW', ncls * (C0 + 1)))]
+            x_t, x_ss, dx, dx_ss = xo.t, xo.ss, dxo.t, dxo.ss
+            lslab, out4, coef, hslab, htmp = [o.t for o in sc]
+            ops = [xo, dxo] + sc
+        if act:
+            nv.call('iunet_head_loss_fwd_act', code, nv.ptr(x_t), x_ss, C0, nv.ptr(wd), nv.ptr(bd), ncls, nv.ptr(yd), nv.ptr(wtd), 0,
+                    LOSS_KINDS[kind], nv.ptr(lslab), nv.ptr(out4), nv.ptr(coef), nv.ptr(sd), nv.ptr(hd), N, vox, nv.stream())
+            nv.call('iunet_head_loss_bwd_act', code, nv.ptr(x_t), x_ss, C0, nv.ptr(wd), nv.ptr(bd), ncls, nv.ptr(yd), nv.ptr(wtd), 0,
+                    nv.ptr(coef), 1.0, nv.ptr(dx), dx_ss, nv.ptr(hslab), nv.ptr(sd), nv.ptr(hd), N, vox, nv.stream())
+        else:
+            nv.call('iunet_head_loss_fwd', code, nv.ptr(x_t), x_ss, C0, nv.ptr(wd), nv.ptr(bd), ncls, nv.ptr(yd), nv.ptr(wtd), 0,
+                    LOSS_KINDS[kind], nv.ptr(lslab), nv.ptr(out4), nv.ptr(coef), N, vox, nv.stream())
+            nv.call('iunet_head_loss_bwd', code, nv.ptr(x_t), x_ss, C0, nv.ptr(wd), nv.ptr(bd), ncls, nv.ptr(yd), nv.ptr(wtd), 0,
+                    nv.ptr(coef), 1.0, nv.ptr(dx), dx_ss, nv.ptr(hslab), N, vox, nv.stream())
+        nv.call('iunet_reduce_slab', nv.ptr(hslab), nparts_b, ncls * (C0 + 1), nv.ptr(htmp), 1.0, 0, nv.stream())
+        torch.cuda.synchronize()
+        for o in ops:
+            o.check()
+        o = out4[:4].cpu()
+        dxl = dx.cpu() if places is None else dxo.logical().reshape(-1)
+        ht = htmp[:ncls * (C0 + 1)].cpu()
+        if first is None:
+            first = (o, coef[:ncls * 3].cpu(), dxl, ht)
+        else:
+            for k, (u, v) in enumerate(zip(first, (o, coef[:ncls * 3].cpu(), dxl, ht))):
+                assert torch.equal(bits(u), bits(v)), f'placement {pl} changes output {k}'
+    o, _, dxl, ht = first
     assert abs(o[0].item() - want) <= 2e-5 * max(1.0, abs(want)), (o[0].item(), want)
     r = metrics_ref.rounded_metrics(p.detach().numpy(), y.numpy(), None if wt is None else wt.numpy(), axes=(0, 2, 3))
     assert np.allclose(o[1:].numpy(), r, atol=2e-5)
-    gx = unblocked(dx.float().cpu(), N, C0, shape)
-    scale = xr.grad.abs().max().item()
-    assert (gx - xr.grad).abs().max() <= 2e-3 * scale + 1e-9        # dx is stored in fp16
-    ht = htmp.cpu()
+    gx = unblocked(dxl.float(), N, C0, shape)
+    if dx_check is not None:
+        dx_check(gx, xr.grad)
+    else:
+        scale = xr.grad.abs().max().item()
+        assert (gx - xr.grad).abs().max() <= 2e-3 * scale + 1e-9        # dx is stored in fp16
     gw = ht[:ncls * C0].view(C0 // 8, ncls, 8).permute(1, 0, 2).reshape(ncls, C0)     # slab: [planes][ncls][8], then [ncls]
-    assert torch.allclose(gw, wr.grad, rtol=1e-3, atol=1e-5 * max(1.0, wr.grad.abs().max().item()))
-    assert torch.allclose(ht[ncls * C0:], br.grad, rtol=1e-3, atol=1e-6)
+    assert torch.allclose(gw.to(ft), wr.grad, rtol=1e-3, atol=1e-5 * max(1.0, wr.grad.abs().max().item()))
+    assert torch.allclose(ht[ncls * C0:].to(ft), br.grad, rtol=1e-3, atol=1e-6)
 
 
 def test_adamw_matches_torch(nv):
