@@ -12,6 +12,8 @@ in the comparison.  Nothing here provokes a fault: every access a correct or a s
 allocation as long as it stays within one sample stride of the operand, which is what the bands at both ends are for.
 
 No GPU is needed to import this module; the device is only touched when an Operand is created with device='cuda'."""
+import ctypes
+
 import torch
 
 SENTINEL = {torch.float16: 0x7FA5, torch.bfloat16: 0x7FA5, torch.float32: 0x7FA5A5A5, torch.uint8: 0xA5}
@@ -118,6 +120,18 @@ def scratch(nelems, dtype=torch.float32, device='cuda', name='scratch'):
     """Scratch of exactly the size the library reports, sentinel-filled (a NaN: a row the entry point leaves unwritten shows in what
     is reduced from it), with a band behind and in front that check_outside() watches."""
     return Operand(1, nelems, dtype, 'tight', None, device, name)
+
+
+def source_tables(operands):
+    """The pointer table and the sample-stride table (`const void* const*`, `const long long*`) of the entry points that read several
+    sources in one launch (iunet_sf_gemm, iunet_sf_wgrad), from one Operand per source: each at its own placement."""
+    n = len(operands)
+    return ((ctypes.c_void_p * n)(*[o.t.data_ptr() for o in operands]), (ctypes.c_longlong * n)(*[o.ss for o in operands]))
+
+
+def pointer_table(operands):
+    """A `const void* const*` table of small parameter vectors (one Operand each), e.g. the per-source prologue scales."""
+    return (ctypes.c_void_p * len(operands))(*[o.t.data_ptr() for o in operands])
 
 
 class StridedInput:
