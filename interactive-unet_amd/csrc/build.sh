@@ -14,7 +14,7 @@ for f in "$HERE"/*.hip; do
   objs+=("$o")
   stale=0
   if [ ! -f "$o" ] || [ "$f" -nt "$o" ]; then stale=1; fi
-  for h in "$HERE"/*.h; do                      # any shared header (common.h, pack_desc.h, x2_prep_desc.h ...) newer than the object
+  for h in "$HERE"/*.h "$HERE/../../include/iunet.h"; do   # any shared header (common.h, launchers.h ..., the public one) newer than the object
     if [ "$h" -nt "$o" ]; then stale=1; fi
   done
   if [ "$stale" = 1 ]; then
@@ -23,5 +23,5 @@ for f in "$HERE"/*.hip; do
   fi
 done
 for p in "${pids[@]}"; do wait "$p"; done
-hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libiunet.so" "${objs[@]}"
+hipcc --offload-arch=gfx950 -shared -fPIC -Wl,--no-undefined -o "$OUT/libiunet.so" "${objs[@]}"
 echo "built $OUT/libiunet.so"

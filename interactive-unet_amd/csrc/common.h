@@ -12,6 +12,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
+#include "../../include/iunet.h"      // the public entry points: every definition and every call is checked against the one declaration
+#include "launchers.h"                // the internal launchers and host helpers, likewise
 
 typedef _Float16 f16;
 typedef __bf16 bf16;
@@ -158,7 +160,6 @@ __device__ __forceinline__ float wave_sum(float v) {
 #define IUNET_ERR_UNSUPPORTED (-3)
 #define IUNET_ERR_WORKSPACE (-4)
 
-void iunet_set_error(const char* fmt, ...);
 #define IUNET_CHECK_HIP(expr)                                                        \
   do {                                                                               \
     hipError_t _e = (expr);                                                          \
@@ -420,4 +421,3 @@ __host__ __device__ inline int f8k_offset(int col, int dy, int m, int e, int o, 
       if (f8k_col(gg, qq) == col) { g = gg; q = qq; }
   return ((((g * 3 + dy) * 2 + m) * 2 + e) * 64 + q * 16 + row) * 16 + 8 * o;
 }
-int iunet_f8_k128(int taps, int Cin);        // conv3_f8k.hip: 1 = the K = 128 order (3-D, Cin % 32 == 0), 0 = the K16 order

@@ -21,10 +21,6 @@
 #include <cstdlib>
 #include <type_traits>
 
-int iunet_conv3_f8k_launch(int dtype, const void* x, long long x_sstride, void* y, long long y_sstride, const void* wpk,
-                           const float* wscale, const float* bias, int N, int D, int H, int W, int Cin, int Cout, int epi,
-                           int ksplit, float* partial, int small, int in8, int out8, hipStream_t stream);
-
 namespace {
 
 typedef long i64;

@@ -73,12 +73,6 @@ __global__ void pack_conv3_k16c_kernel(const float* __restrict__ w, const float*
 
 }  // namespace
 
-int iunet_conv3_v4_launch(int dtype, int nd, const void* x, long long x_sstride, void* y, long long y_sstride, const void* wpk,
-                          const float* bias, float* stats, int N, int D, int H, int W, int Cin, int Cout, int epi,
-                          const float* in_scale, const float* in_shift, hipStream_t stream, const void* bw_y = nullptr,
-                          long long bw_y_ss = 0, const float* const* bw_par = nullptr, int compact = 0, int per_sample = 0,
-                          int* query_rows = nullptr);
-
 // Host entry used by the net runtime and the per-kernel C ABI.  layout: 2 = the padded K16 operator, 3 = the compact one.
 int iunet_conv3_launch(int dtype, int nd, const void* x, long long x_sstride, void* y, long long y_sstride,
                        const void* wpk, const float* bias, float* stats, int N, int D, int H, int W, int Cin,

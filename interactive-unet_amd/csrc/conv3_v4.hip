@@ -35,9 +35,6 @@ extern "C" int iunet_v4_stamps_read(unsigned long long* out) {
 #endif
 // 16 zero bytes: the source of the halo pixels outside the image when the halo tile goes global -> LDS without registers
 __device__ __attribute__((aligned(16))) unsigned int g_v4_zero16[4] = {0u, 0u, 0u, 0u};
-int iunet_conv3_v4_stats_parts(int nd, int Cout);
-int iunet_conv3_v4_pairs(int nd, int N, int D, int H, int W, int Cin, int Cout, int bw);
-int iunet_conv3_v4_x2_pack_mode(int nd);
 
 namespace {
 

@@ -69,14 +69,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_block_kernel(const float* __
 
 }  // namespace
 
-int iunet_conv3_wgrad_v2_blocks(int N, int D, int H, int W, int Cin, int Cout);
-int iunet_conv3_wgrad_v2_launch(int dtype, const void* x, long long x_ss, const void* dy, long long dy_ss, float* slab,
-                                int N, int D, int H, int W, int Cin, int Cout, const float* x_scale, const float* x_shift,
-                                hipStream_t stream);
-int iunet_conv2_wgrad_v2_blocks(int N, int H, int W, int Cin, int Cout, int* rows);
-int iunet_conv2_wgrad_v2_launch(int dtype, const void* x, long long x_ss, const void* dy, long long dy_ss, float* slab, int N, int H, int W,
-                                int Cin, int Cout, const float* x_scale, const float* x_shift, hipStream_t stream);
-
 extern "C" {
 
 // number of slab rows (one or two per voxel-walking workgroup) of a (co, ci) block and the slab size they need

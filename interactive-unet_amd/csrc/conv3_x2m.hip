@@ -1355,8 +1355,6 @@ long long iunet_x2m_w8_bytes_nd(int nd, int Cout, int Cin) {
 
 /* operator of a 3x3x3 stage conv in the x2m form: whi = fp32 [Cout][Cin][27] holding w_hi (feed it to iunet_pack_conv3, dtype 0, mode 2),
  * w8 = iunet_x2m_w8_bytes bytes (the K128 operator of [w_hi8 | w_lo8]); oscale / bias_out as iunet_x2_prep */
-int iunet_x2m_prep_nd(int nd, const void* w, void* whi, void* w8, void* oscale, void* bias_out, const void* gamma, const void* beta,
-                      const void* mean, const void* var, float eps, float act_in, float act_out, int Cout, int Cin, void* stream);
 int iunet_x2m_prep(const void* w, void* whi, void* w8, void* oscale, void* bias_out, const void* gamma, const void* beta, const void* mean,
                    const void* var, float eps, float act_in, float act_out, int Cout, int Cin, void* stream) {
   return iunet_x2m_prep_nd(3, w, whi, w8, oscale, bias_out, gamma, beta, mean, var, eps, act_in, act_out, Cout, Cin, stream);
@@ -1421,9 +1419,6 @@ int iunet_x2m_maxpool_fwd(int nd, const void* x, long long x_ss, const void* x8,
  * x8: the m8 planes of the same tensor (x8_ss bytes per sample); y: Cout / 8 hi planes, the lo planes y_lo planes further on (y_lo < 0: no
  * lo planes -- a tensor only 3x3x3 convs read), y8: its m8 planes or null; w16 / w8 / oscale / bias from iunet_x2m_prep (+ iunet_pack_conv3);
  * epi as iunet_conv3_fwd; sat: optional device int, raised (atomicMax) to the bit pattern of a saturated hi word */
-int iunet_x2m_conv_fwd(int nd, const void* x, long long x_ss, const void* x8, long long x8_ss, void* y, long long y_ss, int y_lo, void* y8,
-                       long long y8_ss, const void* w16, const void* w8, const void* oscale, const void* bias, int N, int D, int H, int W,
-                       int Cin, int Cout, int epi, void* sat, void* stream);
 int iunet_x2m_conv3_fwd(const void* x, long long x_ss, const void* x8, long long x8_ss, void* y, long long y_ss, int y_lo, void* y8,
                         long long y8_ss, const void* w16, const void* w8, const void* oscale, const void* bias, int N, int D, int H, int W,
                         int Cin, int Cout, int epi, void* sat, void* stream) {

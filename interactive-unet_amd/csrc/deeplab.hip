@@ -23,7 +23,6 @@
 #include "common.h"
 #include "gather_gemm.h"
 #include "loss_terms.h"
-#include "../../include/iunet.h"
 
 namespace {
 

@@ -14,7 +14,6 @@
 // The forward GEMMs are gather_gemm.h's skeletons under the LkGather<ND, KIND> policy.
 #include "common.h"
 #include "gather_gemm.h"
-#include "../../include/iunet.h"
 
 namespace {
 

@@ -7,10 +7,6 @@
 #pragma once
 #include "common.h"
 
-// train_pointwise.hip: the loss / metrics / coefficient pass that every fused head + loss forward (16-bit, fp32, upsampled) ends with
-int iunet_loss_finalize_launch(const float* slab, int nparts, int ncls, int kind, int has_weight, double nvox_total, float* out4,
-                               float* coef, hipStream_t stream);
-
 namespace {
 
 __device__ __forceinline__ float load_t(const void* p, long long off, int dt) {

@@ -14,65 +14,6 @@
 #include <string>
 #include <vector>
 
-extern "C" {
-int iunet_x2_prep(const void*, void*, void*, void*, const void*, const void*, const void*, const void*, const void*, float, float, float,
-                  int, int, int, int, int, void*);
-int iunet_x2_first_conv_fwd(int, const void*, int, const long long*, void*, long long, int, const void*, const void*, const void*, float,
-                            int, int, int, int, int, int, int, void*);
-int iunet_x2_conv3_fwd(int, const void*, long long, int, void*, long long, int, const void*, const void*, const void*, int, int, int, int,
-                       int, int, int, void*);
-int iunet_x2_maxpool_fwd(int, const void*, long long, int, void*, long long, int, int, int, int, int, int, void*);
-int iunet_x2_convT_fwd(int, const void*, long long, int, void*, long long, int, const void*, const void*, const void*, int, int, int, int,
-                       int, int, void*);
-int iunet_x2_head_fwd(const void*, long long, int, int, const void*, const void*, float, int, void*, void*, void*, const long long*, float,
-                      int, int, int, int, int, void*);
-int iunet_x2m_prep_nd(int, const void*, void*, void*, void*, void*, const void*, const void*, const void*, const void*, float, float, float, int, int, void*);
-int iunet_x2m_conv_fwd(int, const void*, long long, const void*, long long, void*, long long, int, void*, long long, const void*, const void*,
-                       const void*, const void*, int, int, int, int, int, int, int, void*, void*);
-long long iunet_x2m_w8_bytes_nd(int, int, int);
-int iunet_x2m_head_fusable(int, int);
-int iunet_x2m_conv_head_fwd(int, const void*, long long, const void*, long long, const void*, const void*, const void*, const void*, const void*,
-                            const void*, float, int, void*, void*, void*, const long long*, float, int, int, int, int, int, int, void*, void*);
-int iunet_x2m_first_conv_fwd(int, const void*, int, const long long*, void*, long long, int, void*, long long, const void*, const void*, const void*,
-                             float, int, int, int, int, int, int, int, void*, void*);
-int iunet_x2m_convT_fwd(int, const void*, long long, int, void*, long long, int, void*, long long, const void*, const void*, const void*, int, int,
-                        int, int, int, int, void*, void*);
-int iunet_x2_conv3_fwd_flag(int, const void*, long long, int, void*, long long, int, const void*, const void*, const void*, int, int, int, int,
-                            int, int, int, void*, void*);
-int iunet_x2m_maxpool_fwd(int, const void*, long long, const void*, long long, void*, long long, void*, long long, int, int, int, int, int, void*);
-int iunet_x2m_pool_fusable(int, int);
-int iunet_x2m_first_stage_fusable(int, int, int, int, int, int);
-int iunet_x2m_first_stage_fwd(const void*, int, const long long*, const void*, const void*, const void*, float, void*, long long, int, void*, long long, void*,
-                              long long, void*, long long, const void*, const void*, const void*, const void*, int, int, int, void*, void*);
-int iunet_x2m_conv_pool_fwd(int, const void*, long long, const void*, long long, void*, long long, int, void*, long long, void*, long long, void*, long long,
-                            const void*, const void*, const void*, const void*, int, int, int, int, int, int, int, void*, void*);
-int iunet_x2m_conv3_fwd(const void*, long long, const void*, long long, void*, long long, int, void*, long long, const void*, const void*,
-                        const void*, const void*, int, int, int, int, int, int, int, void*, void*);
-long long iunet_x2m_w8_bytes(int, int);
-int iunet_pack_conv3(int, const void*, const void*, void*, int, int, int, int, void*);
-int iunet_pack_first_conv(int, const void*, const void*, void*, int, int, int, void*);
-int iunet_pack_convT(int, const void*, void*, int, int, int, void*);
-long long iunet_pack_conv3_elems(int, int, int, int);
-long long iunet_pack_first_conv_elems(int, int, int);
-int iunet_conv3_packs_compact(int, int);
-int iunet_conv3_plan(int, int, int, int, int, int, int, int, int, int, int*);
-int iunet_x2_pack_mode(int);
-int iunet_first_conv_fwd(int, int, const void*, int, const long long*, void*, long long, const void*, const void*, void*, int, int, int,
-                         int, int, int, int, void*);
-int iunet_conv3_fwd(int, int, const void*, long long, void*, long long, const void*, const void*, void*, int, int, int, int, int, int,
-                    int, int, void*);
-int iunet_maxpool_fwd(int, int, const void*, long long, void*, long long, int, int, int, int, int, void*);
-int iunet_convT_fwd(int, int, const void*, long long, void*, long long, const void*, const void*, int, int, int, int, int, int, void*);
-long long iunet_gn_precise_slab_bytes(int, int, long long);
-int iunet_x2_gn_relu_fwd(const void*, long long, int, void*, long long, int, const void*, const void*, int, float, float, void*, void*, void*, int, int,
-                         long long, void*, void*);
-int iunet_head_loss_num_parts(int, long long);
-int iunet_head_loss_fwd(int, const void*, long long, int, const void*, const void*, int, const void*, const void*, int, int, void*, void*,
-                        void*, int, long long, void*);
-int iunet_head_fwd(int, const void*, long long, int, const void*, const void*, int, void*, void*, void*, const long long*, float, int, int,
-                   int, int, int, void*);
-}
-
 namespace {
 
 // eval-mode BatchNorm fold of the 16-bit modes: scale = gamma / sqrt(var + eps), bias = beta - mean * scale, every operation rounded
@@ -262,7 +203,6 @@ extern "C" {
 
 /* mode: 0 fp16, 1 bf16, 2 fp16x2 (split precision), 3 fp16x2 with the cross terms of the stage convs on the fp8 matrix cores (3-D only);
  * act_scale: power of two (modes 2, 3; 0 = the default 64) */
-int iunet_net_create_ex(int dim, int levels, int base, int cin, int ncls, int mode, float act_scale, int norm, int groups, iunet_net** out);
 int iunet_net_create(int dim, int levels, int base, int cin, int ncls, int mode, float act_scale, iunet_net** out) {
   return iunet_net_create_ex(dim, levels, base, cin, ncls, mode, act_scale, 0, 8, out);
 }

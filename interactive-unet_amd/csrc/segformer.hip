@@ -23,7 +23,6 @@
 
 #include "common.h"
 #include "gather_gemm.h"
-#include "../../include/iunet.h"
 
 namespace {
 

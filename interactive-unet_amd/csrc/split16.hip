@@ -22,11 +22,6 @@
 #include "common.h"
 #include "x2_prep_desc.h"
 
-int iunet_conv3_v4_x2_launch(int nd, const void* x, long long x_sstride, int x_lo, void* y, long long y_sstride, int y_lo, const void* wpk,
-                             const float* oscale, const float* bias, int N, int D, int H, int W, int Cin, int Cout, int epi,
-                             int* sat, hipStream_t stream);
-int iunet_conv3_v4_x2_pack_mode(int nd);
-
 namespace {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -594,9 +589,6 @@ int iunet_x2_prep_batch(const void* table, int n, int rows, void* stream) {
 
 /* unet.py:65-69 first conv of the split-precision forward: the caller's tensor (strides, dtype as iunet_first_conv_fwd) ->
  * split(relu?(conv * oscale + bias)); w = iunet_pack_first_conv of the virtual operator with "Cin" = 3 Cin */
-int iunet_x2m_first_conv_fwd(int nd, const void* x, int in_dtype, const long long* in_strides, void* y, long long y_sstride, int y_lo,
-                             void* y8, long long y8_sstride, const void* w, const void* oscale, const void* bias, float act_scale, int N,
-                             int D, int H, int W, int Cin, int Cout, int relu, void* sat, void* stream);
 int iunet_x2_first_conv_fwd(int nd, const void* x, int in_dtype, const long long* in_strides, void* y, long long y_sstride, int y_lo,
                             const void* w, const void* oscale, const void* bias, float act_scale, int N, int D, int H, int W, int Cin,
                             int Cout, int relu, void* stream) {
@@ -671,8 +663,6 @@ int iunet_x2_maxpool_fwd(int nd, const void* x, long long x_ss, int x_lo, void* 
 }
 
 /* transposed conv k2 s2; wpk = iunet_pack_convT ("Cin" = 2 Cin) of iunet_x2_prep's transposed = 2 operator [2 Cin][Cout][npos] */
-int iunet_x2m_convT_fwd(int nd, const void* x, long long x_ss, int x_lo, void* y, long long y_ss, int y_lo, void* y8, long long y8_ss,
-                        const void* wpk, const void* oscale, const void* bias, int N, int D, int H, int W, int Cin, int Cout, void* sat, void* stream);
 int iunet_x2_convT_fwd(int nd, const void* x, long long x_ss, int x_lo, void* y, long long y_ss, int y_lo, const void* wpk,
                        const void* oscale, const void* bias, int N, int D, int H, int W, int Cin, int Cout, void* stream) {
   IUNET_REQUIRE(y_lo >= 0, "x2_convT: y_lo must not be negative");

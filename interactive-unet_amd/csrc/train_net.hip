@@ -17,87 +17,6 @@
 #include <string>
 #include <vector>
 
-extern "C" {
-int iunet_pack_batch(const void*, int, int, void*);
-int iunet_pack_desc_bytes(void);
-long long iunet_pack_conv3_elems(int, int, int, int);
-long long iunet_pack_first_conv_elems(int, int, int);
-int iunet_conv3_packs_compact(int, int);
-int iunet_conv3_plan(int, int, int, int, int, int, int, int, int, int, int*);
-int iunet_conv3_num_tiles(int, int, int, int, int);
-int iunet_conv3_stats_parts(int, int, int, int, int, int, int);
-int iunet_first_conv_fwd(int, int, const void*, int, const long long*, void*, long long, const void*, const void*, void*, int, int, int,
-                         int, int, int, int, void*);
-int iunet_conv3_fwd(int, int, const void*, long long, void*, long long, const void*, const void*, void*, int, int, int, int, int, int,
-                    int, int, void*);
-int iunet_conv3_fwd_act(int, int, const void*, long long, void*, long long, const void*, const void*, void*, const void*, const void*,
-                        int, int, int, int, int, int, int, int, void*);
-int iunet_convT_fwd(int, int, const void*, long long, void*, long long, const void*, const void*, int, int, int, int, int, int, void*);
-int iunet_bn_finalize(const void*, int, int, double, const void*, const void*, void*, void*, float, float, void*, void*, void*, void*, void*);
-int iunet_bn_relu_fwd(int, const void*, long long, void*, long long, const void*, const void*, int, int, long long, void*);
-int iunet_bn_relu_pool_fwd(int, int, const void*, long long, void*, long long, void*, long long, const void*, const void*, int, int, int,
-                           int, int, void*);
-int iunet_bn_bwd_num_parts(int, long long);
-int iunet_bn_relu_bwd(int, const void*, long long, const void*, long long, const void*, long long, void*, long long, const void*,
-                      const void*, const void*, const void*, const void*, void*, void*, void*, void*, int, int, long long, void*);
-int iunet_conv3_dgrad_bnstats_lay(int, int, const void*, long long, void*, long long, const void*, void*, const void*, long long, const void*,
-                                  const void*, const void*, const void*, int, int, int, int, int, int, int, void*);
-int iunet_bn_relu_bwd_apply(int, const void*, long long, const void*, long long, void*, long long, const void*, const void*, const void*,
-                            const void*, const void*, void*, void*, const void*, int, void*, int, int, long long, void*);
-int iunet_bn_relu_pool_bwd(int, int, const void*, long long, const void*, long long, const void*, long long, void*, long long, const void*,
-                           const void*, const void*, const void*, const void*, void*, void*, void*, void*, int, int, int, int, int, void*);
-int iunet_head_loss_num_parts(int, long long);
-int iunet_head_loss_fwd(int, const void*, long long, int, const void*, const void*, int, const void*, const void*, int, int, void*, void*,
-                        void*, int, long long, void*);
-int iunet_head_loss_fwd_act(int, const void*, long long, int, const void*, const void*, int, const void*, const void*, int, int, void*,
-                            void*, void*, const void*, const void*, int, long long, void*);
-int iunet_head_loss_bwd_num_parts(int, long long, int, int);
-int iunet_head_loss_bwd_dev(int, const void*, long long, int, const void*, const void*, int, const void*, const void*, int, const void*,
-                            const void*, void*, long long, void*, const void*, const void*, int, long long, void*);
-int iunet_head_grad_scatter(const void*, void*, void*, int, int, void*);
-int iunet_head_bn_bwd_ok(int, int);
-int iunet_head_gn_bwd(int, const void*, long long, int, const void*, const void*, int, const void*, const void*, int, const void*, float, const void*, const void*,
-                      const void*, const void*, const void*, const void*, int, void*, void*, void*, long long, void*, void*, void*, void*, int, long long, void*);
-int iunet_head_loss_fwd_act_ps(int, const void*, long long, int, const void*, const void*, int, const void*, const void*, int, int, void*, void*, void*,
-                               const void*, const void*, int, int, long long, void*);
-int iunet_head_bn_bwd(int, const void*, long long, int, const void*, const void*, int, const void*, const void*, int, const void*, float, const void*, const void*,
-                      const void*, const void*, const void*, const void*, void*, void*, void*, long long, void*, void*, void*, void*, int, long long, void*);
-int iunet_reduce_slab(void*, int, long long, void*, float, int, void*);
-long long iunet_conv3_wgrad_slab_floats(int, int, int, int, int, int, int);
-int iunet_conv3_wgrad(int, int, const void*, long long, const void*, long long, void*, void*, float, int, int, int, int, int, int, void*);
-int iunet_conv3_wgrad_act(int, int, const void*, long long, const void*, long long, void*, void*, float, const void*, const void*, int,
-                          int, int, int, int, int, void*);
-int iunet_convT_dgrad(int, int, const void*, long long, void*, long long, const void*, int, int, int, int, int, int, void*);
-int iunet_convT_wgrad_blocks(int, int, int, int, int, int, int);
-int iunet_convT_wgrad(int, int, const void*, long long, const void*, long long, void*, void*, void*, void*, int, int, int, int, int, int,
-                      void*);
-int iunet_first_conv_wgrad_blocks(int, int, int, int, int);
-int iunet_first_conv_wgrad_bn(int, int, const void*, int, const long long*, const void*, long long, const void*, long long, const void*,
-                              const void*, const void*, const void*, const void*, void*, void*, int, int, int, int, int, int, void*);
-int iunet_adamw_step_dev(void*, const void*, void*, void*, long long, float, float, float, float, float, void*, int, float, void*);
-int iunet_conv3_sample_stats_rows(int, int, int, int, int, int, int, int, int);
-int iunet_conv3_fwd_sample_stats(int, int, const void*, long long, void*, long long, const void*, void*, int, int, int, int, int, int, int, void*);
-int iunet_conv3_dgrad_sample_bnstats(int, int, const void*, long long, void*, long long, const void*, void*, const void*, long long, const void*, const void*,
-                                     const void*, const void*, int, int, int, int, int, int, int, void*);
-int iunet_gn_relu_bwd_rows(int, const void*, long long, const void*, long long, void*, long long, const void*, int, const void*, const void*, const void*,
-                           const void*, void*, void*, void*, int, void*, int, int, long long, void*);
-int iunet_gn_relu_fwd_rows(int, const void*, long long, void*, long long, const void*, const void*, int, float, void*, int, void*, void*, void*, void*, int, int,
-                           long long, void*);
-int iunet_gn_relu_pool_fwd_rows(int, int, const void*, long long, void*, long long, void*, long long, const void*, const void*, int, float, void*, int, void*,
-                                void*, void*, void*, int, int, int, int, int, void*);
-int iunet_gn_relu_fwd(int, const void*, long long, void*, long long, const void*, const void*, int, float, void*, void*, void*, void*, void*, int, int,
-                      long long, void*);
-int iunet_gn_relu_pool_fwd(int, int, const void*, long long, void*, long long, void*, long long, const void*, const void*, int, float, void*, void*,
-                           void*, void*, void*, int, int, int, int, int, void*);
-int iunet_gn_relu_bwd(int, const void*, long long, const void*, long long, void*, long long, const void*, int, const void*, const void*, const void*,
-                      const void*, void*, void*, void*, void*, int, int, long long, void*);
-int iunet_gn_relu_pool_bwd(int, int, const void*, long long, const void*, long long, const void*, long long, void*, long long, const void*, int,
-                           const void*, const void*, const void*, const void*, void*, void*, void*, void*, int, int, int, int, int, void*);
-int iunet_first_conv_wgrad(int, int, const void*, int, const long long*, const void*, long long, void*, void*, int, int, int, int, int, int, void*);
-int iunet_bn_relu_sum_bwd(int, int, int, const void* const*, const long long*, const void*, long long, const void*, long long, void*, long long,
-                          const void*, const void*, const void*, const void*, const void*, void*, void*, void*, void*, int, int, int, int, int, void*);
-}
-
 namespace {
 
 long long align256(long long v) { return (v + 255) & ~255ll; }
@@ -320,7 +239,6 @@ extern "C" {
 
 /* dtype: 0 fp16, 1 bf16 (the 16-bit training modes of interactive_unet.train_engine.TrainEngine); loss_kind: 0 ce, 1 dice, 2 iou, 3 mcc,
  * 4 dice_ce, 5 iou_ce, 6 mcc_ce (utils.py:458-475; the reference's default is mcc_ce, unet.py:17) */
-int iunet_train_create_ex(int dim, int levels, int base, int cin, int ncls, int dtype, int loss_kind, int norm, int groups, iunet_train** out);
 int iunet_train_create(int dim, int levels, int base, int cin, int ncls, int dtype, int loss_kind, iunet_train** out) {
   return iunet_train_create_ex(dim, levels, base, cin, ncls, dtype, loss_kind, 0, 8, out);
 }
@@ -507,10 +425,6 @@ int iunet_train_repack(iunet_train* n, void* stream) {
  * c, d, h, w), target / weight = [N][ncls][D*H*W] of tdtype (0 f32, 1 f16; weight may be null -- loader.py:142-154's batch contract).
  * Leaves loss_scale x dLoss/dparameter in the bound gradient vector, out4 = [Loss, Dice, IoU, MCC] (fp32 device pointer, optional),
  * the BatchNorm running statistics updated (momentum 0.1).  workspace: iunet_train_workspace_bytes. */
-typedef void (*iunet_train_hook)(void* ctx, int stage);
-int iunet_train_forward_backward_hooks(iunet_train* n, const void* x, int in_dtype, const long long* in_strides, const void* target,
-                                       const void* weight, int tdtype, int N, int D, int H, int W, void* workspace, void* out4,
-                                       iunet_train_hook hook, void* hook_ctx, void* stream);
 int iunet_train_forward_backward(iunet_train* n, const void* x, int in_dtype, const long long* in_strides, const void* target,
                                  const void* weight, int tdtype, int N, int D, int H, int W, void* workspace, void* out4, void* stream) {
   return iunet_train_forward_backward_hooks(n, x, in_dtype, in_strides, target, weight, tdtype, N, D, H, W, workspace, out4, nullptr, nullptr, stream);

@@ -4,7 +4,6 @@
 // per-block partial slabs summed in a fixed order (deterministic, no float atomics).
 #include "common.h"
 #include "loss_terms.h"
-#include "../../include/iunet.h"
 
 namespace {
 

@@ -6,6 +6,7 @@ fallback: if the shared library is missing or a call fails, this module raises.
 """
 import ctypes
 import os
+import re
 
 import torch
 
@@ -13,285 +14,68 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('IUNET_LIB') or os.path.join(os.path.dirname(_HERE), 'lib', 'libiunet.so')   # IUNET_LIB: A/B builds
 
 _lib = None
+_sigs = None
 
 c_void_p, c_int, c_ll, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
-_IP = ctypes.POINTER(c_int)
-_LP = ctypes.POINTER(c_ll)
-_VP = ctypes.POINTER(c_void_p)
-
-# name -> argtypes (all functions return int status except where noted)
-_SIGS = {
-    'iunet_abi_version': [],
-    'iunet_conv3_num_tiles': [c_int] * 5,
-    'iunet_conv3_stats_parts': [c_int] * 7,
-    'iunet_pack_conv3': [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_pack_first_conv': [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    'iunet_pack_convT': [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    'iunet_pack_batch': [c_void_p, c_int, c_int, c_void_p],
-    'iunet_conv3_fwd': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p,
-                        c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_conv3_pick_layout': [c_int] * 7,
-    'iunet_conv3_tile_pairs': [c_int] * 7,
-    'iunet_conv3_compact_ok': [c_int] * 9,
-    'iunet_conv3_packs_compact': [c_int] * 2,
-    'iunet_conv3_plan': [c_int] * 10 + [_IP],
-    'iunet_conv3_fwd_act': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                            c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_first_conv_fwd': [c_int, c_int, c_void_p, c_int, ctypes.POINTER(c_ll), c_void_p, c_ll, c_void_p, c_void_p,
-                             c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_maxpool_fwd': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_convT_fwd': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p,
-                        c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_head_fwd': [c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                       ctypes.POINTER(c_ll), c_float, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    # ---- fp32 parity mode
-    'iunet_f32_pack_conv': [c_void_p] * 7 + [c_float, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_f32_conv_fwd': [c_int, c_void_p, c_int, ctypes.POINTER(c_ll), c_void_p, c_ll, c_void_p, c_void_p,
-                           c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_f32_maxpool_fwd': [c_int, c_void_p, c_ll, c_void_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_f32_head_fwd': [c_void_p, c_ll, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                           ctypes.POINTER(c_ll), c_float, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    # ---- fp32 parity form of the training step (csrc/train_f32.hip)
-    'iunet_f32_bn_stats': [c_void_p, c_ll, c_int, c_int, c_ll, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    'iunet_f32_bn_relu_fwd': [c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_ll, c_void_p],
-    'iunet_f32_bn_relu_bwd': [c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                              c_int, c_int, c_ll, c_void_p],
-    'iunet_f32_maxpool_bwd': [c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_f32_wgrad_splits': [c_int] * 7,
-    'iunet_f32_wgrad': [c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_f32_head_loss_num_parts': [c_int, c_ll],
-    'iunet_f32_head_loss_fwd': [c_void_p, c_ll, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                                c_void_p, c_int, c_ll, c_void_p],
-    'iunet_f32_head_loss_bwd': [c_void_p, c_ll, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_ll,
-                                c_void_p, c_ll, c_int, c_ll, c_void_p],
-    'iunet_f32_channel_sum': [c_void_p, c_ll, c_void_p, c_int, c_int, c_ll, c_void_p],
-    # ---- fp16x2 split precision (the tolerance-meeting mode on the 16-bit matrix cores)
-    'iunet_x2_prep': [c_void_p] * 9 + [c_float, c_float, c_float, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_x2_first_conv_fwd': [c_int, c_void_p, c_int, ctypes.POINTER(c_ll), c_void_p, c_ll, c_int, c_void_p, c_void_p, c_void_p,
-                                c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_x2_conv3_fwd': [c_int, c_void_p, c_ll, c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_void_p,
-                           c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_x2_maxpool_fwd': [c_int, c_void_p, c_ll, c_int, c_void_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_x2_convT_fwd': [c_int, c_void_p, c_ll, c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_void_p,
-                           c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_x2_head_fwd': [c_void_p, c_ll, c_int, c_int, c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p,
-                          ctypes.POINTER(c_ll), c_float, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    # ---- fp16x2 with the cross terms on the fp8 matrix cores (csrc/conv3_x2m.hip)
-    'iunet_x2m_prep': [c_void_p] * 9 + [c_float, c_float, c_float, c_int, c_int, c_void_p],
-    'iunet_x2m_prep_nd': [c_int] + [c_void_p] * 9 + [c_float, c_float, c_float, c_int, c_int, c_void_p],
-    'iunet_x2_prep_batch': [c_void_p, c_int, c_int, c_void_p],
-    'iunet_x2m_prep_batch': [c_void_p, c_int, c_int, c_void_p],
-    'iunet_x2m_conv_fwd': [c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_int, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p,
-                           c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    'iunet_x2m_conv_pool_fwd': [c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll,
-                                c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    'iunet_x2m_first_stage_fwd': [c_void_p, c_int, ctypes.POINTER(c_ll), c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_ll, c_int, c_void_p, c_ll,
-                                  c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
-    'iunet_x2m_conv_head_fwd': [c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
-                                c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_ll), c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    'iunet_x2m_make8': [c_void_p, c_ll, c_int, c_void_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_x2m_first_conv_fwd': [c_int, c_void_p, c_int, ctypes.POINTER(c_ll), c_void_p, c_ll, c_int, c_void_p, c_ll, c_void_p, c_void_p, c_void_p,
-                                 c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    'iunet_x2m_convT_fwd': [c_int, c_void_p, c_ll, c_int, c_void_p, c_ll, c_int, c_void_p, c_ll, c_void_p, c_void_p, c_void_p,
-                            c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    'iunet_x2_conv3_fwd_flag': [c_int, c_void_p, c_ll, c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_void_p,
-                                c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    'iunet_x2m_maxpool_fwd': [c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_x2m_conv3_fwd': [c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_int, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p,
-                            c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    # ---- handle level (csrc/net.hip): the whole forward sequenced in C++
-    'iunet_f32_gn_relu_fwd': [c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_ll, c_void_p],
-    'iunet_x2_gn_relu_fwd': [c_void_p, c_ll, c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
-                             c_int, c_int, c_ll, c_void_p, c_void_p],
-    'iunet_x2m_gn_relu_fwd': [c_void_p, c_ll, c_int, c_void_p, c_ll, c_int, c_void_p, c_ll, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
-                              c_int, c_int, c_ll, c_void_p, c_void_p],
-    'iunet_logit_diff': [c_void_p, c_void_p, c_ll, c_void_p, c_void_p],
-    'iunet_net_create': [c_int, c_int, c_int, c_int, c_int, c_int, c_float, ctypes.POINTER(c_void_p)],
-    'iunet_net_create_ex': [c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, ctypes.POINTER(c_void_p)],
-    'iunet_net_create_nested': [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)],
-    'iunet_net_num_tensors': [c_void_p],
-    'iunet_net_param': [c_void_p, c_int, ctypes.c_char_p, c_int, ctypes.POINTER(c_ll), ctypes.POINTER(c_ll)],
-    'iunet_net_load': [c_void_p, c_void_p, c_void_p, c_void_p],
-    'iunet_net_forward': [c_void_p, c_void_p, c_int, ctypes.POINTER(c_ll), c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                          c_void_p, ctypes.POINTER(c_ll), c_float, c_int, c_void_p],
-    'iunet_net_eval_step': [c_void_p, c_void_p, c_int, ctypes.POINTER(c_ll), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                            c_void_p, c_void_p, c_void_p],
-    'iunet_net_forward_argmax': [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    # ---- training state on the device + the training step as one C call (csrc/train_net.hip)
-    'iunet_train_state_init': [c_void_p, c_float, c_int, c_void_p],
-    'iunet_head_loss_bwd_dev': [c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_int, c_ll, c_void_p],
-    'iunet_head_grad_scatter': [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
-    'iunet_adamw_step_dev': [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int, c_float, c_void_p],
-    'iunet_train_create': [c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)],
-    'iunet_train_create_ex': [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)],
-    'iunet_train_create_nested': [c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)],
-    'iunet_train_num_tensors': [c_void_p],
-    'iunet_train_param': [c_void_p, c_int, ctypes.c_char_p, c_int, ctypes.POINTER(c_ll), ctypes.POINTER(c_ll)],
-    'iunet_train_num_bn': [c_void_p],
-    'iunet_train_bind': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_void_p, c_void_p, c_void_p],
-    'iunet_train_repack': [c_void_p, c_void_p],
-    'iunet_train_forward_backward': [c_void_p, c_void_p, c_int, ctypes.POINTER(c_ll), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                     c_void_p, c_void_p, c_void_p],
-    'iunet_train_forward_backward_hooks': [c_void_p, c_void_p, c_int, ctypes.POINTER(c_ll), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    'iunet_train_update': [c_void_p, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p],
-    'iunet_train_step': [c_void_p, c_void_p, c_int, ctypes.POINTER(c_ll), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                         c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p],
-    # ---- fp8 matrix cores (config C5)
-    'iunet_f8_pack_conv3': [c_void_p] * 5 + [c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    'iunet_conv3_f8_fwd': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p,
-                           c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    'iunet_conv3_f8_fwd_q': [c_int, c_int, c_void_p, c_ll, c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_void_p,
-                             c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    'iunet_first_conv_fwd_q': [c_int, c_int, c_void_p, c_int, ctypes.POINTER(c_ll), c_void_p, c_ll, c_void_p, c_void_p,
-                               c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_maxpool_q_fwd': [c_int, c_void_p, c_ll, c_void_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_convT_fwd_q': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p,
-                          c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_gather_block': [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    'iunet_blend_accumulate': [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                               ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p],
-    'iunet_normalize_quantize': [c_void_p, c_void_p, c_void_p, c_ll, c_int, c_float, c_void_p],
-    'iunet_div_f32': [c_void_p, c_ll, c_float, c_void_p],
-    'iunet_colorize': [c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p],
-    'iunet_slice_gather': [c_void_p, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int),
-                           ctypes.POINTER(c_int), c_int, c_int, c_int, c_void_p, c_void_p],
-    'iunet_slice_scatter': [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), c_int, c_int, c_void_p, c_void_p,
-                            c_void_p],
-    'iunet_augment_batch': [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    'iunet_zoom_nearest_table': [c_int, ctypes.c_double, ctypes.POINTER(c_int), c_int],
-    'iunet_zoom_nearest_u8': [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_ll), c_void_p, ctypes.POINTER(c_ll),
-                              ctypes.POINTER(c_int), c_void_p, c_void_p],
-    # ---- training
-    'iunet_bn_finalize': [c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
-                          c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    'iunet_bn_relu_fwd': [c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_int, c_int, c_ll, c_void_p],
-    'iunet_bn_relu_pool_fwd': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p,
-                               c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_bn_bwd_num_parts': [c_int, c_ll],
-    'iunet_conv3_dgrad_bnstats': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p,
-                                  c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_conv3_dgrad_bnstats_lay': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_head_bn_bwd_ok': [c_int, c_int],
-    'iunet_head_bn_bwd': [c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p,
-                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_ll, c_void_p],
-    'iunet_bn_relu_bwd_apply': [c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_ll, c_void_p],
-    'iunet_gn_num_parts': [c_int, c_ll],
-    'iunet_gn_finalize': [c_void_p, c_int, c_int, c_int, c_ll, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    'iunet_gn_relu_fwd': [c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p,
-                          c_void_p, c_void_p, c_int, c_int, c_ll, c_void_p],
-    'iunet_gn_relu_fwd_rows': [c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p,
-                               c_void_p, c_void_p, c_int, c_int, c_ll, c_void_p],
-    'iunet_gn_relu_pool_fwd_rows': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_int, c_float, c_void_p,
-                                    c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_conv3_sample_stats_rows': [c_int] * 9,
-    'iunet_conv3_fwd_sample_stats': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                     c_int, c_int, c_int, c_void_p],
-    'iunet_conv3_dgrad_sample_bnstats': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_gn_relu_bwd_rows': [c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                               c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_ll, c_void_p],
-    'iunet_gn_relu_bwd': [c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_ll, c_void_p],
-    'iunet_gn_relu_pool_fwd': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_int, c_float, c_void_p,
-                               c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_gn_relu_pool_bwd': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p,
-                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_bn_relu_bwd': [c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p,
-                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_ll, c_void_p],
-    'iunet_bn_relu_pool_bwd': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p,
-                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                               c_int, c_int, c_void_p],
-    'iunet_bn_relu_sum_bwd': [c_int, c_int, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_ll), c_void_p, c_ll, c_void_p, c_ll,
-                              c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                              c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_maxpool_bwd': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_int, c_int, c_int, c_int,
-                          c_int, c_int, c_void_p],
-    'iunet_head_loss_num_parts': [c_int, c_ll],
-    'iunet_head_loss_bwd_num_parts': [c_int, c_ll, c_int, c_int],
-    'iunet_head_loss_fwd': [c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
-                            c_void_p, c_void_p, c_void_p, c_int, c_ll, c_void_p],
-    'iunet_head_loss_bwd': [c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
-                            c_void_p, c_float, c_void_p, c_ll, c_void_p, c_int, c_ll, c_void_p],
-    'iunet_head_loss_fwd_act': [c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
-                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_ll, c_void_p],
-    'iunet_head_loss_fwd_act_ps': [c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
-                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_ll, c_void_p],
-    'iunet_head_gn_bwd': [c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p,
-                          c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_ll, c_void_p],
-    'iunet_head_loss_bwd_act': [c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
-                                c_void_p, c_float, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_int, c_ll, c_void_p],
-    'iunet_reduce_slab': [c_void_p, c_int, c_ll, c_void_p, c_float, c_int, c_void_p],
-    'iunet_check_finite': [c_void_p, c_ll, c_void_p, c_void_p],
-    'iunet_adamw_step': [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_float, c_float, c_float, c_float, c_float,
-                         c_int, c_float, c_void_p, c_void_p],
-    'iunet_conv3_wgrad_blocks': [c_int] * 7,
-    'iunet_conv3_wgrad': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_float,
-                          c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_conv3_wgrad_act': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
-                              c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_pack_convT_dgrad': [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    'iunet_convT_dgrad': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                          c_int, c_void_p],
-    'iunet_convT_wgrad_blocks': [c_int] * 7,
-    'iunet_convT_wgrad': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p,
-                          c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_first_conv_wgrad_blocks': [c_int] * 5,
-    'iunet_first_conv_wgrad_bn': [c_int, c_int, c_void_p, c_int, ctypes.POINTER(c_ll), c_void_p, c_ll, c_void_p, c_ll, c_void_p,
-                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                  c_int, c_void_p],
-    'iunet_first_conv_wgrad': [c_int, c_int, c_void_p, c_int, ctypes.POINTER(c_ll), c_void_p, c_ll, c_void_p, c_void_p,
-                               c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    # ---- LinkNet decoder blocks (csrc/linknet.hip)
-    'iunet_lk_pack': [c_int, c_int, c_int] + [c_void_p] * 5 + [c_float, c_void_p, c_void_p, c_int, c_int, c_void_p],
-    'iunet_lk_stats_parts': [c_int] * 7,
-    'iunet_lk_conv_fwd': [c_int, c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll,
-                          c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_lk_wgrad': [c_int, c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
-                       c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_lk_bn_relu_add': [c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_int, c_int, c_ll, c_void_p],
-    'iunet_lk_f32_conv_fwd': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_ll,
-                              c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    # ---- DeepLabV3 decoder (csrc/deeplab.hip)
-    'iunet_dl_pack': [c_int, c_int, c_int, c_int] + [c_void_p] * 5 + [c_float, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p],
-    'iunet_dl_stats_parts': [c_int] * 5,
-    'iunet_dl_conv_fwd': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_int, c_int, _IP, _IP, _IP, c_void_p, c_void_p, c_void_p,
-                          c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_dl_wgrad': [c_int, c_int, c_int, c_void_p, c_ll, c_int, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                       c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_dl_f32_conv_fwd': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p,
-                              c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    'iunet_dl_chansum': [c_int, c_void_p, c_ll, c_void_p, c_float, c_int, c_int, c_ll, c_void_p],
-    'iunet_dl_pool_gemv': [c_void_p] * 4 + [c_int] * 3 + [c_void_p],
-    'iunet_dl_pool_psb': [c_void_p] * 7 + [c_float] + [c_void_p] * 5 + [c_int, c_int, c_void_p],
-    'iunet_dl_pool_bwd': [c_void_p] * 15 + [c_int] * 3 + [c_void_p],
-    'iunet_dl_dropout': [c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_ll, c_void_p],
-    'iunet_dl_up_head': [c_int, c_void_p] + [c_int] * 5 + [c_void_p] * 3 + [ctypes.POINTER(c_ll), c_float, c_int, c_int, c_void_p],
-    'iunet_dl_up_loss_fwd': [c_int, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    'iunet_dl_up_loss_bwd': [c_int, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_void_p],
-    'iunet_dl_head_bwd': [c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_int, c_void_p, c_ll] + [c_void_p] * 3 + [c_int, c_ll, c_void_p],
-    # ---- Segformer decoder (csrc/segformer.hip)
-    'iunet_sf_pack': [c_int, c_int, c_int, _IP, c_void_p, _VP, _VP] + [c_void_p] * 4 + [c_float] + [c_void_p] * 4,
-    'iunet_sf_gemm': [c_int, c_int, c_int, _VP, _LP, _IP, _IP, _VP, _VP, c_void_p, c_void_p, c_void_p, c_ll, c_void_p] + [c_int] * 6 + [c_void_p],
-    'iunet_sf_wgrad': [c_int, c_int, c_int, _VP, _LP, _IP, _IP, _VP, _VP, c_void_p, c_ll, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p],
-    'iunet_sf_adjoint': [c_int, c_int, c_void_p, c_ll, c_int, c_int, c_int, c_void_p, c_ll] + [c_int] * 5 + [c_void_p],
-    'iunet_sf_param_grads': [c_int, c_int, _IP, c_void_p, _VP, _VP, c_void_p, c_void_p, c_int, _VP, _VP, c_void_p, c_void_p],
-}
-# functions that return a size / count instead of a status
-_INT_RETURN = ['iunet_pack_desc_bytes', 'iunet_augment_desc_bytes', 'iunet_x2_prep_desc_bytes']
-_INT_RETURN_ARGS = {'iunet_sf_stats_parts': [c_int] * 4, 'iunet_dl_num_taps': [c_int] * 5, 'iunet_dl_up_loss_num_parts': [c_int, c_ll], 'iunet_dl_head_bwd_parts': [c_int, c_ll], 'iunet_zoom_nearest_len': [c_int, ctypes.c_double], 'iunet_x2_convT_kc': [c_int], 'iunet_x2m_head_fusable': [c_int, c_int], 'iunet_x2m_pool_fusable': [c_int, c_int], 'iunet_x2m_first_stage_fusable': [c_int] * 6, 'iunet_x2_pack_mode': [c_int], 'iunet_f8_pack_order': [c_int, c_int]}
-_LL_RETURN = {'iunet_gn_precise_slab_bytes': [c_int, c_int, c_ll], 'iunet_net_eval_scratch_bytes': [c_void_p, c_int, c_int, c_int, c_int], 'iunet_x2m_w8_bytes': [c_int] * 2, 'iunet_x2m_w8_bytes_nd': [c_int] * 3, 'iunet_train_num_params': [c_void_p], 'iunet_train_packed_bytes': [c_void_p], 'iunet_train_workspace_bytes': [c_void_p, c_int, c_int, c_int, c_int], 'iunet_conv3_wgrad_slab_floats': [c_int] * 7, 'iunet_f32_pack_conv_elems': [c_int] * 3, 'iunet_f8_pack_conv3_bytes': [c_int] * 3, 'iunet_conv3_f8_workspace_elems': [c_int] * 7, 'iunet_pack_conv3_elems': [c_int] * 4,
-              'iunet_pack_first_conv_elems': [c_int] * 3, 'iunet_slice_scatter_workspace_bytes': [c_int],
-              'iunet_lk_pack_elems': [c_int] * 4, 'iunet_lk_wgrad_slab_floats': [c_int] * 8, 'iunet_dl_wgrad_slab_floats': [c_int] * 8,
-              'iunet_sf_wgrad_slab_floats': [c_int] * 6,
-              'iunet_net_num_params': [c_void_p], 'iunet_net_packed_bytes': [c_void_p], 'iunet_net_workspace_bytes': [c_void_p] + [c_int] * 4}
 
 
 class NativeError(RuntimeError):
     pass
+
+
+# ---- the bindings come from include/iunet.h, the one place a public signature is written.  C type (const dropped) -> ctypes:
+_SCALAR = {'int': c_int, 'long long': c_ll, 'float': c_float, 'double': ctypes.c_double}
+_POINTEE = ('int', 'long long', 'double')               # host arrays: POINTER(scalar)
+_OPAQUE = ('void', 'iunet_net', 'iunet_train')          # T* crosses as a raw address, T** / T* const* as an array of them
+# the header says `const int* tables`, but it is a DEVICE pointer: Python passes an address, not a host int array
+_OVERRIDE = {('iunet_zoom_nearest_u8', 'tables'): c_void_p}
+_PROTO = re.compile(r'([\w\s*]*?)\b(iunet_\w+)\s*\(([^()]*)\)\s*;')
+
+
+def _ctype(spelled, ret=False):
+    base, stars = ' '.join(re.sub(r'\bconst\b|\*', ' ', spelled).split()), spelled.count('*')
+    if stars == 0:
+        if ret and base == 'void':
+            return None
+        return c_void_p if base == 'iunet_train_hook' and not ret else _SCALAR[base]
+    if base in _OPAQUE and stars <= 2:
+        return c_void_p if stars == 1 else ctypes.POINTER(c_void_p)
+    if stars == 1 and base == 'char':
+        return ctypes.c_char_p
+    if stars == 1 and base in _POINTEE and not ret:
+        return ctypes.POINTER(_SCALAR[base])
+    raise KeyError(spelled)
+
+
+def parse_header(text):
+    """{name: (restype, argtypes)} of every prototype of the header text (every parameter named, as include/iunet.h writes them).  A
+    type the mapping above does not know raises NativeError with the function and the parameter: nothing is guessed."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    text = re.sub(r'^[ \t]*#.*$', '', text, flags=re.M)
+    sigs = {}
+    for ret, name, params in _PROTO.findall(text):
+        try:
+            where = 'return type'
+            restype, argtypes = _ctype(ret, ret=True), []
+            for where in [' '.join(p.split()) for p in params.split(',') if p.split() not in ([], ['void'])]:
+                spelled, pname = re.fullmatch(r'(.*?)(\w+)', where).groups()
+                argtypes.append(_OVERRIDE.get((name, pname)) or _ctype(spelled))
+        except (KeyError, AttributeError):
+            raise NativeError(f'iunet.h: {name}: no ctypes mapping for `{where}`') from None
+        sigs[name] = (restype, argtypes)
+    return sigs
+
+
+def signatures():
+    """The parsed header, read once: $IUNET_HEADER, else the checkout's include/iunet.h, else the copy beside the library (overlay install)."""
+    global _sigs
+    if _sigs is None:
+        found = [p for p in (os.path.join(_HERE, '..', '..', 'include', 'iunet.h'), os.path.join(_HERE, '..', 'lib', 'iunet.h')) if os.path.isfile(p)]
+        path = os.environ.get('IUNET_HEADER') or (found[0] if found else None)
+        if path is None or not os.path.isfile(path):
+            raise NativeError(f'iunet.h is missing ({path or "include/iunet.h of the checkout, lib/iunet.h beside the library"}); IUNET_HEADER names another')
+        _sigs = parse_header(open(path).read())
+    return _sigs
 
 
 def lib():
@@ -302,30 +86,15 @@ def lib():
             raise NativeError(f'{LIB_PATH} is missing: build it with __graft_entry__.build() '
                               f'(interactive-unet_amd/csrc/build.sh); there is no CPU fallback')
         l = ctypes.CDLL(LIB_PATH)
-        l.iunet_last_error.restype = ctypes.c_char_p
-        l.iunet_last_error.argtypes = []
-        for name, args in _SIGS.items():
+        for name, (restype, argtypes) in signatures().items():
             fn = getattr(l, name)          # AttributeError here = header/library mismatch
-            fn.argtypes = args
-            fn.restype = c_int
-        for name in _INT_RETURN:
-            getattr(l, name).restype = c_int
-            getattr(l, name).argtypes = []
-        for name, args in _INT_RETURN_ARGS.items():
-            getattr(l, name).restype = c_int
-            getattr(l, name).argtypes = args
-        for name, args in _LL_RETURN.items():
-            fn = getattr(l, name)
-            fn.argtypes = args
-            fn.restype = c_ll
-        l.iunet_net_destroy.argtypes, l.iunet_net_destroy.restype = [c_void_p], None
-        l.iunet_train_destroy.argtypes, l.iunet_train_destroy.restype = [c_void_p], None
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = l
     return _lib
 
 
 def exported_symbols():
-    return ['iunet_last_error', 'iunet_net_destroy', 'iunet_train_destroy'] + list(_SIGS) + list(_LL_RETURN) + list(_INT_RETURN) + list(_INT_RETURN_ARGS)
+    return list(signatures())
 
 
 def check(status):

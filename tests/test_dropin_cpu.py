@@ -89,6 +89,8 @@ def test_overlay_install_resolves_every_caller_attribute(tmp_path):
     assert set(install_overlay.REPLACED) <= set(done)
     assert (pkg / 'utils.py').read_text() == textwrap.dedent(STUB_UTILS)    # the caller's utils.py is untouched
     assert (pkg / 'predict.py.reference').exists()
+    # the header _native.py derives its bindings from lies beside the library, where the installed _native.py finds it
+    assert (tmp_path / 'checkout' / 'lib' / 'iunet.h').read_text() == open(os.path.join(ROOT, 'include', 'iunet.h')).read()
     # every module a native module imports from its own package -- at import time or lazily inside a function -- was installed with it
     import re
     for f in pkg.glob('*.py'):

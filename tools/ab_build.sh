@@ -11,5 +11,5 @@ mkdir -p /tmp/iunet_ab
 hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result -Wno-int-to-pointer-cast "$@" -c $C/$src -o /tmp/iunet_ab/${src%.hip}.o
 objs=""
 for o in $C/obj/*.o; do b=$(basename $o); if [ "$b" = "${src%.hip}.o" ]; then objs="$objs /tmp/iunet_ab/$b"; else objs="$objs $o"; fi; done
-hipcc --offload-arch=gfx950 -shared -fPIC -o $R/interactive-unet_amd/lib/libiunet_ab.so $objs
+hipcc --offload-arch=gfx950 -shared -fPIC -Wl,--no-undefined -o $R/interactive-unet_amd/lib/libiunet_ab.so $objs
 echo built $R/interactive-unet_amd/lib/libiunet_ab.so

@@ -6,7 +6,7 @@ The reference's app.py does `from . import utils, trainer, predict, suggestor` (
 inside ITS package directory, so a directory on PYTHONPATH is never consulted.  The drop-in is therefore file-level:
 the hot-path modules of the reference (unet, trainer, predict, metrics, slicer, loader, suggestor) are replaced by the
 native ones of the same names, the native-only modules (engine, engine_f32, engine_x2, engine_auto, net_graph, train_engine, train_engine_f32, engine_nested, train_engine_nested, engine_linknet, train_engine_linknet, engine_deeplab, train_engine_deeplab, engine_segformer, train_engine_segformer, shard, dp, multiscale, zarr3,
-_native) are added beside them, and libiunet.so goes to <package>/../lib/ where _native.py looks for it.  The reference's
+_native) are added beside them, and libiunet.so and include/iunet.h go to <package>/../lib/ where _native.py looks for them.  The reference's
 app.py, annotator.py, volumedata.py and -- deliberately -- utils.py are NOT touched: app.py:33-788 calls ~15 project /
 TIFF / plotting helpers of utils.py that are outside the hot path.  The replaced files are kept as <name>.py.reference.
 """
@@ -38,14 +38,15 @@ def install(target, symlink=False, keep_backup=True):
                 os.remove(d)
         (os.symlink if symlink else shutil.copyfile)(s, d)
         done.append(name)
-    lib_src = os.path.join(PKG, 'lib', 'libiunet.so')
     lib_dir = os.path.join(os.path.dirname(os.path.abspath(target)), 'lib')
-    if os.path.isfile(lib_src):
-        os.makedirs(lib_dir, exist_ok=True)
-        d = os.path.join(lib_dir, 'libiunet.so')
-        if os.path.lexists(d):
-            os.remove(d)
-        (os.symlink if symlink else shutil.copyfile)(lib_src, d)
+    # the library and, beside it, the header _native.py derives its bindings from
+    for s in (os.path.join(PKG, 'lib', 'libiunet.so'), os.path.join(os.path.dirname(PKG), 'include', 'iunet.h')):
+        if os.path.isfile(s):
+            os.makedirs(lib_dir, exist_ok=True)
+            d = os.path.join(lib_dir, os.path.basename(s))
+            if os.path.lexists(d):
+                os.remove(d)
+            (os.symlink if symlink else shutil.copyfile)(s, d)
     return done
 
 
