@@ -127,13 +127,15 @@ int iunet_f32_pack_conv(const void* w, void* dst, void* bias_out, const void* ga
                         const void* var, float eps, int Cout, int Cin, int taps, int transposed, void* stream);
 /* 3^d conv pad 1 (transposed == 0), ConvTranspose k2 s2 (transposed == 1; D, H, W = input grid, output 2x) or 1x1 conv
  * (transposed == 2; operator packed with taps == 1) + bias + optional ReLU.  The input is read through element strides in_strides (n, c, d, h, w) and in_dtype (0 f32, 1 f16, 2 u8 / 255, 3
- * bf16), so the first conv takes the caller's tensor or a 2.5-D view of a block directly; y: planar fp32. */
+ * bf16), so the first conv takes the caller's tensor or a 2.5-D view of a block directly; y: planar fp32.  Any other value of
+ * `transposed` is refused. */
 int iunet_f32_conv_fwd(int nd, const void* x, int in_dtype, const long long* in_strides, void* y, long long y_ss,
                        const void* wpk, const void* bias, int N, int D, int H, int W, int Cin, int Cout, int relu,
                        int transposed, void* stream);
 int iunet_f32_maxpool_fwd(int nd, const void* x, long long x_ss, void* y, long long y_ss, int C, int N, int Do, int Ho, int Wo,
                           void* stream);
-/* iunet_head_fwd on planar fp32 features: w fp32 [ncls][C0]; same output contract. */
+/* iunet_head_fwd on planar fp32 features: w fp32 [ncls][C0]; same output contract.  C0, N, D, H, W > 0; at least one of logits /
+ * probs / cls is non-NULL; divisor != 0. */
 int iunet_f32_head_fwd(const void* x, long long x_ss, int C0, const void* w, const void* bias, int ncls, void* logits,
                        void* probs, void* cls, const long long* out_strides, float divisor, int accumulate, int N, int D, int H,
                        int W, void* stream);
@@ -634,7 +636,8 @@ int iunet_first_conv_wgrad_bn(int dtype, int nd, const void* x, int in_dtype, co
                               const void* coef, const void* scale, const void* shift, void* slab, void* dW, int N, int D, int H,
                               int W, int Cin, int Cout, void* stream);
 /* AdamW with torch defaults (unet.py:71-73); grads are multiplied by grad_scale_inv (loss scaling, 1/world);
- * if *skip_flag != 0 (set by iunet_check_finite) the step is skipped. */
+ * if *skip_flag != 0 (set by iunet_check_finite) the step is skipped.  iunet_check_finite: *flag |= 1 if any of the n fp32 values
+ * of g is not finite; g and flag non-NULL, n >= 0 (n == 0: nothing is launched, the flag stays as it is). */
 int iunet_check_finite(const void* g, long long n, void* flag, void* stream);
 int iunet_adamw_step(void* p, const void* g, void* m, void* v, long long n, float lr, float b1, float b2, float eps,
                      float wd, int step, float grad_scale_inv, const void* skip_flag, void* stream);

@@ -258,6 +258,7 @@ int iunet_f32_conv_fwd(int nd, const void* x, int in_dtype, const long long* in_
   IUNET_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && (nd == 3 || D == 1), "f32_conv: bad shape %d %d %d %d", N, D, H, W);
   IUNET_REQUIRE(in_dtype >= 0 && in_dtype <= 3, "f32_conv: bad input dtype %d", in_dtype);
   IUNET_REQUIRE(Cout > 0 && Cout % 32 == 0 && Cin > 0, "f32_conv: Cout must be a positive multiple of 32, Cin > 0 (got %d, %d)", Cout, Cin);
+  IUNET_REQUIRE(transposed >= 0 && transposed <= 2, "f32_conv: transposed must be 0 (conv), 1 (ConvTranspose k2 s2) or 2 (1x1), got %d", transposed);
   return iunet_f32_conv_launch(nd, x, in_dtype, in_strides, (float*)y, y_ss, (const float*)wpk, (const float*)bias, N, D, H, W,
                                Cin, Cout, relu, transposed, (hipStream_t)stream);
 }
@@ -275,6 +276,9 @@ int iunet_f32_head_fwd(const void* x, long long x_ss, int C0, const void* w, con
                        int W, void* stream) {
   IUNET_REQUIRE(x && w && bias && out_strides, "f32_head: null pointer");
   IUNET_REQUIRE(ncls >= 2 && ncls <= 10, "f32_head: num_classes must be 2..10 (got %d)", ncls);
+  IUNET_REQUIRE(C0 > 0 && N > 0 && D > 0 && H > 0 && W > 0, "f32_head: bad shape %d %d %d %d %d", C0, N, D, H, W);
+  IUNET_REQUIRE(logits || probs || cls, "f32_head: no output (logits, probs and cls are all null)");
+  IUNET_REQUIRE(divisor != 0.f, "f32_head: divisor must not be zero");
   return iunet_f32_head_launch((const float*)x, x_ss, C0, (const float*)w, (const float*)bias, ncls, (float*)logits,
                                (float*)probs, (unsigned char*)cls, out_strides, divisor, accumulate, N, D, H, W,
                                (hipStream_t)stream);

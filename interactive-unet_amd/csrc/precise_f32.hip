@@ -185,11 +185,15 @@ __global__ __launch_bounds__(256) void f32_conv_kernel(F32ConvParams p) {
 // fp32 master weights -> the operator order above.  conv: w [Cout][Cin][taps]; transposed: w [Cin][Cout][npos].
 // dst [npos or 1][Cout/32][chunks][taps or 1][4 k pairs][2 cout tiles][2 k parity][16]; channels >= Cin are zeros.
 // A non-null gamma folds an eval-mode BatchNorm exactly as the oracle does (separately rounded fp32 operations):
-// a = gamma / sqrt(var + eps), w' = w * a, bias_out = beta - mean * a.
+// a = gamma / sqrt(var + eps), w' = w * a, bias_out = beta - mean * a.  Written with plain operators under `fp contract(off)` and
+// sqrtf, which this build rounds correctly: __fsqrt_rn is, despite its name, the hardware's approximate v_sqrt_f32 here (one unit off
+// for ~8 % of arguments), and __fsub_rn(beta, __fmul_rn(mean, a)) is inlined from a header compiled with contraction on, so it became
+// one fma (the pragma is lexical).
 __global__ void f32_pack_conv_kernel(const float* __restrict__ w, float* __restrict__ dst, float* __restrict__ bias_out,
                                      const float* __restrict__ gamma, const float* __restrict__ beta,
                                      const float* __restrict__ mean, const float* __restrict__ var, float eps, int Cout,
                                      int Cin, int taps, int transposed) {
+#pragma clang fp contract(off)
   const int nchunks = (Cin + 7) / 8, ncob = Cout / 32;
   const int T = transposed ? 1 : taps, NPOS = transposed ? taps : 1;
   const long long total = (long long)NPOS * ncob * nchunks * T * 256;
@@ -207,14 +211,14 @@ __global__ void f32_pack_conv_kernel(const float* __restrict__ w, float* __restr
     float v = 0.f;
     if (ci < Cin) {
       v = transposed ? w[((long long)ci * Cout + co) * taps + pos] : w[((long long)co * Cin + ci) * taps + tap];
-      if (gamma) v = __fmul_rn(v, __fdiv_rn(gamma[co], __fsqrt_rn(__fadd_rn(var[co], eps))));
+      if (gamma) v = v * (gamma[co] / sqrtf(var[co] + eps));
     }
     dst[i] = v;
   }
   if (gamma && bias_out)
     for (int co = blockIdx.x * blockDim.x + threadIdx.x; co < Cout; co += gridDim.x * blockDim.x) {
-      const float a = __fdiv_rn(gamma[co], __fsqrt_rn(__fadd_rn(var[co], eps)));
-      bias_out[co] = __fsub_rn(beta[co], __fmul_rn(mean[co], a));
+      const float a = gamma[co] / sqrtf(var[co] + eps);
+      bias_out[co] = beta[co] - mean[co] * a;
     }
 }
 

@@ -1738,6 +1738,8 @@ int iunet_reduce_slab(void* slab, int nparts, long long n, void* out, float alph
 }
 
 int iunet_check_finite(const void* g, long long n, void* flag, void* stream) {
+  IUNET_REQUIRE(g && flag && n >= 0, "check_finite: null pointer or negative length");
+  if (n == 0) return IUNET_OK;
   hipLaunchKernelGGL(check_finite_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, (const float*)g, n, (int*)flag);
   IUNET_CHECK_HIP(hipGetLastError());
   return IUNET_OK;

@@ -155,3 +155,33 @@ class StridedInput:
         bad = now != self.before
         if bool(bad.any()):
             raise AssertionError(f'{self.name}: strided input modified, first at allocation offset {int(bad.nonzero()[0])}')
+
+
+class StridedOutput:
+    """The mirror image of StridedInput for an output [N, C, D, H, W] that a kernel writes through element strides: channels last
+    (sC = 1), every pitch larger than its extent.  The body and its surroundings start as the sentinel; `logical()` is what was written
+    (planar, on the CPU), `check()` that nothing outside it was."""
+
+    def __init__(self, shape, dtype=torch.float32, pad=(1, 2, 3, 5), device='cuda', name='out'):
+        N, C, D, H, W = shape
+        pc, pd, ph, pw = pad
+        self.shape, self.name, self.is_input = tuple(shape), name, False
+        self.full = (N, D + pd, H + ph, W + pw, C + pc)
+        big = sentinel_filled(N * (D + pd) * (H + ph) * (W + pw) * (C + pc) + 2 * 64, dtype)
+        body = big[64:-64].view(self.full)
+        sn, sd, sh, sw, sc = body.stride()
+        self.strides = (sn, sc, sd, sh, sw)
+        self.inside = torch.zeros(big.numel(), dtype=torch.bool)
+        self.inside[64:-64].view(self.full)[:, :D, :H, :W, :C] = True
+        self.before = bits(big).clone()
+        self.buf = big.to(device)
+        self.t = self.buf[64:]
+
+    def logical(self):
+        N, C, D, H, W = self.shape
+        return self.buf.cpu()[64:-64].view(self.full)[:, :D, :H, :W, :C].permute(0, 4, 1, 2, 3).contiguous()
+
+    def check(self):
+        bad = (bits(self.buf.cpu()) != self.before) & ~self.inside
+        if bool(bad.any()):
+            raise AssertionError(f'{self.name}: {int(bad.sum())} sentinel elements of a strided output overwritten, first at allocation offset {int(bad.nonzero()[0])}')
