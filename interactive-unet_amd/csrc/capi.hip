@@ -229,8 +229,7 @@ int iunet_head_fwd(int dtype, const void* x, long long x_ss, int C0, const void*
   IUNET_REQUIRE(x && w && bias && out_strides, "head: null pointer");
   IUNET_REQUIRE(C0 % 8 == 0, "head: C0 must be a multiple of 8");
   return iunet_head_launch(dtype, x, x_ss, C0, (const float*)w, (const float*)bias, ncls, (float*)logits, (float*)probs,
-                           (unsigned char*)cls, out_strides[0], out_strides[1], out_strides[2], out_strides[3],
-                           out_strides[4], divisor, accumulate, N, D, H, W, (hipStream_t)stream);
+                           (unsigned char*)cls, out_strides, divisor, accumulate, N, D, H, W, (hipStream_t)stream);
 }
 
 /* ---- fp32 parity mode (precise_f32.hip): planar fp32 activations, v_mfma_f32_16x16x4_f32 ------------------- */

@@ -106,9 +106,66 @@ inline auto iunet_dispatch(int dtype, int nd, bool flag, F&& f) {
   return with_t(bf16());
 }
 
-// Eval-mode BatchNorm folded into an operator: row c is scaled by bn_fold_scale, the bias is bn_fold_bias of that scale
-__device__ __forceinline__ float bn_fold_scale(const float* gamma, const float* var, float eps, int c) { return gamma[c] / sqrtf(var[c] + eps); }
-__device__ __forceinline__ float bn_fold_bias(const float* beta, const float* mean, float scale, int c) { return beta[c] - mean[c] * scale; }
+// ---- Eval-mode BatchNorm folded into an operator, THE definition (every pack / prep kernel of csrc/ calls these): the IEEE fp32
+// formula of the host / oracle (oracle/unet_ref.py: fold_bn), every operation rounded on its own --
+//   a = gamma[c] / sqrt(var[c] + eps);  w' = w * a;  bias = beta[c] - (mean[c] * a).
+// Plain operators and sqrtf (hipcc's default sqrt and divide are correctly rounded; __fsqrt_rn is, despite its name, the approximate
+// v_sqrt_f32 here, one unit off for ~8 % of arguments), each body under its own `fp contract(off)`: the pragma is lexical, so it holds
+// whatever the including file sets, and mean * a cannot fuse into the subtraction -- as it did when this header had the bias as one
+// expression, and as __fsub_rn(beta, __fmul_rn(mean, a)) does (those wrappers are inlined from a header compiled with contraction on).
+__device__ __forceinline__ float bn_fold_scale(const float* gamma, const float* var, float eps, int c) {
+#pragma clang fp contract(off)
+  const float s = var[c] + eps;
+  return gamma[c] / sqrtf(s);
+}
+__device__ __forceinline__ float bn_fold_mul(float w, float a) {
+#pragma clang fp contract(off)
+  return w * a;
+}
+__device__ __forceinline__ float bn_fold_bias(const float* beta, const float* mean, float a, int c) {
+#pragma clang fp contract(off)
+  const float t = mean[c] * a;
+  return beta[c] - t;
+}
+
+// ---- OCP e4m3 (4 exponent bits, bias 7, 3 mantissa bits, subnormal step 2^-9) in software: the operator quantisation of the fp8
+// convolutions (pack_batch.hip kind 5 / qscale, conv3_f8.hip: pack_f8_kernel).
+// round |x| <= 448 to the nearest e4m3 value, ties to even
+__device__ __forceinline__ float round_e4m3(float x) {
+  const float a = fabsf(x);
+  int e;
+  (void)frexpf(a, &e);                                     // a = m 2^e, m in [0.5, 1)
+  const int fl = (a == 0.f || e - 1 < -6) ? -6 : e - 1;     // exponent of the binade (subnormals share -6)
+  const float step = ldexpf(1.0f, fl - 3);
+  return copysignf(rintf(a / step) * step, x);
+}
+// byte of an e4m3 value: sign | 4 exponent bits (bias 7) | 3 mantissa bits
+__device__ __forceinline__ unsigned char encode_e4m3(float v) {
+  const float a = fabsf(v);
+  const unsigned char s = v < 0.f || (v == 0.f && __builtin_signbit(v)) ? 0x80 : 0;
+  if (a == 0.f) return s;
+  int e;
+  const float m = frexpf(a, &e);                                  // a = m 2^e, m in [0.5, 1)
+  if (e - 1 < -6) return s | (unsigned char)(int)ldexpf(a, 9);    // subnormal: a / 2^-9
+  return s | (unsigned char)(((e - 1 + 7) << 3) | ((int)ldexpf(m, 4) - 8));
+}
+// per-output-channel scale 2^k with max |w| / 2^k <= 448 (k minimal)
+__device__ __forceinline__ float e4m3_scale(float amax) {
+  if (!(amax > 0.f)) return 1.0f;
+  int e;
+  const float m = frexpf(amax / 448.0f, &e);
+  return ldexpf(1.0f, m == 0.5f ? e - 1 : e);
+}
+// row scale of the split-precision operators (split16.hip, conv3_x2m.hip): s = 2^k with max |w'| * s in [2^9, 2^10), k clamped to +-40
+// (1 for an all-zero or non-finite row)
+__device__ __forceinline__ float split_row_scale(float amax) {
+  if (!(amax > 0.f && amax < INFINITY)) return 1.0f;
+  int e;
+  (void)frexpf(amax, &e);                                  // amax = f 2^e, f in [0.5, 1)
+  int k = 10 - e;
+  k = k < -40 ? -40 : k > 40 ? 40 : k;
+  return ldexpf(1.0f, k);
+}
 
 // fp16x2 split precision: v ~ hi + lo with hi = T(v), lo = T(v - hi) -- for T = f16 22 significant bits (the lo word is subnormal, i.e.
 // exact to 2^-24, once |v| < 2^-2: callers keep activations scaled up by a power of two).  Finite by construction: |v| is clamped
@@ -152,6 +209,14 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
+}
+
+// max over the 256 threads of a workgroup (LDS tree; red: [256]); every thread gets the result
+__device__ __forceinline__ float block_max_256(float v, float* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]); __syncthreads(); }
+  return red[0];
 }
 
 #define IUNET_OK 0

@@ -351,24 +351,7 @@ int launch_f8(ConvF8Params p, hipStream_t stream) {
 
 // fp32 [Cout][Cin][taps] -> e4m3 bytes in the K16 order + the per-output-channel scales.  One workgroup per output
 // channel: max |folded weight| -> scale 2^k (k minimal with max / 2^k <= 448), then every element of that channel.
-__device__ __forceinline__ float f8_round_e4m3(float x) {       // pack_batch.hip: round_e4m3
-  const float a = fabsf(x);
-  int e;
-  (void)frexpf(a, &e);
-  const int fl = (a == 0.f || e - 1 < -6) ? -6 : e - 1;
-  const float step = ldexpf(1.0f, fl - 3);
-  return copysignf(rintf(a / step) * step, x);
-}
-__device__ __forceinline__ unsigned char f8_encode_e4m3(float v) {   // v is an e4m3 value: sign | 4 exponent bits (bias 7) | 3 mantissa bits
-  const float a = fabsf(v);
-  unsigned char s = v < 0.f || (v == 0.f && __builtin_signbit(v)) ? 0x80 : 0;
-  if (a == 0.f) return s;
-  int e;
-  const float m = frexpf(a, &e);                                  // a = m 2^e, m in [0.5, 1)
-  if (e - 1 < -6) return s | (unsigned char)(int)ldexpf(a, 9);    // subnormal: a / 2^-9
-  return s | (unsigned char)(((e - 1 + 7) << 3) | ((int)ldexpf(m, 4) - 8));
-}
-
+// The fold, the e4m3 rounding / bytes and the scale are common.h's (bn_fold_*, round_e4m3, encode_e4m3, e4m3_scale), shared with pack_batch.hip.
 __global__ __launch_bounds__(256) void pack_f8_kernel(const float* __restrict__ w, const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, const float* __restrict__ mean,
                                                       const float* __restrict__ var, float eps, unsigned char* __restrict__ dst,
@@ -376,19 +359,15 @@ __global__ __launch_bounds__(256) void pack_f8_kernel(const float* __restrict__ 
                                                       int taps, int k128) {
 #pragma clang fp contract(off)
   const int co = blockIdx.x;
-  const float fs = gamma ? gamma[co] / sqrtf(var[co] + eps) : 1.0f;
+  const float fs = gamma ? bn_fold_scale(gamma, var, eps, co) : 1.0f;
   const float* wc = w + (long long)co * Cin * taps;
   __shared__ float red[256];
   float m = 0.f;
-  for (int i = threadIdx.x; i < Cin * taps; i += 256) m = fmaxf(m, fabsf(wc[i] * fs));
-  red[threadIdx.x] = m;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]); __syncthreads(); }
-  float sc = 1.0f;
-  if (red[0] > 0.f) { int e; const float mm = frexpf(red[0] / 448.0f, &e); sc = ldexpf(1.0f, mm == 0.5f ? e - 1 : e); }
+  for (int i = threadIdx.x; i < Cin * taps; i += 256) m = fmaxf(m, fabsf(bn_fold_mul(wc[i], fs)));
+  const float sc = e4m3_scale(block_max_256(m, red));
   if (threadIdx.x == 0) {
     wscale[co] = sc;
-    if (bias_out) bias_out[co] = gamma ? beta[co] - mean[co] * fs : 0.f;
+    if (bias_out) bias_out[co] = gamma ? bn_fold_bias(beta, mean, fs, co) : 0.f;
   }
   // elements of this output channel in the K16 order [cob32][chunk16][column pair][dy][2][64][8]: one thread = the 8 bytes of
   // one lane slot (8 consecutive input channels of one tap), written as one 8-byte store
@@ -408,7 +387,7 @@ __global__ __launch_bounds__(256) void pack_f8_kernel(const float* __restrict__ 
       const int ci0 = chunk * 16 + 8 * (qq & 1);
 #pragma unroll
       for (int j = 0; j < 8; ++j)
-        pk |= (unsigned long long)f8_encode_e4m3(f8_round_e4m3((wc[(ci0 + j) * taps + tap] * fs) / sc)) << (8 * j);
+        pk |= (unsigned long long)encode_e4m3(round_e4m3(bn_fold_mul(wc[(ci0 + j) * taps + tap], fs) / sc)) << (8 * j);
     }
     const int lane = qq * 16 + row;
     long long o = ((((((long long)cob * nchunk + chunk) * ncmb + c) * 3 + dy) * 2 + mt) * 64 + lane) * 8;

@@ -25,6 +25,7 @@
 // kind is a double buffer: while the consumers work on the 16-bit step of chunk c the loaders fill the fp8 buffers of chunk c, and
 // vice versa.  LDS: 34 816 (16-bit halo) + 30 720 (K16 operator) + 36 864 (e4m3 halo, z stride 192) + 27 648 (K128 operator) + 256.
 #include "common.h"
+#include "head_out.h"
 #include "x2_prep_desc.h"
 // tools/ab_build.sh conv3_x2m.hip -DX2M_ABLATE_NO_MFMA: timing only -- every matrix instruction becomes one multiply-add on the first words of its
 // operands (the LDS reads and the loaders stay): what the kernel takes without its matrix work (what bounds the x2m kernel)
@@ -74,9 +75,7 @@ struct ConvX2MParams {
   // predict.py:38 on the split words this conv would have stored -- the arithmetic of split16.hip's x2_head_kernel, bit for bit
   const float* head_w; const float* head_b;   // fp32 [ncls][32], [ncls]
   float inv_act;
-  float* logits; float* probs; unsigned char* cls;
-  long long oN, oC, oD, oH, oW;               // element strides of logits / probs
-  float divisor; int accumulate;
+  HeadOut head;                               // head_out.h: logits / probs / cls and how they are stored
   // 2^d max-pool on the way out (template POOL): besides y / y8 the launch writes the pooled tensor (hi + m8 planes of the half-size grid),
   // the words of x2m_maxpool_kernel on y / y8 (common.h: x2m_pool_take)
   void* pool_y;  long long pool_y_ss;         // hi planes, elements per sample
@@ -91,7 +90,7 @@ struct ConvX2MParams {
 // The head in the epilogue, in two parts.  (1) x2m_head_logits, per fragment: lane (q, l15) holds the 8 channels 8 q .. 8 q + 7 of voxel
 // l15 (fp32 epilogue values r, scaled by act_scale).  Summation order of split16.hip's x2_head_kernel: one fmaf chain per 8-channel plane
 // (= lane group), then (p0 + p1) + (p2 + p3) -- two butterfly exchanges between the lane groups; IEEE addition commutes, so all four
-// groups end with the same bits -- + bias: the unfused kernel's logits, bit for bit, in every lane group.  (2) x2m_head_store, once per
+// groups end with the same bits -- + bias: the unfused kernel's logits, bit for bit, in every lane group.  (2) head_store (head_out.h), once per
 // tile: a consumer wave owns FOUR fragments of 16 voxels and has four lane groups, so group q takes fragment q -- softmax, class map and
 // stores run once per VOXEL per lane (computed per fragment they ran four times over: +70 us on the 2 x 128^3 launch).
 // hw: LDS copy [NCLS][32] of the head weights + [NCLS] biases behind it.
@@ -118,38 +117,6 @@ __device__ __forceinline__ void x2m_head_logits(const ConvX2MParams& p, const fl
     l[c] = __fadd_rn(l[c], hw[NCLS * 32 + c]);
   }
 }
-template <int NCLS>
-__device__ __forceinline__ void x2m_head_store(const ConvX2MParams& p, const float (&l)[NCLS], bool ok, int n_img, long long nvox, long long vo,
-                                               int gz, int gy, int gx) {
-  if (!ok) return;
-  const long long obase = n_img * p.oN + gz * p.oD + gy * p.oH + gx * p.oW;
-  float mx = l[0];
-#pragma unroll
-  for (int c = 1; c < NCLS; ++c) mx = fmaxf(mx, l[c]);
-  if (p.logits) {
-#pragma unroll
-    for (int c = 0; c < NCLS; ++c) p.logits[obase + c * p.oC] = l[c];
-  }
-  float e[NCLS], sum = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCLS; ++c) { e[c] = expf(l[c] - mx); sum += e[c]; }
-  float pr[NCLS];
-  pr[0] = __fdiv_rn(e[0], sum);
-  float pm = pr[0]; int am = 0;
-#pragma unroll
-  for (int c = 1; c < NCLS; ++c) { pr[c] = __fdiv_rn(e[c], sum); if (pr[c] > pm) { pm = pr[c]; am = c; } }
-  if (p.cls) p.cls[n_img * nvox + vo] = (unsigned char)am;
-  if (p.probs) {
-#pragma unroll
-    for (int c = 0; c < NCLS; ++c) {
-      float* o = p.probs + obase + c * p.oC;
-      float rr = p.accumulate ? __fadd_rn(*o, pr[c]) : pr[c];
-      if (p.divisor != 1.0f) rr = __fdiv_rn(rr, p.divisor);
-      *o = rr;
-    }
-  }
-}
-
 // POOL: the 2 x 2 x 2 max-pool of the output rides along.  A consumer wave owns 4 rows of ONE z slice: it pools x (lane pairs, DPP) and y
 // (fragment pairs) in registers and leaves its 2 x 8 winners per 8-channel group in LDS (32 B each: eight 24-bit keys, common.h x2m_pool_keys; 2 KB per wave);
 // the z pair lives in the wave two further on, so the LOADER waves -- idle between their LDS-DMA issue and the step's barrier -- combine the
@@ -565,7 +532,7 @@ __global__ __launch_bounds__((XMTile<SMALL>::NCW * 64 + XM_NLT), 1) void conv3_x
     if constexpr (HEAD > 0) {
       const int row = row_first + q;                                            // this lane group's fragment
       const int gz = z0 + row / TY, gy = y0 + row % TY, gx = x0 + l15;
-      x2m_head_store<HEAD>(p, hl, gz < p.D && gy < p.H && gx < p.W, n_img, plane16b / 16, ((long long)gz * p.H + gy) * p.W + gx, gz, gy, gx);
+      if (gz < p.D && gy < p.H && gx < p.W) head_store<HEAD, true>(p.head, hl, n_img, plane16b / 16, ((long long)gz * p.H + gy) * p.W + gx, gz, gy, gx);
     }
   };
 
@@ -1114,7 +1081,7 @@ __global__ __launch_bounds__(8 * 64 + XM_NLT, 1) void conv2_x2m_kernel(ConvX2MPa
     }
     if constexpr (HEAD > 0) {
       const int gy = y0 + row_first + q / FX, gx = x0 + (q % FX) * 16 + l15;     // this lane group's fragment
-      x2m_head_store<HEAD>(p, hl, gy < p.H && gx < p.W, n_img, nvox, (long long)gy * p.W + gx, 0, gy, gx);
+      if (gy < p.H && gx < p.W) head_store<HEAD, true>(p.head, hl, n_img, nvox, (long long)gy * p.W + gx, 0, gy, gx);
     }
   };
 
@@ -1195,24 +1162,12 @@ __device__ __forceinline__ void x2m_prep_row(const float* __restrict__ w, float*
                                              float act_in, float act_out, int Cout, int Cin, int taps, int co, float* red) {
 #pragma clang fp contract(off)
   const int tid = threadIdx.x;
-  float a = 1.0f;
-  if (gamma) { const float s = var[co] + eps; a = gamma[co] / sqrtf(s); }
+  const float a = gamma ? bn_fold_scale(gamma, var, eps, co) : 1.0f;
   const int n = Cin * taps;
   const float* wc = w + (long long)co * n;
   float m = 0.f;
-  for (int i = tid; i < n; i += 256) m = fmaxf(m, fabsf(gamma ? wc[i] * a : wc[i]));
-  red[tid] = m;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]); __syncthreads(); }
-  m = red[0];
-  float s = 1.0f;
-  if (m > 0.f && m < INFINITY) {
-    int e;
-    (void)frexpf(m, &e);
-    int k = 10 - e;
-    k = k < -40 ? -40 : k > 40 ? 40 : k;
-    s = ldexpf(1.0f, k);
-  }
+  for (int i = tid; i < n; i += 256) m = fmaxf(m, fabsf(gamma ? bn_fold_mul(wc[i], a) : wc[i]));
+  const float s = split_row_scale(block_max_256(m, red));
   const int cob = co >> 5, r32 = co & 31;
   const int mt = (r32 >> 2) & 1, row = (r32 >> 3) * 4 + (r32 & 3);       // co = cob * 32 + 8 (row >> 2) + 4 m + (row & 3)
   const int nchunk = Cin >> 4;
@@ -1226,7 +1181,7 @@ __device__ __forceinline__ void x2m_prep_row(const float* __restrict__ w, float*
     for (int j = 0; j < 8; ++j) {
       const int ci = g8 * 8 + j;
       const float v0 = wc[(long long)ci * taps + tap];
-      float v = (gamma ? v0 * a : v0) * s;
+      float v = (gamma ? bn_fold_mul(v0, a) : v0) * s;
       v = fminf(fmaxf(v, -65504.f), 65504.f);
       const f16 h = (f16)v;
       const float res = v - (float)h;
@@ -1247,7 +1202,7 @@ __device__ __forceinline__ void x2m_prep_row(const float* __restrict__ w, float*
   if (tid == 0) {
     oscale[co] = act_out / (act_in * s);
     float b = 0.f;
-    if (gamma) { const float t = mean[co] * a; b = beta[co] - t; }
+    if (gamma) b = bn_fold_bias(beta, mean, a, co);
     bias_out[co] = b * act_out;
   }
 }
@@ -1445,8 +1400,7 @@ static int x2m_conv_impl(const char* who, int nd, const void* x, long long x_ss,
   p.N = N; p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.epi = epi; p.sat = (int*)sat;
   p.tilesZ = p.tilesY = p.tilesX = 0;
   p.bz = p.by = p.bx = p.nbz = p.nby = p.nbx = 0;
-  p.head_w = p.head_b = nullptr; p.inv_act = 0.f; p.logits = p.probs = nullptr; p.cls = nullptr;
-  p.oN = p.oC = p.oD = p.oH = p.oW = 0; p.divisor = 1.f; p.accumulate = 0;
+  p.head_w = p.head_b = nullptr; p.inv_act = 0.f; p.head = HeadOut{nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 1.f, 0};
   p.pool_y = py; p.pool_y_ss = py_ss; p.pool_y8 = py8; p.pool_y8_ss = py8_ss;
   p.f_x = p.f_w = nullptr; p.f_oscale = p.f_bias = nullptr; p.f_sN = p.f_sH = p.f_sW = 0; p.f_dtype = 0; p.f_act = 0.f;
   hipStream_t s = (hipStream_t)stream;
@@ -1526,8 +1480,7 @@ int iunet_x2m_first_stage_fwd(const void* x, int in_dtype, const long long* in_s
   p.N = N; p.D = 1; p.H = H; p.W = W; p.Cin = 32; p.Cout = 32; p.epi = 2; p.sat = (int*)sat;
   p.tilesZ = p.tilesY = p.tilesX = 0;
   p.bz = p.by = p.bx = p.nbz = p.nby = p.nbx = 0;
-  p.head_w = p.head_b = nullptr; p.inv_act = 0.f; p.logits = p.probs = nullptr; p.cls = nullptr;
-  p.oN = p.oC = p.oD = p.oH = p.oW = 0; p.divisor = 1.f; p.accumulate = 0;
+  p.head_w = p.head_b = nullptr; p.inv_act = 0.f; p.head = HeadOut{nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 1.f, 0};
   p.pool_y = py; p.pool_y_ss = py_ss; p.pool_y8 = py8; p.pool_y8_ss = py8_ss;
   p.f_x = x; p.f_sN = in_strides[0]; p.f_sH = in_strides[3]; p.f_sW = in_strides[4]; p.f_dtype = in_dtype;
   p.f_w = fw; p.f_oscale = (const float*)f_oscale; p.f_bias = (const float*)f_bias; p.f_act = act_scale;
@@ -1565,9 +1518,7 @@ int iunet_x2m_conv_head_fwd(int nd, const void* x, long long x_ss, const void* x
   p.tilesZ = p.tilesY = p.tilesX = 0;
   p.bz = p.by = p.bx = p.nbz = p.nby = p.nbx = 0;
   p.head_w = (const float*)head_w; p.head_b = (const float*)head_b; p.inv_act = 1.0f / act_scale;
-  p.logits = (float*)logits; p.probs = (float*)probs; p.cls = (unsigned char*)cls;
-  p.oN = out_strides[0]; p.oC = out_strides[1]; p.oD = out_strides[2]; p.oH = out_strides[3]; p.oW = out_strides[4];
-  p.divisor = divisor; p.accumulate = accumulate;
+  if (const int rc = head_out_fill(p.head, "x2m_conv_head", logits, probs, cls, out_strides, divisor, accumulate)) return rc;
   p.pool_y = p.pool_y8 = nullptr; p.pool_y_ss = p.pool_y8_ss = 0;
   p.f_x = p.f_w = nullptr; p.f_oscale = p.f_bias = nullptr; p.f_sN = p.f_sH = p.f_sW = 0; p.f_dtype = 0; p.f_act = 0.f;
   hipStream_t s = (hipStream_t)stream;

@@ -22,6 +22,7 @@
 // The GEMMs are gather_gemm.h's skeletons under the DlFwdGather / DlWgGather policies (segformer.hip calls the forward for M^T dZ).
 #include "common.h"
 #include "gather_gemm.h"
+#include "head_out.h"
 #include "loss_terms.h"
 
 namespace {
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(256) void dl_pack_kernel(const float* __restrict__ 
   const int kidx = (int)(i % kvol), ci = (int)((i / kvol) % Cin), co = (int)(i / ((long long)kvol * Cin));
   float v = w[((long long)co * Cin_tot + ci_off + ci) * kvol + kidx];
   if (mode == 0) {
-    if (gamma != nullptr) v *= bn_fold_scale(gamma, var, eps, co);
+    if (gamma != nullptr) v = bn_fold_mul(v, bn_fold_scale(gamma, var, eps, co));
     dst[(long long)co * ld + k_off + (long long)kidx * Cin + ci] = (OT)v;
     if (bias_out != nullptr && gamma != nullptr && ci == 0 && kidx == 0) bias_out[co] = bn_fold_bias(beta, mean, bn_fold_scale(gamma, var, eps, co), co);
   } else {
@@ -219,7 +220,7 @@ __global__ __launch_bounds__(256) void dl_pool_psb_kernel(const float* __restric
   const int n = i / C, c = i - n * C;
   float s = 0.f;
   for (int j = 0; j < C; ++j) s = fmaf(wproj[(long long)c * 5 * C + 4 * C + j], bp[(long long)n * C + j], s);
-  if (pgamma != nullptr) s *= bn_fold_scale(pgamma, pvar, eps, c);
+  if (pgamma != nullptr) s = bn_fold_mul(s, bn_fold_scale(pgamma, pvar, eps, c));
   psb[i] = s;
 }
 
@@ -341,9 +342,7 @@ __device__ __forceinline__ void dl_up_logits(const float* lc, int n, int d, int 
 
 struct DlUp {
   const float* lc; int Dc, Hc, Wc, s;
-  float* logits; float* probs; unsigned char* cls;
-  long long oN, oC, oD, oH, oW;
-  float divisor; int accumulate;
+  HeadOut o;
   int N, D, H, W;
 };
 
@@ -357,32 +356,7 @@ __global__ __launch_bounds__(256) void dl_up_head_kernel(DlUp p) {
   const int gx = (int)(v % p.W), gy = (int)((v / p.W) % p.H), gz = (int)(v / ((long long)p.W * p.H));
   float l[NCLS];
   dl_up_logits<NCLS, ND>(p.lc, n, gz, gy, gx, p.Dc, p.Hc, p.Wc, p.D, p.H, p.W, l);
-  const long long obase = n * p.oN + gz * p.oD + gy * p.oH + gx * p.oW;
-  float mx = l[0];
-#pragma unroll
-  for (int c = 1; c < NCLS; ++c) mx = fmaxf(mx, l[c]);
-  if (p.logits) {
-#pragma unroll
-    for (int c = 0; c < NCLS; ++c) p.logits[obase + c * p.oC] = l[c];
-  }
-  float e[NCLS], s = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCLS; ++c) { e[c] = __expf(l[c] - mx); s += e[c]; }
-  const float inv = 1.0f / s;
-  float pm = e[0] * inv; int am = 0;
-#pragma unroll
-  for (int c = 1; c < NCLS; ++c) { const float pc = e[c] * inv; if (pc > pm) { pm = pc; am = c; } }
-  if (p.cls) p.cls[n * vox + v] = (unsigned char)am;
-  if (p.probs) {
-#pragma unroll
-    for (int c = 0; c < NCLS; ++c) {
-      const float pr = e[c] * inv;
-      float* o = p.probs + obase + c * p.oC;
-      float r = p.accumulate ? __fadd_rn(*o, pr) : pr;
-      if (p.divisor != 1.0f) r = __fdiv_rn(r, p.divisor);
-      *o = r;
-    }
-  }
+  head_store<NCLS, false>(p.o, l, n, vox, v, gz, gy, gx);
 }
 
 #define DL_UPL_ITER 8
@@ -792,13 +766,9 @@ int iunet_dl_up_head(int nd, const void* lc, int ncls, int Dc, int Hc, int Wc, i
                      const long long* out_strides, float divisor, int accumulate, int N, void* stream) {
   const int rc = dl_up_check("dl_up_head", nd, lc, ncls, N, Dc, Hc, Wc, s);
   if (rc != IUNET_OK) return rc;
-  IUNET_REQUIRE(out_strides || (!logits && !probs), "dl_up_head: logits / probs need out_strides");
   DlUp p;
-  p.lc = (const float*)lc; p.Dc = Dc; p.Hc = Hc; p.Wc = Wc; p.s = s;
-  p.logits = (float*)logits; p.probs = (float*)probs; p.cls = (unsigned char*)cls;
-  p.oN = out_strides ? out_strides[0] : 0; p.oC = out_strides ? out_strides[1] : 0; p.oD = out_strides ? out_strides[2] : 0;
-  p.oH = out_strides ? out_strides[3] : 0; p.oW = out_strides ? out_strides[4] : 0;
-  p.divisor = divisor; p.accumulate = accumulate; p.N = N;
+  if (const int rc2 = head_out_fill(p.o, "dl_up_head", logits, probs, cls, out_strides, divisor, accumulate)) return rc2;
+  p.lc = (const float*)lc; p.Dc = Dc; p.Hc = Hc; p.Wc = Wc; p.s = s; p.N = N;
   p.D = nd == 3 ? Dc * s : 1; p.H = Hc * s; p.W = Wc * s;
   const long long vox = (long long)p.D * p.H * p.W;
   const dim3 grid((unsigned)((vox + 255) / 256), N);

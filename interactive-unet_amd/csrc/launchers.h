@@ -46,8 +46,8 @@ int iunet_convT_launch(int dtype, int nd, const void* x, long long x_ss, void* y
                        const float* bias, int N, int D, int H, int W, int Cin, int Cout, hipStream_t stream, int out8 = 0);
 int iunet_pack_convT_launch(int dtype, const float* w, void* dst, int Cin, int Cout, int npos, hipStream_t stream);
 int iunet_head_launch(int dtype, const void* x, long long x_ss, int C0, const float* w, const float* bias, int ncls,
-                      float* logits, float* probs, unsigned char* cls, long long oN, long long oC, long long oD,
-                      long long oH, long long oW, float divisor, int accumulate, int N, int D, int H, int W,
+                      float* logits, float* probs, unsigned char* cls, const long long* os, float divisor, int accumulate, int N,
+                      int D, int H, int W,
                       hipStream_t stream);
 
 // precise_f32.hip: fp32 parity mode

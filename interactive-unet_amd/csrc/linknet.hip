@@ -250,7 +250,7 @@ __global__ __launch_bounds__(256) void lk_pack_kernel(const float* __restrict__ 
       const int t = (int)(kk / Cout), co = (int)(kk - (long long)t * Cout);
       v = w[((long long)row * Cout + co) * (1 << (2 * nd)) + t];
     }
-    if (gamma != nullptr && (kind == 0 || kind == 2)) v *= bn_fold_scale(gamma, var, eps, row);
+    if (gamma != nullptr && (kind == 0 || kind == 2)) v = bn_fold_mul(v, bn_fold_scale(gamma, var, eps, row));
   }
   dst[i] = (OT)v;
   if (bias_out != nullptr && gamma != nullptr && cls == 0 && kk == 0 && (kind == 0 || kind == 2))

@@ -17,17 +17,14 @@
 namespace {
 
 // eval-mode BatchNorm fold of the 16-bit modes: scale = gamma / sqrt(var + eps), bias = beta - mean * scale, every operation rounded
-// on its own (pack_batch.hip: fold_scale / fold_bias; oracle/unet_ref.py: fold_bn)
+// on its own (common.h: bn_fold_scale / bn_fold_bias; oracle/unet_ref.py: fold_bn)
 __global__ void net_fold_bn_kernel(const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
                                    const float* __restrict__ var, float eps, float* __restrict__ scale, float* __restrict__ bias, int C) {
-#pragma clang fp contract(off)
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const float s = var[c] + eps;
-  const float a = gamma[c] / sqrtf(s);
-  const float t = mean[c] * a;
+  const float a = bn_fold_scale(gamma, var, eps, c);
   scale[c] = a;
-  bias[c] = beta[c] - t;
+  bias[c] = bn_fold_bias(beta, mean, a, c);
 }
 
 long long align256(long long v) { return (v + 255) & ~255ll; }

@@ -3,58 +3,16 @@
 // ~150 launches per step.  A descriptor table in device memory (built once by the host: all pointers are
 // stable) drives one kernel; blockIdx.y selects the layer.  The element mappings are the ones of the per-layer
 // kernels (conv3_host_pack.hip, pointwise.hip, train_misc.hip) -- tests/test_gpu_kernels.py checks bit equality.
+// The arithmetic (BatchNorm fold, e4m3 codec and scales, channel maximum) is common.h's, shared with every other pack kernel.
 #include "common.h"
 #include "pack_desc.h"
 
 namespace {
 
 
-// round |x| <= 448 to the nearest OCP e4m3 value (4 exponent bits, bias 7, 3 mantissa bits, subnormal step 2^-9), ties to even
-__device__ __forceinline__ float round_e4m3(float x) {
-  const float a = fabsf(x);
-  int e;
-  (void)frexpf(a, &e);                                     // a = m 2^e, m in [0.5, 1)
-  const int fl = (a == 0.f || e - 1 < -6) ? -6 : e - 1;     // exponent of the binade (subnormals share -6)
-  const float step = ldexpf(1.0f, fl - 3);
-  return copysignf(rintf(a / step) * step, x);
-}
-
-// per-output-channel scale 2^k with max |w| / 2^k <= 448 (k minimal)
-__device__ __forceinline__ float e4m3_scale(float amax) {
-  if (!(amax > 0.f)) return 1.0f;
-  int e;
-  const float m = frexpf(amax / 448.0f, &e);
-  return ldexpf(1.0f, m == 0.5f ? e - 1 : e);
-}
-
-// byte of an e4m3 value (conv3_f8.hip: f8_encode_e4m3): sign | 4 exponent bits (bias 7) | 3 mantissa bits
-__device__ __forceinline__ unsigned char encode_e4m3(float v) {
-  const float a = fabsf(v);
-  const unsigned char s = v < 0.f || (v == 0.f && __builtin_signbit(v)) ? 0x80 : 0;
-  if (a == 0.f) return s;
-  int e;
-  const float m = frexpf(a, &e);                                  // a = m 2^e, m in [0.5, 1)
-  if (e - 1 < -6) return s | (unsigned char)(int)ldexpf(a, 9);    // subnormal: a / 2^-9
-  return s | (unsigned char)(((e - 1 + 7) << 3) | ((int)ldexpf(m, 4) - 8));
-}
-
-// The fold is the IEEE fp32 formula of the host / oracle (oracle/unet_ref.py: fold_bn): every operation rounded
-// on its own (no fma contraction; hipcc's default sqrt and divide are correctly rounded).
-__device__ __forceinline__ float fold_scale(const PackDesc& d, int co) {
-#pragma clang fp contract(off)
-  if (!d.gamma) return 1.0f;
-  const float s = d.var[co] + d.eps;
-  return d.gamma[co] / sqrtf(s);
-}
-__device__ __forceinline__ float fold_bias(const PackDesc& d, int co) {
-#pragma clang fp contract(off)
-  const float t = d.mean[co] * fold_scale(d, co);
-  return d.beta[co] - t;
-}
-__device__ __forceinline__ float mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
+// The BatchNorm fold of a descriptor (common.h: bn_fold_scale / bn_fold_mul / bn_fold_bias, the one definition); no gamma: no fold
+__device__ __forceinline__ float fold_scale(const PackDesc& d, int co) { return d.gamma ? bn_fold_scale(d.gamma, d.var, d.eps, co) : 1.0f; }
+__device__ __forceinline__ float fold_bias(const PackDesc& d, int co) { return bn_fold_bias(d.beta, d.mean, fold_scale(d, co), co); }
 
 __device__ __forceinline__ float elem(const PackDesc& d, long long i, int& oc) {
   oc = 0;
@@ -76,7 +34,7 @@ __device__ __forceinline__ float elem(const PackDesc& d, long long i, int& oc) {
     if (col >= ncol) return 0.f;
     const int tap = ((col / 3) * 3 + dy) * 3 + (col % 3);
     oc = co;
-    if (!d.dgrad) return mul_rn(w[((long long)co * d.Cin + ci) * d.taps + tap], fold_scale(d, co));
+    if (!d.dgrad) return bn_fold_mul(w[((long long)co * d.Cin + ci) * d.taps + tap], fold_scale(d, co));
     return w[((long long)ci * d.Cin + co) * d.taps + (d.taps - 1 - tap)];
   }
   if (d.kind == 2) {                                   // first conv: [cob32][kstep][2][64][8], k = tap * Cin + c
@@ -87,7 +45,7 @@ __device__ __forceinline__ float elem(const PackDesc& d, long long i, int& oc) {
     const int k = 32 * ks + 8 * qq + j;
     if (k >= KK) return 0.f;
     oc = co;
-    return mul_rn(w[(co * d.Cin + k % d.Cin) * d.taps + k / d.Cin], fold_scale(d, co));
+    return bn_fold_mul(w[(co * d.Cin + k % d.Cin) * d.taps + k / d.Cin], fold_scale(d, co));
   }
   const int npos = d.taps;
   if (d.kind == 3) {                                   // convT fwd: [cob32][kstep][pos][t][64][8]
@@ -203,7 +161,7 @@ __device__ __forceinline__ void pack_k16_block(const PackDesc& d, int blk, float
         const float fs = fold_scale(d, oc);
         const float* src = tile + co_l * rowlen + ci_l * taps + tap;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = mul_rn(src[j * taps], fs);
+        for (int j = 0; j < 8; ++j) v[j] = bn_fold_mul(src[j * taps], fs);
       } else {
         const float* src = tile + ci_l * rowlen + co_l * taps + (taps - 1 - tap);
 #pragma unroll
@@ -213,7 +171,7 @@ __device__ __forceinline__ void pack_k16_block(const PackDesc& d, int blk, float
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = 0.f;
     }
-    if (d.kind == 5) {                                 // e4m3 bytes of w * fold / scale (the arithmetic of conv3_f8.hip: pack_f8_kernel)
+    if (d.kind == 5) {                                 // e4m3 bytes of w * fold / scale (as conv3_f8.hip: pack_f8_kernel)
       const float sc = d.qscale[oc];
       unsigned long long pk = 0;
       if (col < ncol) {
@@ -304,7 +262,7 @@ __device__ __forceinline__ void pack_k16c_block(const PackDesc& d, int blk, floa
       const float fs = fold_scale(d, oc);
       const float* src = tile + co_l * rowlen + ci_l * taps + tap;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = mul_rn(src[j * taps], fs);
+      for (int j = 0; j < 8; ++j) v[j] = bn_fold_mul(src[j * taps], fs);
     } else {
       const float* src = tile + ci_l * rowlen + co_l * taps + (taps - 1 - tap);
 #pragma unroll
@@ -424,12 +382,10 @@ __global__ __launch_bounds__(256) void pack_qscale_kernel(const PackDesc* __rest
   } else {                                               // conv: w[co][ci][tap], folded
     const float fs = fold_scale(d, co);
     const float* w = d.w + (long long)co * d.Cin * d.taps;
-    for (int i = threadIdx.x; i < d.Cin * d.taps; i += 256) m = fmaxf(m, fabsf(mul_rn(w[i], fs)));
+    for (int i = threadIdx.x; i < d.Cin * d.taps; i += 256) m = fmaxf(m, fabsf(bn_fold_mul(w[i], fs)));
   }
-  red[threadIdx.x] = m;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]); __syncthreads(); }
-  if (threadIdx.x == 0) d.qscale[co] = e4m3_scale(red[0]);
+  m = block_max_256(m, red);
+  if (threadIdx.x == 0) d.qscale[co] = e4m3_scale(m);
 }
 
 }  // namespace

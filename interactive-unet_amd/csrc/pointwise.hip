@@ -4,6 +4,7 @@
 // its 8x larger output, not by the matrix cores) and the 1x1 head fused with
 // softmax / argmax (writes the caller's NCHW fp32 / uint8 / strided accumulator).
 #include "common.h"
+#include "head_out.h"
 
 namespace {
 
@@ -659,11 +660,7 @@ struct HeadParams {
   const void* x; long long x_sstride; int planes;     // C0/8
   const float* w;      // [ncls][C0] fp32
   const float* bias;   // [ncls]
-  float* logits;       // optional, generic strides
-  float* probs;        // optional, generic strides
-  unsigned char* cls;  // optional, [N][vox]
-  long long oN, oC, oD, oH, oW;   // output strides (elements) for logits / probs
-  float divisor; int accumulate;  // probs: out = ((accumulate ? out : 0) + p) / divisor  (predict.py:101-110)
+  HeadOut o;           // head_out.h: logits / probs / cls and how they are stored
   int N, D, H, W;
 };
 
@@ -688,34 +685,7 @@ __global__ __launch_bounds__(256) void head_kernel(HeadParams p) {
     }
   }
   const int gx = (int)(v % p.W), gy = (int)((v / p.W) % p.H), gz = (int)(v / ((long long)p.W * p.H));
-  const long long obase = n * p.oN + gz * p.oD + gy * p.oH + gx * p.oW;
-  float mx = l[0];
-#pragma unroll
-  for (int c = 1; c < NCLS; ++c) mx = fmaxf(mx, l[c]);
-  if (p.logits) {
-#pragma unroll
-    for (int c = 0; c < NCLS; ++c) p.logits[obase + c * p.oC] = l[c];
-  }
-  float e[NCLS], s = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCLS; ++c) { e[c] = __expf(l[c] - mx); s += e[c]; }
-  const float inv = 1.0f / s;
-  // class map = first maximum of the probabilities, exactly what np.argmax over the
-  // returned softmax gives (predict.py:38)
-  float pm = e[0] * inv; int am = 0;
-#pragma unroll
-  for (int c = 1; c < NCLS; ++c) { const float pc = e[c] * inv; if (pc > pm) { pm = pc; am = c; } }
-  if (p.cls) p.cls[n * vox + v] = (unsigned char)am;
-  if (p.probs) {
-#pragma unroll
-    for (int c = 0; c < NCLS; ++c) {
-      const float pr = e[c] * inv;
-      float* o = p.probs + obase + c * p.oC;
-      float r = p.accumulate ? __fadd_rn(*o, pr) : pr;
-      if (p.divisor != 1.0f) r = __fdiv_rn(r, p.divisor);
-      *o = r;
-    }
-  }
+  head_store<NCLS, false>(p.o, l, n, vox, v, gz, gy, gx);
 }
 
 }  // namespace
@@ -859,13 +829,12 @@ int iunet_pack_convT_launch(int dtype, const float* w, void* dst, int Cin, int C
 }
 
 int iunet_head_launch(int dtype, const void* x, long long x_ss, int C0, const float* w, const float* bias, int ncls,
-                      float* logits, float* probs, unsigned char* cls, long long oN, long long oC, long long oD,
-                      long long oH, long long oW, float divisor, int accumulate, int N, int D, int H, int W,
-                      hipStream_t stream) {
+                      float* logits, float* probs, unsigned char* cls, const long long* os, float divisor, int accumulate, int N,
+                      int D, int H, int W, hipStream_t stream) {
   IUNET_REQUIRE(ncls >= 2 && ncls <= 10, "head: num_classes must be 2..10 (got %d)", ncls);
   HeadParams p;
-  p.x = x; p.x_sstride = x_ss; p.planes = C0 / 8; p.w = w; p.bias = bias; p.logits = logits; p.probs = probs; p.cls = cls;
-  p.oN = oN; p.oC = oC; p.oD = oD; p.oH = oH; p.oW = oW; p.divisor = divisor; p.accumulate = accumulate;
+  p.x = x; p.x_sstride = x_ss; p.planes = C0 / 8; p.w = w; p.bias = bias;
+  if (const int rc = head_out_fill(p.o, "head", logits, probs, cls, os, divisor, accumulate)) return rc;
   p.N = N; p.D = D; p.H = H; p.W = W;
   const long long vox = (long long)D * H * W;
   dim3 grid((unsigned)((vox + 255) / 256), N);

@@ -19,6 +19,7 @@
 //                                scatter store
 // plus a max-pool and the 1x1 head + softmax / argmax.
 #include "common.h"
+#include "head_out.h"
 
 namespace {
 
@@ -185,15 +186,12 @@ __global__ __launch_bounds__(256) void f32_conv_kernel(F32ConvParams p) {
 // fp32 master weights -> the operator order above.  conv: w [Cout][Cin][taps]; transposed: w [Cin][Cout][npos].
 // dst [npos or 1][Cout/32][chunks][taps or 1][4 k pairs][2 cout tiles][2 k parity][16]; channels >= Cin are zeros.
 // A non-null gamma folds an eval-mode BatchNorm exactly as the oracle does (separately rounded fp32 operations):
-// a = gamma / sqrt(var + eps), w' = w * a, bias_out = beta - mean * a.  Written with plain operators under `fp contract(off)` and
-// sqrtf, which this build rounds correctly: __fsqrt_rn is, despite its name, the hardware's approximate v_sqrt_f32 here (one unit off
-// for ~8 % of arguments), and __fsub_rn(beta, __fmul_rn(mean, a)) is inlined from a header compiled with contraction on, so it became
-// one fma (the pragma is lexical).
+// a = gamma / sqrt(var + eps), w' = w * a, bias_out = beta - mean * a -- common.h: bn_fold_scale / bn_fold_mul / bn_fold_bias, which say
+// why they are written with plain operators and sqrtf under a lexical `fp contract(off)`.
 __global__ void f32_pack_conv_kernel(const float* __restrict__ w, float* __restrict__ dst, float* __restrict__ bias_out,
                                      const float* __restrict__ gamma, const float* __restrict__ beta,
                                      const float* __restrict__ mean, const float* __restrict__ var, float eps, int Cout,
                                      int Cin, int taps, int transposed) {
-#pragma clang fp contract(off)
   const int nchunks = (Cin + 7) / 8, ncob = Cout / 32;
   const int T = transposed ? 1 : taps, NPOS = transposed ? taps : 1;
   const long long total = (long long)NPOS * ncob * nchunks * T * 256;
@@ -211,15 +209,13 @@ __global__ void f32_pack_conv_kernel(const float* __restrict__ w, float* __restr
     float v = 0.f;
     if (ci < Cin) {
       v = transposed ? w[((long long)ci * Cout + co) * taps + pos] : w[((long long)co * Cin + ci) * taps + tap];
-      if (gamma) v = v * (gamma[co] / sqrtf(var[co] + eps));
+      if (gamma) v = bn_fold_mul(v, bn_fold_scale(gamma, var, eps, co));
     }
     dst[i] = v;
   }
   if (gamma && bias_out)
-    for (int co = blockIdx.x * blockDim.x + threadIdx.x; co < Cout; co += gridDim.x * blockDim.x) {
-      const float a = gamma[co] / sqrtf(var[co] + eps);
-      bias_out[co] = beta[co] - mean[co] * a;
-    }
+    for (int co = blockIdx.x * blockDim.x + threadIdx.x; co < Cout; co += gridDim.x * blockDim.x)
+      bias_out[co] = bn_fold_bias(beta, mean, bn_fold_scale(gamma, var, eps, co), co);
 }
 
 template <int ND>
@@ -249,9 +245,7 @@ __global__ __launch_bounds__(256) void f32_maxpool_kernel(const float* __restric
 struct F32HeadParams {
   const float* x; long long x_ss; int C0;
   const float* w; const float* bias;
-  float* logits; float* probs; unsigned char* cls;
-  long long oN, oC, oD, oH, oW;
-  float divisor; int accumulate;
+  HeadOut o;
   int N, D, H, W;
 };
 
@@ -275,32 +269,7 @@ __global__ __launch_bounds__(256) void f32_head_kernel(F32HeadParams p) {
 #pragma unroll
   for (int c = 0; c < NCLS; ++c) l[c] = __fadd_rn(l[c], p.bias[c]);
   const int gx = (int)(v % p.W), gy = (int)((v / p.W) % p.H), gz = (int)(v / ((long long)p.W * p.H));
-  const long long obase = n * p.oN + gz * p.oD + gy * p.oH + gx * p.oW;
-  float mx = l[0];
-#pragma unroll
-  for (int c = 1; c < NCLS; ++c) mx = fmaxf(mx, l[c]);
-  if (p.logits) {
-#pragma unroll
-    for (int c = 0; c < NCLS; ++c) p.logits[obase + c * p.oC] = l[c];
-  }
-  float e[NCLS], s = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCLS; ++c) { e[c] = expf(l[c] - mx); s += e[c]; }
-  float pm = __fdiv_rn(e[0], s); int am = 0;
-  float pr[NCLS];
-  pr[0] = pm;
-#pragma unroll
-  for (int c = 1; c < NCLS; ++c) { pr[c] = __fdiv_rn(e[c], s); if (pr[c] > pm) { pm = pr[c]; am = c; } }
-  if (p.cls) p.cls[n * vox + v] = (unsigned char)am;
-  if (p.probs) {
-#pragma unroll
-    for (int c = 0; c < NCLS; ++c) {
-      float* o = p.probs + obase + c * p.oC;
-      float r = p.accumulate ? __fadd_rn(*o, pr[c]) : pr[c];
-      if (p.divisor != 1.0f) r = __fdiv_rn(r, p.divisor);
-      *o = r;
-    }
-  }
+  head_store<NCLS, true>(p.o, l, n, vox, v, gz, gy, gx);
 }
 
 }  // namespace
@@ -359,8 +328,8 @@ int iunet_f32_head_launch(const float* x, long long x_ss, int C0, const float* w
                           float* probs, unsigned char* cls, const long long* os, float divisor, int accumulate, int N, int D,
                           int H, int W, hipStream_t stream) {
   F32HeadParams p;
-  p.x = x; p.x_ss = x_ss; p.C0 = C0; p.w = w; p.bias = bias; p.logits = logits; p.probs = probs; p.cls = cls;
-  p.oN = os[0]; p.oC = os[1]; p.oD = os[2]; p.oH = os[3]; p.oW = os[4]; p.divisor = divisor; p.accumulate = accumulate;
+  p.x = x; p.x_ss = x_ss; p.C0 = C0; p.w = w; p.bias = bias;
+  if (const int rc = head_out_fill(p.o, "f32_head", logits, probs, cls, os, divisor, accumulate)) return rc;
   p.N = N; p.D = D; p.H = H; p.W = W;
   const long long vox = (long long)D * H * W;
   dim3 grid((unsigned)((vox + 255) / 256), N);

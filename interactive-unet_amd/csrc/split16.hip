@@ -20,6 +20,7 @@
 // (BatchNorm fold in the oracle's fp32 operation order, scaling, split into the virtual fp32 operator that the ordinary pack
 // kernels then reorder), the first convolution, the max-pool, the transposed convolution and the head.
 #include "common.h"
+#include "head_out.h"
 #include "x2_prep_desc.h"
 
 namespace {
@@ -32,7 +33,7 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 // kind 1: convT w [Cin][Cout][npos]   -> wv [3 Cin][Cout][npos], [hi | hi | lo] over all channels (activation parts [hi | lo | hi])
 // kind 2: convT w [Cin][Cout][npos]   -> wv [2 Cin][Cout][npos]: both words of every entry once, in chunks of kc k-steps (of 32
 // channels) [chunk][hi | lo][kc][32] -- the operator x2_convT_lds_kernel keeps in LDS.  One workgroup per output channel:
-// a = gamma / sqrt(var + eps), w' = w * a, bias' = beta - mean * a (each operation rounded on its own, oracle/unet_ref.py fold_bn),
+// a = gamma / sqrt(var + eps), w' = w * a, bias' = beta - mean * a (common.h: bn_fold_*, each operation rounded on its own),
 // s = 2^k with max |w'| * s in [2^9, 2^10), w'' = w' * s (exact), hi = f16(w''), lo = f16(w'' - hi);
 // oscale = act_out / (act_in * s), bias_out = bias' * act_out (powers of two: exact).
 __device__ __forceinline__ void x2_prep_row(const float* __restrict__ w, float* __restrict__ wv, float* __restrict__ oscale,
@@ -42,28 +43,16 @@ __device__ __forceinline__ void x2_prep_row(const float* __restrict__ w, float* 
                                             float act_in, float act_out, int Cout, int Cin, int taps, int kind, int kc, int co, float* red) {
 #pragma clang fp contract(off)
   const int tid = threadIdx.x;
-  float a = 1.0f;
-  if (gamma) { const float s = var[co] + eps; a = gamma[co] / sqrtf(s); }
+  const float a = gamma ? bn_fold_scale(gamma, var, eps, co) : 1.0f;
   const int n = Cin * taps;
   auto src = [&](int i) -> float {                       // i = ci * taps + tap
     const int ci = i / taps, t = i - ci * taps;
     const float v = kind == 0 ? w[((long long)co * Cin + ci) * taps + t] : w[((long long)ci * Cout + co) * taps + t];
-    return gamma ? v * a : v;
+    return gamma ? bn_fold_mul(v, a) : v;
   };
   float m = 0.f;
   for (int i = tid; i < n; i += 256) m = fmaxf(m, fabsf(src(i)));
-  red[tid] = m;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]); __syncthreads(); }
-  m = red[0];
-  float s = 1.0f;
-  if (m > 0.f && m < INFINITY) {
-    int e;
-    (void)frexpf(m, &e);                                 // m = f 2^e, f in [0.5, 1)
-    int k = 10 - e;
-    k = k < -40 ? -40 : k > 40 ? 40 : k;
-    s = ldexpf(1.0f, k);
-  }
+  const float s = split_row_scale(block_max_256(m, red));
   for (int i = tid; i < n; i += 256) {
     const int ci = i / taps, t = i - ci * taps;
     const float v = src(i) * s;
@@ -89,7 +78,7 @@ __device__ __forceinline__ void x2_prep_row(const float* __restrict__ w, float* 
   if (tid == 0) {
     oscale[co] = act_out / (act_in * s);
     float b = 0.f;
-    if (gamma) { const float t = mean[co] * a; b = beta[co] - t; }
+    if (gamma) b = bn_fold_bias(beta, mean, a, co);
     else if (bias_in) b = bias_in[co];
     bias_out[co] = b * act_out;
   }
@@ -463,9 +452,7 @@ __global__ __launch_bounds__(256, RES ? 2 : 1) void x2_convT_lds_kernel(X2ConvTP
 struct X2HeadParams {
   const void* x; long long x_sstride; int planes, x_lo;
   const float* w; const float* bias; float inv_act;
-  float* logits; float* probs; unsigned char* cls;
-  long long oN, oC, oD, oH, oW;
-  float divisor; int accumulate;
+  HeadOut o;
   int N, D, H, W;
 };
 
@@ -517,32 +504,7 @@ __global__ __launch_bounds__(256) void x2_head_kernel(X2HeadParams p) {
 #pragma unroll
   for (int c = 0; c < NCLS; ++c) l[c] = __fadd_rn(l[c], p.bias[c]);
   const int gx = (int)(v % p.W), gy = (int)((v / p.W) % p.H), gz = (int)(v / ((long long)p.W * p.H));
-  const long long obase = n * p.oN + gz * p.oD + gy * p.oH + gx * p.oW;
-  float mx = l[0];
-#pragma unroll
-  for (int c = 1; c < NCLS; ++c) mx = fmaxf(mx, l[c]);
-  if (p.logits) {
-#pragma unroll
-    for (int c = 0; c < NCLS; ++c) p.logits[obase + c * p.oC] = l[c];
-  }
-  float e[NCLS], s = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCLS; ++c) { e[c] = expf(l[c] - mx); s += e[c]; }
-  float pr[NCLS];
-  pr[0] = __fdiv_rn(e[0], s);
-  float pm = pr[0]; int am = 0;
-#pragma unroll
-  for (int c = 1; c < NCLS; ++c) { pr[c] = __fdiv_rn(e[c], s); if (pr[c] > pm) { pm = pr[c]; am = c; } }
-  if (p.cls) p.cls[n * vox + v] = (unsigned char)am;
-  if (p.probs) {
-#pragma unroll
-    for (int c = 0; c < NCLS; ++c) {
-      float* o = p.probs + obase + c * p.oC;
-      float r = p.accumulate ? __fadd_rn(*o, pr[c]) : pr[c];
-      if (p.divisor != 1.0f) r = __fdiv_rn(r, p.divisor);
-      *o = r;
-    }
-  }
+  head_store<NCLS, true>(p.o, l, n, vox, v, gz, gy, gx);
 }
 
 bool pow2(float v) { int e; return v > 0.f && frexpf(v, &e) == 0.5f; }
@@ -709,9 +671,9 @@ int iunet_x2_head_fwd(const void* x, long long x_ss, int x_lo, int C0, const voi
   IUNET_REQUIRE(pow2(act_scale), "x2_head: the activation scale must be a power of two (got %g)", act_scale);
   X2HeadParams p;
   p.x = x; p.x_sstride = x_ss; p.planes = C0 / 8; p.x_lo = x_lo; p.w = (const float*)w; p.bias = (const float*)bias;
-  p.inv_act = 1.0f / act_scale; p.logits = (float*)logits; p.probs = (float*)probs; p.cls = (unsigned char*)cls;
-  p.oN = out_strides[0]; p.oC = out_strides[1]; p.oD = out_strides[2]; p.oH = out_strides[3]; p.oW = out_strides[4];
-  p.divisor = divisor; p.accumulate = accumulate; p.N = N; p.D = D; p.H = H; p.W = W;
+  p.inv_act = 1.0f / act_scale;
+  if (const int rc = head_out_fill(p.o, "x2_head", logits, probs, cls, out_strides, divisor, accumulate)) return rc;
+  p.N = N; p.D = D; p.H = H; p.W = W;
   const long long vox = (long long)D * H * W;
   dim3 grid((unsigned)((vox + 255) / 256), N);
 #define X2_HEAD(NC) case NC: hipLaunchKernelGGL((x2_head_kernel<NC>), grid, dim3(256), 0, (hipStream_t)stream, p); break;

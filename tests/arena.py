@@ -185,3 +185,21 @@ class StridedOutput:
         bad = (bits(self.buf.cpu()) != self.before) & ~self.inside
         if bool(bad.any()):
             raise AssertionError(f'{self.name}: {int(bad.sum())} sentinel elements of a strided output overwritten, first at allocation offset {int(bad.nonzero()[0])}')
+
+
+# ---- the eval-mode BatchNorm fold every pack / prep kernel promises (csrc/common.h: bn_fold_scale / bn_fold_mul / bn_fold_bias), shared by
+# the read-back tests of the fp32 form and of the other pack entry points
+def sqrt_rn(t):
+    """The correctly rounded fp32 square root (the device's __fsqrt_rn): the float64 root rounded once more, which is innocuous for a
+    square root (53 >= 2 x 24 + 2 bits).  torch.sqrt on fp32 CPU tensors is NOT always correctly rounded (its vectorised path is one
+    unit off for ~0.7 % of random arguments; tests/test_f32_matrix_cpu.py holds this function to numpy's fp32 root instead)."""
+    return torch.sqrt(t.double()).float()
+
+
+def fold_ref(w, bn, eps, transposed):
+    """The eval-mode BatchNorm fold in separately, correctly rounded fp32 operations: a = gamma / sqrt(var + eps), w' = w a, bias = beta - mean a."""
+    gamma, beta, mean, var = [t.float() for t in bn]
+    a = gamma / sqrt_rn(var + torch.tensor(eps, dtype=torch.float32))
+    shape = [1] * w.dim()
+    shape[1 if transposed else 0] = -1
+    return w * a.view(shape), beta - mean * a

@@ -30,7 +30,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import metrics_ref
-from tests.arena import SENTINEL, Operand, StridedInput, StridedOutput, bits, scratch as _scratch
+from tests.arena import SENTINEL, Operand, StridedInput, StridedOutput, bits, fold_ref, scratch as _scratch, sqrt_rn
 
 pytestmark = pytest.mark.gpu
 
@@ -197,22 +197,6 @@ def conv_call(nv, nd, x_t, strides, code, yo, wpk, bias_t, N, grid, cin, cout, r
     D, H, W = dhw(nd, grid)
     nv.call('iunet_f32_conv_fwd', nd, nv.ptr(x_t), code, nv.ll_array(strides), nv.ptr(yo.t), yo.ss, nv.ptr(wpk.t),
             None if bias_t is None else nv.ptr(bias_t), N, D, H, W, cin, cout, int(relu), mode, nv.stream())
-
-
-def sqrt_rn(t):
-    """The correctly rounded fp32 square root (the device's __fsqrt_rn): the float64 root rounded once more, which is innocuous for a
-    square root (53 >= 2 x 24 + 2 bits).  torch.sqrt on fp32 CPU tensors is NOT always correctly rounded (its vectorised path is one
-    unit off for ~0.7 % of random arguments; tests/test_f32_matrix_cpu.py holds this function to numpy's fp32 root instead)."""
-    return torch.sqrt(t.double()).float()
-
-
-def fold_ref(w, bn, eps, transposed):
-    """The eval-mode BatchNorm fold in separately, correctly rounded fp32 operations: a = gamma / sqrt(var + eps), w' = w a, bias = beta - mean a."""
-    gamma, beta, mean, var = [t.float() for t in bn]
-    a = gamma / sqrt_rn(var + torch.tensor(eps, dtype=F32))
-    shape = [1] * w.dim()
-    shape[1 if transposed else 0] = -1
-    return w * a.view(shape), beta - mean * a
 
 
 # ---------------------------------------------------------------------------------------------------------------- conv, mode 0
