@@ -203,3 +203,125 @@ def fold_ref(w, bn, eps, transposed):
     shape = [1] * w.dim()
     shape[1 if transposed else 0] = -1
     return w * a.view(shape), beta - mean * a
+
+
+# ---- the split forms of the prediction kernels (csrc/split16.hip, conv3_x2m.hip): channel-blocked planes inside a sentinel-filled allocation
+SPLIT_PLACEMENTS = ('tight', 'gap', 'skip', 'up')
+
+
+def blocked(x, cpp):
+    """[N, C, ...] -> the channel-blocked planes [N][C / cpp][vox][cpp], flat per sample."""
+    N, C = x.shape[:2]
+    return x.reshape(N, C // cpp, cpp, -1).permute(0, 1, 3, 2).contiguous().reshape(N, -1)
+
+
+def unblocked(flat, C, sp, cpp):
+    """The inverse of blocked(): [N, C / cpp * vox * cpp] -> [N, C, *sp]."""
+    N = flat.shape[0]
+    return flat.reshape(N, C // cpp, -1, cpp).permute(0, 1, 3, 2).reshape((N, C) + tuple(sp))
+
+
+class PlaneOperand:
+    """N samples of `total` planes of [vox][cpp] elements each, `ss` elements apart, of which the operand owns the planes [p0, p0 + C / cpp)
+    -- and, with lo >= 0, the planes [p0 + lo, p0 + lo + C / cpp) -- everything else, the bands at both ends included, holds the sentinel.
+    Placements (`planes` = C / cpp; `pad` = 8 elements of a 16-bit type, 16 bytes: strides keep the 16-byte alignment the layout guarantees):
+      tight  [own | lo] (or [own] alone), ss = total planes;          gap   the same, ss + 37 pad, 5 pad into the allocation;
+      skip   the lower half of a concat buffer of 2 C channels, [skip | up | skip_lo | up_lo] (without lo planes: [skip | up]);
+      up     its upper half: p0 = planes.
+    `lo_at` overrides the distance of the lo planes at tight / gap (the hole in between holds the sentinel).  `t` is the device view that
+    starts at plane p0 of sample 0: pass its pointer, `ss` and `lo`.  first / second: CPU tensors [N, C, ...] (an input) or None."""
+
+    def __init__(self, N, C, vox, dtype, cpp, place, first=None, second=None, own_lo=True, lo_at=None, pair=True, device='cuda', name='operand',
+                 band=BAND):
+        planes, plane = C // cpp, vox * cpp
+        pad = 8 if dtype != torch.uint8 else 16
+        assert C % cpp == 0 and place in SPLIT_PLACEMENTS and (second is None or own_lo)
+        if place in ('tight', 'gap'):
+            p0, lo = 0, (lo_at or planes) if own_lo else -1
+            total = lo + planes if own_lo else planes
+        else:
+            p0, lo = (0 if place == 'skip' else planes), (2 * planes if own_lo else -1)
+            total = 4 * planes if pair else 2 * planes
+        self.N, self.C, self.vox, self.dtype, self.cpp, self.place, self.name, self.band = N, C, vox, dtype, cpp, place, name, band
+        self.planes, self.plane, self.p0, self.lo, self.total_planes = planes, plane, p0, lo, total
+        self.ss = total * plane + (37 * pad if place == 'gap' else 0)
+        self.lead = 5 * pad if place == 'gap' else 0
+        self.per = planes * plane
+        self.total = band + N * self.ss + band
+        host = sentinel_filled(self.total, dtype)
+        self.inside = torch.zeros(self.total, dtype=torch.bool)
+        for k, data in enumerate((first, second) if own_lo else (first,)):
+            rows = blocked(data, cpp).to(dtype) if data is not None else None
+            for n in range(N):
+                a = self.start(n, k)
+                self.inside[a:a + self.per] = True
+                if rows is not None:
+                    host[a:a + self.per] = rows[n]
+        self.is_input = first is not None
+        self.before = bits(host).clone()
+        self.buf = host.to(device)
+        self.t = self.buf[band + self.lead + p0 * plane:]
+
+    def start(self, n, second=0):
+        return self.band + self.lead + n * self.ss + (self.p0 + (self.lo if second else 0)) * self.plane
+
+    def host(self):
+        return self.buf.cpu()
+
+    def _read(self, second):
+        h = self.host()
+        return torch.stack([h[self.start(n, second):self.start(n, second) + self.per] for n in range(self.N)])
+
+    def check_outside(self):
+        now = bits(self.host())
+        bad = (now != self.before) & ~self.inside
+        if bool(bad.any()):
+            i = int(bad.nonzero()[0])
+            n, r = divmod(i - self.band - self.lead, self.ss)
+            raise AssertionError(f'{self.name} [{self.place}]: {int(bad.sum())} sentinel elements overwritten, the first in plane {r // self.plane} '
+                                 f'(element {r % self.plane}) of sample slot {n}; the operand owns planes {self.p0}..{self.p0 + self.planes - 1}'
+                                 + (f' and {self.p0 + self.lo}..{self.p0 + self.lo + self.planes - 1}' if self.lo >= 0 else '') + f' of {self.total_planes}')
+
+    def check_unchanged(self):
+        now = bits(self.host())
+        bad = now != self.before
+        if bool(bad.any()):
+            raise AssertionError(f'{self.name} [{self.place}]: input modified ({int(bad.sum())} elements), first at allocation offset {int(bad.nonzero()[0])}')
+
+    def check(self):
+        if self.is_input:
+            self.check_unchanged()
+        else:
+            self.check_outside()
+
+
+class SplitOperand(PlaneOperand):
+    """A tensor of the fp16x2 form: C / 8 hi planes of [vox][8] fp16 and, with own_lo, its lo planes `lo` planes further on."""
+
+    def __init__(self, N, C, vox, place='tight', hi=None, lo=None, own_lo=True, lo_at=None, device='cuda', name='split'):
+        super().__init__(N, C, vox, torch.float16, 8, place, hi, lo, own_lo, lo_at, True, device, name)
+
+    def logical(self):
+        """(hi words, lo words or None), each [N, C / 8 * vox * 8] on the CPU."""
+        return self._read(0), (self._read(1) if self.lo >= 0 else None)
+
+    def values(self, sp):
+        """hi and lo words as fp32 [N, C, *sp] (lo: zeros where the operand owns none)."""
+        h, l = self.logical()
+        h = unblocked(h.float(), self.C, sp, 8)
+        return h, (unblocked(l.float(), self.C, sp, 8) if l is not None else torch.zeros_like(h))
+
+
+class M8Operand(PlaneOperand):
+    """The lo8 granule planes of a tensor of the x2m form: C / 16 planes of [vox][16] e4m3 bytes; skip / up: the halves of a concat buffer's
+    granule planes (the upper half starts C / 16 planes in)."""
+
+    def __init__(self, N, C, vox, place='tight', lo8=None, device='cuda', name='m8'):
+        super().__init__(N, C, vox, torch.uint8, 16, place, lo8, None, False, None, False, device, name)
+
+    def logical(self):
+        return self._read(0)
+
+    def codes(self, sp):
+        """The e4m3 bytes [N, C, *sp]."""
+        return unblocked(self.logical(), self.C, sp, 16)

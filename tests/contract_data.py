@@ -178,3 +178,202 @@ def lk_convT_ref(wf, nd):
             kidx = sum(k[a] * 4 ** a for a in range(nd))
             out[p, :, t * cin:(t + 1) * cin] = wf[:, :, kidx].t()
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- split-precision matrix
+# Data on which the prediction kernels (tests/test_gpu_x2_matrix.py) are EXACT, and the conditions that make them so, asserted here.
+import numpy as np
+import torch.nn.functional as F
+
+from oracle import unet_ref
+
+X2_ACT_IN, X2_ACT_OUT = 64.0, 16.0          # fp16x2 exact rows: the accumulator is divided by 4
+X2_EXACT_BOUND = float(1 << 17)
+X2M_EXACT_BOUND = float(1 << 18)
+
+
+def conv_nd(nd):
+    return F.conv2d if nd == 2 else F.conv3d
+
+
+def convT_nd(nd):
+    return F.conv_transpose2d if nd == 2 else F.conv_transpose3d
+
+
+def e4m3_round(v):
+    """The nearest e4m3 value (ties to even, saturating at +-448) by the project's CPU codec, as fp32."""
+    return torch.from_numpy(unet_ref.round_e4m3(np.clip(v.detach().numpy().astype(np.float32), -448.0, 448.0)))
+
+
+def e4m3_codes(v):
+    """The e4m3 byte of every value (rounded by the codec first: the cast itself is then exact)."""
+    return e4m3_round(v).to(torch.float8_e4m3fn).view(torch.uint8)
+
+
+def e4m3_values(codes):
+    return codes.contiguous().view(torch.float8_e4m3fn).float()
+
+
+def lo8_interval(lo_words):
+    """The interval rule for a lo8 byte beside NON-exact words (hi, lo): the residual the device rounded lies in the fp16 rounding
+    interval [l-, l+] of the lo word it stored, and e4m3 rounding is monotone, so e4m3(16 l-) <= byte <= e4m3(16 l+) as e4m3 VALUES.
+    lo_words: fp32 tensor of fp16 values -> (lowest, highest) admissible value."""
+    l = lo_words.numpy().astype(np.float16)
+    dn = (l.astype(np.float64) + np.nextafter(l, np.float16(-np.inf)).astype(np.float64)) / 2
+    up = (l.astype(np.float64) + np.nextafter(l, np.float16(np.inf)).astype(np.float64)) / 2
+    f = lambda a: e4m3_round(torch.from_numpy((16.0 * a).astype(np.float32)))          # (12 significant bits: exact in fp32)
+    return f(dn), f(up)
+
+
+def lo8_in_interval(codes, lo_words):
+    """[bool]: every byte obeys the interval rule; the count of bytes that do not."""
+    lo, hi = lo8_interval(lo_words)
+    v = e4m3_values(codes)
+    bad = ~((v >= lo) & (v <= hi))          # (a NaN code fails; -0 == +0 as values)
+    return int(bad.sum())
+
+
+def pool_key(hi_words, lo8_codes):
+    """common.h's x2m_pool_keys on the CPU: the 24-bit key [sortable hi word | sortable lo8 byte] (sign-magnitude -> offset binary) as int64.
+    hi_words: fp16 tensor, lo8_codes: uint8 tensor of the same shape."""
+    h = hi_words.contiguous().view(torch.int16).to(torch.int64) & 0xFFFF
+    b = lo8_codes.to(torch.int64)
+    hs = torch.where(h >= 0x8000, h ^ 0xFFFF, h ^ 0x8000)
+    bs = torch.where(b >= 0x80, b ^ 0xFF, b ^ 0x80)
+    return (hs << 8) | bs
+
+
+def pool_unkey(key):
+    hs, bs = key >> 8, key & 0xFF
+    h = torch.where(hs >= 0x8000, hs ^ 0x8000, hs ^ 0xFFFF)
+    b = torch.where(bs >= 0x80, bs ^ 0x80, bs ^ 0xFF)
+    h = torch.where(h >= 0x8000, h - 0x10000, h).to(torch.int16).view(torch.float16)
+    return h, b.to(torch.uint8)
+
+
+def windows(t, nd):
+    """[N, C, (D,) H, W] -> [N, C, (D/2,) H/2, W/2, 2^nd]: the candidates of every 2^nd pool window."""
+    if nd == 2:
+        N, C, H, W = t.shape
+        return t.reshape(N, C, H // 2, 2, W // 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(N, C, H // 2, W // 2, 4)
+    N, C, D, H, W = t.shape
+    return t.reshape(N, C, D // 2, 2, H // 2, 2, W // 2, 2).permute(0, 1, 2, 4, 6, 3, 5, 7).reshape(N, C, D // 2, H // 2, W // 2, 8)
+
+
+def pool_by_key(hi_words, lo8_codes, nd):
+    """The pooled (hi words, lo8 bytes): per window the pair with the largest key."""
+    return pool_unkey(windows(pool_key(hi_words, lo8_codes), nd).max(-1).values)
+
+
+POOL_HI = torch.tensor([0.0, -0.0, 1.0, -1.0, 2.0, -2.0, 0.5, 3.0], dtype=torch.float16)          # both zero signs, negative values
+
+
+@functools.lru_cache(maxsize=None)
+def pool_tie_data(N, C, sp, seed):
+    """hi words from POOL_HI, a second word in -2..2 (lo words as they are; lo8 bytes as e4m3 codes of them): windows whose maximum hi is
+    shared while the second word decides (>= 5 %), windows whose whole best pair ties (>= 1 %).  -> hi fp16 [N, C, *sp], second fp32."""
+    g, nd = gen(seed), len(sp)
+    hi = POOL_HI[torch.randint(0, len(POOL_HI), (N, C) + tuple(sp), generator=g)]
+    lo = torch.randint(-2, 3, (N, C) + tuple(sp), generator=g).float()
+    hw, lw = windows(hi.float(), nd), windows(lo, nd)
+    top = hw == hw.max(-1, keepdim=True).values
+    shared = top.sum(-1) > 1
+    best_lo = torch.where(top, lw, torch.full_like(lw, -9.0)).max(-1, keepdim=True).values
+    whole = (top & (lw == best_lo)).sum(-1) > 1
+    decides = shared & (torch.where(top, lw, torch.full_like(lw, 9.0)).min(-1).values < best_lo.squeeze(-1))
+    assert decides.float().mean().item() >= 0.05, f'the second word decides only {100 * decides.float().mean().item():.1f} % of the windows'
+    assert whole.float().mean().item() >= 0.01, f'only {100 * whole.float().mean().item():.2f} % of the windows tie in the whole pair'
+    assert bool((hi.view(torch.int16) == -32768).any()) and bool((hi.float() < 0).any())
+    return hi, lo
+
+
+@functools.lru_cache(maxsize=None)
+def x2m_exact_operator(nd, co, ci, seed):
+    """Entries 16 a + b / 256: |a| in {36, 40, .., 60} (w_hi = 16 a exactly: |b| / 256 stays under half an fp16 ulp of it; a is an e4m3 value =
+    w_hi8), b in 16 x {-3 .. 3} (= w_lo8).  -> a, b, w"""
+    g = gen(seed)
+    shape = (co, ci) + (3,) * nd
+    a = (torch.randint(9, 16, shape, generator=g) * 4).float() * (torch.randint(0, 2, shape, generator=g) * 2 - 1).float()
+    b = (torch.randint(-3, 4, shape, generator=g) * 16).float()
+    w = 16.0 * a + b / 256.0
+    assert torch.equal(w.double(), 16.0 * a.double() + b.double() / 256.0) and torch.equal((16.0 * a).half().float(), 16.0 * a)
+    assert torch.equal(w.half().float(), 16.0 * a) and torch.equal(e4m3_round(a), a) and torch.equal(e4m3_round(b), b)
+    m = w.abs().reshape(co, -1).max(1).values
+    assert bool(((m >= 512) & (m < 1024)).all())          # the row scale is 1
+    return a, b, w
+
+
+@functools.lru_cache(maxsize=None)
+def x2m_exact_input(N, ci, sp, seed):
+    """hi planes sparse -1 / 0 / 1 (hi8 = hi / 256 exactly, a subnormal of e4m3), hand-made lo8 planes in -4..4."""
+    g = gen(seed)
+    X = (torch.randint(-1, 2, (N, ci) + tuple(sp), generator=g) * (torch.rand((N, ci) + tuple(sp), generator=g) < 0.25)).float()
+    L8 = torch.randint(-4, 5, (N, ci) + tuple(sp), generator=g).float()
+    assert torch.equal(e4m3_round(X / 256.0), X / 256.0) and torch.equal(e4m3_round(L8), L8)
+    return X, L8
+
+
+def x2m_exact_ref(nd, X, L8, a, b):
+    """float64 x_hi w_hi + x_lo8 w_hi8 + x_hi8 w_lo8 (the accumulator: 64 x the value stored at act_out = 1), one conv over [X | L8]."""
+    want = conv_nd(nd)(torch.cat([X, L8], 1).double(), torch.cat([16.0 * a + b / 256.0, a], 1).double(), padding=1)
+    assert float(want.abs().max()) < X2M_EXACT_BOUND          # + 4 fraction bits = 22: hi + lo hold acc / 64 exactly
+    return want
+
+
+@functools.lru_cache(maxsize=None)
+def split_exact_operator(shape, co_axis, seed):
+    """A sparse operator whose nonzero entries are h + r: |h| a multiple of 1/2 in [512, 1024) (an fp16 value at spacing 1/2, so w_hi = h and
+    the row scale is 1), r in {0, +-1/16, +-2/16, +-3/16} (under half that spacing: w_lo = r exactly).  About 120 nonzero entries per
+    output channel whatever the shape.  (|h| starts at 512.5: 512 - 3/16 would fall into the binade below, spacing 1/4.)  -> h, r (fp32, the operator is h + r)"""
+    g = gen(seed)
+    per_row = int(np.prod(shape)) // shape[co_axis]
+    keep = torch.rand(shape, generator=g) < min(0.5, 120.0 / per_row)
+    h = (torch.randint(1025, 2048, shape, generator=g).float() / 2) * (torch.randint(0, 2, shape, generator=g) * 2 - 1).float() * keep
+    r = torch.randint(-3, 4, shape, generator=g).float() / 16 * keep
+    w = h + r
+    assert torch.equal(w.double(), h.double() + r.double()) and torch.equal(w.half().float(), h) and torch.equal((w - h).half().float(), r)
+    m = w.abs().transpose(0, co_axis).reshape(shape[co_axis], -1).max(1).values
+    assert bool(((m >= 512) & (m < 1024)).all())          # every output channel has an entry: its row scale is 1
+    assert float((r[keep] != 0).float().mean()) >= 0.25
+    return h, r
+
+
+@functools.lru_cache(maxsize=None)
+def split_exact_input(N, ci, sp, seed):
+    """Hand-made planes (a non-canonical split: the kernels only consume words): x_hi sparse integers in -1..1, x_lo multiples of 1/8 in
+    [-3/8, 3/8], drawn independently of x_hi and nonzero on about half of the elements."""
+    g = gen(seed)
+    shape = (N, ci) + tuple(sp)
+    xh = (torch.randint(-1, 2, shape, generator=g) * (torch.rand(shape, generator=g) < 0.25)).float()
+    xl = torch.randint(-3, 4, shape, generator=g).float() / 8 * (torch.rand(shape, generator=g) < 0.5)
+    assert float((xl != 0).float().mean()) > 0.3 and float(((xl != 0) & (xh == 0)).float().mean()) > 0.2
+    return xh, xl
+
+
+def split_exact_ref(nd, xh, xl, h, r, transposed):
+    """float64 op(x_hi, w_hi) + op(x_lo, w_hi) + op(x_hi, w_lo) -- the kernels drop the fourth term by design -- as two operations:
+    op(x_hi, w_hi + w_lo) + op(x_lo, w_hi).  Every term is a multiple of 1/16 and the sum of the absolute terms stays below 2^17 everywhere,
+    so every partial sum in any order is exact in fp32 (21 bits)."""
+    op = (lambda x, w: convT_nd(nd)(x, w, stride=2)) if transposed else (lambda x, w: conv_nd(nd)(x, w, padding=1))
+    want = op(xh.double(), (h + r).double()) + op(xl.double(), h.double())
+    mag = op(xh.abs().double(), (h.abs() + r.abs()).double()) + op(xl.abs().double(), h.abs().double())
+    assert float(mag.max()) < X2_EXACT_BOUND, f'sum of absolute terms {float(mag.max()):.0f}'
+    assert torch.equal(want * 16, (want * 16).round())
+    return want
+
+
+def split_store(acc, bias):
+    """What an exact row stores, before any ReLU: v = acc x act_out / act_in + act_out x bias (integer biases; the row scale is 1) -- a
+    multiple of 1/64 below 2^15 + 64, at most 22 significant bits.  -> v (float64)"""
+    shape = [1, -1] + [1] * (acc.dim() - 2)
+    v = acc * (X2_ACT_OUT / X2_ACT_IN) + X2_ACT_OUT * bias.double().view(shape)
+    return v
+
+
+def split_words_of(v):
+    """float64 values (exact in fp32) -> hi = f16(v), lo = f16(v - hi), asserted to return v exactly."""
+    assert float(v.abs().max()) < 65504 and torch.equal(v.float().double(), v)
+    hi = v.float().half().float()
+    lo = (v.float() - hi).half().float()
+    assert torch.equal(hi.double() + lo.double(), v)
+    return hi, lo
