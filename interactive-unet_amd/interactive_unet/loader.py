@@ -8,6 +8,12 @@ with num_workers=0 (loader.py:95-99).
 
 File reading (TIFF / PNG through PIL) and `colored_to_categorical` are caller-side format code; `annotations_from_arrays`
 takes arrays directly.  `reslice=True` (load_resliced_annotations, dead code in the reference: trainer.py:18) is not provided.
+
+The 3-D producer is the 3-D form of VolumeData.sample + load_resliced_annotations (volumedata.py:68-80,
+loader.py:48-82) for the dim = 3 network: `load_volume_annotations` / `volume_annotations_from_arrays` keep the image, mask and
+weight VOLUMES as uint8 on the GPU, `VolumeDataset` draws random oblique patches around annotated voxels (`patch_candidates`,
+`draw_patch_params`) and every batch -- image at spline order 1, mask and weight at order 0, one-hot, dark rule, fp16 -- is ONE
+gather launch (libiunet: iunet_patch_batch).  `get_volume_loader` wraps it in the same `DeviceLoader`.
 """
 import ctypes
 import glob
@@ -226,4 +232,202 @@ def get_data_loader(set_type='train', num_classes=2, batch_size=2, reslice=False
     if annotations is None:
         annotations = load_annotations(set_type=set_type)
     dataset = UNetDataset(annotations, None, reslice=reslice, reslice_factor=reslice_factor, augment=augment, generator=generator)
+    return DeviceLoader(dataset, batch_size=batch_size, shuffle=shuffle, generator=generator)
+
+
+# ---- the 3-D producer: random oblique patches of annotation volumes ----------------------------------
+class PatchDesc(ctypes.Structure):
+    """Mirror of csrc/patch_batch.hip: PatchDesc."""
+    _fields_ = [('image', ctypes.c_void_p), ('mask', ctypes.c_void_p), ('weight', ctypes.c_void_p), ('wstride', ctypes.c_int),
+                ('Z', ctypes.c_int), ('Y', ctypes.c_int), ('X', ctypes.c_int), ('m', ctypes.c_float * 9), ('c', ctypes.c_float * 3),
+                ('keep_dark', ctypes.c_int)]
+
+
+def volume_annotations_from_arrays(volumes, device='cuda'):
+    """volumes: iterable of (image uint8 [Z, Y, X] or [Z, Y, X, ch], mask uint8 [Z, Y, X] class ids, weight uint8 [Z, Y, X] or
+    [Z, Y, X, 2]: what VolumeData.build_annotation_volumes / Slicer.update_volume produce).  Returns the list VolumeDataset works
+    on: uint8 tensors resident on `device`, the image as [Z, Y, X, ch]."""
+    out = []
+    for image, mask, weight in volumes:
+        t = [a.to(device=device, dtype=torch.uint8).contiguous() if torch.is_tensor(a)
+             else torch.from_numpy(np.array(a, dtype=np.uint8, order='C')).to(device) for a in (image, mask, weight)]
+        if t[0].dim() == 3:
+            t[0] = t[0][..., None]
+        _check_volume(*t)
+        out.append(t)
+    return out
+
+
+def _check_volume(image, mask, weight):
+    ok = image.dim() == 4 and 1 <= image.shape[3] <= 4 and mask.shape == image.shape[:3] and weight.shape[:3] == image.shape[:3] \
+        and (weight.dim() == 3 or (weight.dim() == 4 and weight.shape[3] == 2))
+    if not ok or any(t.dtype != torch.uint8 or not t.is_contiguous() for t in (image, mask, weight)):
+        raise ValueError(f'annotation volumes: image {tuple(image.shape)} (uint8 [Z, Y, X, 1..4]), mask {tuple(mask.shape)} ([Z, Y, X]), '
+                         f'weight {tuple(weight.shape)} ([Z, Y, X] or [Z, Y, X, 2]) must be contiguous uint8 over one grid')
+
+
+def load_volume_annotations(device='cuda'):
+    """What VolumeData(f, annotations=True) reads (volumedata.py:24-30), for every data/image_volumes/<name>.zarr in sorted
+    order: level '0' of the image, data/mask_volumes/<name>.npy, data/weight_volumes/<name>.npy."""
+    from . import multiscale
+    volumes = []
+    for f in sorted(glob.glob(os.path.join('data', 'image_volumes', '*.zarr'))):
+        name = os.path.splitext(os.path.basename(f))[0]
+        image = multiscale.read_volume(f, 0).to_device(device)
+        volumes.append((image, np.load(os.path.join('data', 'mask_volumes', f'{name}.npy')),
+                        np.load(os.path.join('data', 'weight_volumes', f'{name}.npy'))))
+    return volume_annotations_from_arrays(volumes, device)
+
+
+def patch_candidates(mask, weight):
+    """Slicer.get_origin_candidates (slicer.py:67-72) over the ANNOTATED voxels (weight > 0) of a class-id volume: per class
+    present there its voxel indices (int64 [n, 3] tensors, row-major order) and the class probabilities max(count) / count,
+    normalised.  Torch ops on the tensors' device, once per volume."""
+    annotated = weight > 0
+    classes = torch.unique(mask[annotated])
+    candidates = [torch.nonzero((mask == c) & annotated) for c in classes]
+    counts = torch.tensor([c.shape[0] for c in candidates], dtype=torch.float64)
+    if len(candidates) == 0:
+        return candidates, counts
+    weights = counts.max() / counts
+    return candidates, weights / weights.sum()
+
+
+def _random_rotation(gen):
+    """Rotation by a uniform angle about a uniformly random unit axis (normals, normalised: slicer.py:40-44), by Rodrigues' formula."""
+    while True:
+        k = torch.randn(3, generator=gen, dtype=torch.float64).numpy()
+        if np.linalg.norm(k) >= 0.0001:
+            break
+    k = k / np.linalg.norm(k)
+    angle = _uniform(0.0, 2.0 * math.pi, gen)
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + math.sin(angle) * K + (1.0 - math.cos(angle)) * (K @ K)
+
+
+def draw_patch_params(shape, patch, candidates, gen=None, sampling_mode='random', scale=(0.5, 1.0), augment=True):
+    """One sample's (m[9], c[3]) of iunet_patch_batch for a volume of `shape` and a patch (SZ, SY, SX): patch voxel t (centred
+    coordinates) reads source coordinate m t + c.  'random': a random rotation times an isotropic scale from `scale` (source
+    voxels per output voxel) times three independent flips; 'grid' (the app's "Axially-aligned" mode): a uniformly chosen signed
+    permutation, scale 1; augment=False: the identity.  The centre puts a drawn candidate voxel (class by `candidates`'
+    probabilities, then uniform among its voxels, as Slicer.randomize) exactly on a uniformly drawn voxel of the patch, so the
+    patch holds an annotation without the reference's draw-again loop (loader.py:62-68).  In the two axis-aligned forms every
+    source coordinate is then an integer (even patch sizes) and the patch is moved inside the volume where it fits."""
+    cands, probs = candidates
+    if len(cands) == 0:
+        raise ValueError('no annotated voxel (weight > 0) to centre a patch on')
+    aligned = not augment or sampling_mode == 'grid'
+    if not augment:
+        M = np.eye(3)
+    elif sampling_mode == 'grid':
+        perm = torch.randperm(3, generator=gen).tolist()
+        sign = torch.randint(0, 2, (3,), generator=gen).tolist()
+        M = np.zeros((3, 3))
+        for a in range(3):
+            M[a, perm[a]] = 1.0 - 2.0 * sign[a]
+    elif sampling_mode == 'random':
+        R = _random_rotation(gen)
+        s = _uniform(scale[0], scale[1], gen)
+        flips = 1.0 - 2.0 * torch.randint(0, 2, (3,), generator=gen).double().numpy()
+        M = s * R * flips[None, :]
+    else:
+        raise ValueError('sampling_mode must be either "random" or "grid".')
+    cum = np.cumsum(np.asarray(probs, dtype=np.float64))
+    k = min(int(np.searchsorted(cum, torch.rand(1, generator=gen, dtype=torch.float64).item(), side='right')), len(cands) - 1)
+    voxel = np.array(cands[k][torch.randint(0, int(cands[k].shape[0]), (1,), generator=gen).item()].tolist(), dtype=np.float64)
+    half = (np.array(patch, dtype=np.float64) - 1.0) / 2.0
+    t = np.array([torch.randint(0, int(S), (1,), generator=gen).item() for S in patch], dtype=np.float64) - half
+    c = voxel - M @ t
+    if aligned:                                       # source box of axis a: c[a] -+ half[j] of the patch axis j it runs along
+        for a in range(3):
+            h, n = half[int(np.argmax(np.abs(M[a])))], int(shape[a])
+            if 2 * h + 1 <= n:
+                c[a] = min(max(c[a], h), n - 1 - h)
+    return [float(v) for v in M.reshape(-1)], [float(v) for v in c]
+
+
+class VolumeDataset:
+    """`count` random patches per epoch of the volumes of load_volume_annotations / volume_annotations_from_arrays (the 3-D form
+    of load_resliced_annotations, loader.py:48-82: a uniformly drawn volume per sample, VolumeData.sample's orders -- image
+    `order`, mask and weight 0).  augment=True: new patches at every call; augment=False: `count` axis-aligned patches drawn once
+    here from `generator`, the same every epoch."""
+
+    def __init__(self, volumes, num_classes, patch_size=64, count=100, weight_channel=0, augment=True, sampling_mode='random', order=1,
+                 generator=None, keep_dark=False):
+        self.volumes = [tuple(v) for v in volumes]
+        if not self.volumes:
+            raise ValueError('no annotation volumes')
+        for v in self.volumes:
+            _check_volume(*v)
+        if len({int(v[0].shape[3]) for v in self.volumes}) != 1:
+            raise ValueError('annotation volumes differ in their number of image channels')
+        self.patch = (int(patch_size),) * 3 if isinstance(patch_size, int) else tuple(int(s) for s in patch_size)
+        if len(self.patch) != 3 or min(self.patch) < 1 or (sampling_mode == 'grid' or not augment) and any(s % 2 for s in self.patch):
+            raise ValueError(f'patch_size {patch_size}: an int or (SZ, SY, SX), even for the axis-aligned forms')
+        if order not in (0, 1) or sampling_mode not in ('random', 'grid'):
+            raise ValueError(f'order {order} (0 or 1), sampling_mode {sampling_mode!r} ("random" or "grid")')
+        self.num_classes, self.count, self.weight_channel = int(num_classes), int(count), int(weight_channel)
+        self.augment, self.sampling_mode, self.order, self.generator, self.keep_dark = augment, sampling_mode, int(order), generator, bool(keep_dark)
+        self.candidates = []                    # per volume, on the host: drawing from them costs no device round trip
+        for image, mask, weight in self.volumes:
+            cands, probs = patch_candidates(mask, self._weight(weight))
+            self.candidates.append(([c.cpu() for c in cands], probs))
+        self._lut = None
+        self._fixed = None if augment else [self.draw() for _ in range(self.count)]
+
+    def _weight(self, weight):
+        return weight if weight.dim() == 3 else weight[..., self.weight_channel]
+
+    def __len__(self):
+        return self.count
+
+    def draw(self):
+        """(volume index, m, c) of one sample, from the generator."""
+        vi = torch.randint(0, len(self.volumes), (1,), generator=self.generator).item()
+        m, c = draw_patch_params(tuple(self.volumes[vi][1].shape), self.patch, self.candidates[vi], self.generator,
+                                 sampling_mode=self.sampling_mode, augment=self.augment)
+        return vi, m, c
+
+    def descriptors(self, params):
+        descs = (PatchDesc * len(params))()
+        for d, (vi, m, c) in zip(descs, params):
+            image, mask, weight = self.volumes[vi]
+            d.image, d.mask = image.data_ptr(), mask.data_ptr()
+            d.weight, d.wstride = (weight.data_ptr(), 1) if weight.dim() == 3 else (weight.data_ptr() + self.weight_channel, int(weight.shape[3]))
+            d.Z, d.Y, d.X = [int(s) for s in mask.shape]
+            d.keep_dark = int(self.keep_dark)
+            for q in range(9):
+                d.m[q] = m[q]
+            for q in range(3):
+                d.c[q] = c[q]
+        return descs
+
+    def batch(self, indices, params=None):
+        """(X [B, ch, SZ, SY, SX], y, w [B, C, SZ, SY, SX]) fp16 for len(indices) samples in one launch.  `params`: optional list of
+        (volume index, m[9], c[3]) per sample; else drawn from the generator (augment=True) or the fixed set's entries `indices`."""
+        if params is None:
+            params = [self.draw() for _ in indices] if self.augment else [self._fixed[i] for i in indices]
+        dev = self.volumes[0][0].device
+        assert nv.lib().iunet_patch_desc_bytes() == ctypes.sizeof(PatchDesc), 'PatchDesc layout mismatch with libiunet'
+        if self._lut is None:
+            self._lut = torch.from_numpy((np.arange(256) / 255).astype('float32')).to(torch.float16).to(dev)
+        raw = torch.frombuffer(bytearray(bytes(self.descriptors(params))), dtype=torch.uint8).to(dev)
+        B, ch, C = len(params), int(self.volumes[0][0].shape[3]), self.num_classes
+        X = torch.empty((B, ch) + self.patch, dtype=torch.float16, device=dev)
+        y = torch.empty((B, C) + self.patch, dtype=torch.float16, device=dev)
+        w = torch.empty((B, C) + self.patch, dtype=torch.float16, device=dev)
+        with torch.cuda.device(dev):
+            nv.call('iunet_patch_batch', nv.ptr(raw), B, ch, C, *self.patch, self.order, nv.ptr(self._lut), nv.ptr(X), nv.ptr(y), nv.ptr(w),
+                    nv.stream())
+        return X, y, w
+
+
+def get_volume_loader(set_type='train', num_classes=2, batch_size=2, patch_size=64, count=100, augment=True, shuffle=True, volumes=None,
+                      generator=None):
+    """The 3-D counterpart of get_data_loader: `count` patches per epoch from the annotation volumes (`volumes`: skip the file read
+    and use these).  set_type 'train' reads weight channel 0, anything else channel 1 (loader.py:56-59)."""
+    if volumes is None:
+        volumes = load_volume_annotations()
+    dataset = VolumeDataset(volumes, num_classes, patch_size=patch_size, count=count, weight_channel=0 if set_type == 'train' else 1,
+                            augment=augment, generator=generator)
     return DeviceLoader(dataset, batch_size=batch_size, shuffle=shuffle, generator=generator)

@@ -9,6 +9,7 @@ reads:
   utils.get_training_history: columns epoch, step, train/<M>, val/<M> for Loss, Dice, IoU, MCC)
 """
 import csv
+import inspect
 import os
 import time
 import warnings
@@ -30,6 +31,25 @@ def _loaders(num_classes, batch_size, reslice, reslice_factor):
     return tr, va
 
 
+def _volume_loaders(num_classes, batch_size, patch_size, patches_per_epoch):
+    from . import loader                           # the 3-D patch producer over the annotation volumes
+    volumes = loader.load_volume_annotations()
+    tr = loader.get_volume_loader('train', num_classes=num_classes, batch_size=batch_size, patch_size=patch_size,
+                                  count=patches_per_epoch, augment=True, shuffle=True, volumes=volumes)
+    va = loader.get_volume_loader('val', num_classes=num_classes, batch_size=batch_size, patch_size=patch_size,
+                                  count=patches_per_epoch, augment=False, shuffle=False, volumes=volumes)
+    return tr, va
+
+
+def _check_patch_size(patch_size, levels):
+    """A `levels`-level network halves the grid levels - 1 times: every extent of a training patch must be a multiple of 2**(levels-1)."""
+    sizes = (patch_size,) * 3 if isinstance(patch_size, int) else tuple(patch_size)
+    step = 2 ** (levels - 1)
+    if len(sizes) != 3 or any(int(s) < step or int(s) % step for s in sizes):
+        raise ValueError(f'patch_size {patch_size}: 2**(levels-1) = {step} must divide every extent of a 3-D training patch '
+                         f'(the {levels}-level network halves the grid {levels - 1} times)')
+
+
 def _mean(rows):
     """Epoch mean of the per-step [loss, dice, iou, mcc] device tensors: ONE device-to-host transfer per epoch (a `.tolist()` per
     step kept the host from running ahead of the device: every step then paid its ~130 launches' host time in full)."""
@@ -41,14 +61,19 @@ def _mean(rows):
 
 def train_model(lr=0.0001, batch_size=1, epochs=10, num_channels=1, num_classes=2, loss_function_name='MCC + CE',
                 architecture='U-Net', encoder_name='mit_b0', pretrained=True, reslice=False, reslice_factor=2,
-                train_loader=None, val_loader=None, dim=2, act_dtype=None, process_group=None):
-    if train_loader is None or val_loader is None:
+                train_loader=None, val_loader=None, dim=2, act_dtype=None, process_group=None, patch_size=64, patches_per_epoch=100):
+    """dim=3 without loaders: `patches_per_epoch` patches of `patch_size` (an int or (SZ, SY, SX)) per epoch from the annotation
+    volumes under data/ (loader.get_volume_loader): augmented for training, a fixed axis-aligned set for validation."""
+    model_path = os.path.join('model', 'model.ckpt')
+    volumes = dim == 3 and (train_loader is None or val_loader is None)
+    if volumes and not os.path.isfile(model_path):  # a new model has the default depth: refused before anything touches the GPU
+        _check_patch_size(patch_size, inspect.signature(unet.UNet.__init__).parameters['levels'].default)
+    elif not volumes and (train_loader is None or val_loader is None):
         train_loader, val_loader = _loaders(num_classes, batch_size, reslice, reslice_factor)
     loss_function = metrics.loss_name_to_function(loss_function_name)
     device = torch.device('cuda', torch.cuda.current_device())
 
     # If model exists - continue training (trainer.py:30-39)
-    model_path = os.path.join('model', 'model.ckpt')
     if os.path.isfile(model_path):
         model = unet.UNet.load_from_checkpoint(checkpoint_path=model_path)
         model.lr = lr
@@ -59,6 +84,9 @@ def train_model(lr=0.0001, batch_size=1, epochs=10, num_channels=1, num_classes=
             model = unet.UNet(lr=lr, num_channels=num_channels, num_classes=num_classes, loss_function=loss_function,
                               architecture=architecture, encoder_name=encoder_name, pretrained=pretrained, dim=dim,
                               act_dtype=act_dtype)
+    if volumes:                                     # (a resumed model brings its own depth)
+        _check_patch_size(patch_size, model.levels)
+        train_loader, val_loader = _volume_loaders(num_classes, batch_size, patch_size, patches_per_epoch)
     model = model.to(device)
     rank0 = process_group is None or torch.distributed.get_rank(process_group) == 0
     if process_group is not None:                   # every rank has read the checkpoint before rank 0 removes it
