@@ -17,19 +17,10 @@ import os
 import torch
 
 from . import _native as nv
+from . import topology
+from .topology import _vox, check_spatial          # (other modules import them from here)
 
 BN_EPS = 1e-5
-
-
-def _vox(dims):
-    return dims[0] * dims[1] * dims[2]
-
-
-def check_spatial(dim, levels, D, H, W):
-    """Every level halves the grid: H, W (and D in 3-D) must be divisible by 2^(levels-1), and D == 1 in 2-D."""
-    f = 2 ** (levels - 1)
-    if H % f or W % f or (dim == 3 and D % f) or (dim == 2 and D != 1):
-        raise ValueError(f'spatial size {(D, H, W)} must be divisible by {f} (and D == 1 in 2-D)')
 
 
 class F8Conv:
@@ -39,83 +30,65 @@ class F8Conv:
         self.bytes, self.scale = bytes_, scale
 
 
-class Engine:
-    def __init__(self, dim=2, levels=4, base=32, cin=1, ncls=2, act_dtype=torch.float16, device='cuda',
-                 weight_dtype=None, norm='batch', groups=8, act_quant=None):
-        if dim not in (2, 3):
-            raise ValueError('dim must be 2 or 3')
-        if base % 32 != 0:
-            raise NotImplementedError('native U-Net needs base channels to be a multiple of 32')
-        if not (1 <= cin <= 4):
-            raise NotImplementedError('native U-Net supports 1..4 input channels')
-        if not (2 <= ncls <= 10):
-            raise NotImplementedError('native U-Net supports 2..10 classes (app.py:162)')
+class ForwardEngine:
+    """What every forward engine is on the host side, whatever its numeric form or architecture: the network's shape (topology.py), the
+    source tensors of `load_eval`, the hand-off to the C-sequenced forward and the workspaces kept by batch shape.  A subclass adds its
+    operator formats (`load_eval`), its buffers (`_build_workspace(N, dims)` -> the workspace dict with its 'dims') and its launches
+    (`infer`); one with a handle mode also says which (`_graph_spec`)."""
+    workspaces_kept = 1        # batch shapes whose workspace stays allocated
+    limits_cin = True          # 1..4 input channels
+
+    def __init__(self, dim, levels, base, cin, ncls, device, norm='batch', groups=8):
+        topology.check_limits(dim, base, cin if self.limits_cin else None, ncls, norm, groups)
         self.dim, self.levels, self.base, self.cin, self.ncls = dim, levels, base, cin, ncls
-        self.act_dtype = act_dtype
-        if weight_dtype not in (None, 'fp8_e4m3'):
-            raise ValueError("weight_dtype must be None (= activation dtype) or 'fp8_e4m3'")
-        self.weight_dtype = weight_dtype      # 'fp8_e4m3': inference weights on the OCP e4m3 grid (config C5)
-        # act_quant (fp8 weights only).  True (default, "W8A8"): the stage convs run on the fp8 matrix cores -- gfx950 has no mixed
-        # fp8 x bf16 MFMA, so their 16-bit activations are ALSO rounded to unscaled e4m3 (3 mantissa bits, saturating at +-448) on
-        # the way into LDS; measured on C5: mean |dp| 1.5e-2 against fp32, class map equal on ~95 % (tests/test_gpu_f8.py).
-        # False ("W8A16", BASELINE C5's literal "fp8 weights / bf16 activations"): the operators are e4m3 VALUES times a per-channel
-        # power of two, stored in the activation dtype and multiplied on the 16-bit matrix cores with unquantised activations.
-        if act_quant is not None and not weight_dtype:
-            raise ValueError("act_quant selects between the two fp8-weight modes: give weight_dtype='fp8_e4m3'")
-        self.act_quant = bool(weight_dtype) if act_quant is None else bool(act_quant)
-        if norm not in ('batch', 'group'):
-            raise ValueError("norm must be 'batch' or 'group'")
-        if norm == 'group' and weight_dtype:
-            raise NotImplementedError('the fp8 operator format folds the norm into the weights: BatchNorm only')
-        if norm == 'group' and base % groups:
-            raise ValueError(f'{groups} groups do not divide {base} channels')
-        # 'group': GroupNorm(groups) + ReLU after every stage conv instead of (folded) BatchNorm -- per-sample statistics, so the
-        # convs write their raw output and a statistics + normalise pass follows (iunet_gn_relu_fwd)
         self.norm, self.groups = norm, groups
-        self.dt = nv.DTYPE_CODE[act_dtype]
         self.device = torch.device(device)
-        self.ch = [base * 2 ** l for l in range(levels)]
-        self.taps = 3 ** dim
-        self.npos = 2 ** dim
+        self.ch = topology.channels(base, levels)
+        self.taps, self.npos = 3 ** dim, 2 ** dim
         self.packed = None
-        self._ws_cache = {}
-        self._f8_ws = None
+        self._ws_cache, self._stage, self._eval_sig = {}, {}, None
         self.probe = None          # {'name': layer, 'events': []}: timing hook of one layer's launches (bench.py roofline)
         self.use_graph = True      # False: every forward sequenced from Python (tests compare the two)
         self._g, self._gparams, self._g_dirty, self._g_fwd = None, None, False, 0      # the C++-sequenced forward (_graph)
         nv.lib()   # fail loudly now if the HIP library is missing
 
+    # ------------------------------------------------------------------ the C++-sequenced forward
+    def _graph_spec(self):
+        """net_graph.NetGraph's arguments beyond the network's shape (mode, ...) where this engine's forward exists at the handle level, else
+        None."""
+        return None
+
     def _graph(self):
         """The C++-sequenced forward (net_graph.NetGraph) on this engine's current parameters, or None where the handle level does not
-        apply (GroupNorm, fp8 operators, IUNET_PY_GRAPH=1).  The handle packs its own copy of the operators (one copy of the parameters
-        + ~40 launches), so it is loaded at the SECOND forward on the same parameters: a training loop that predicts once per optimiser
-        step, or a validation pass that only asks for features, never pays for it; a slice / block / volume prediction does once."""
+        apply (_graph_spec: GroupNorm, fp8 operators; IUNET_PY_GRAPH=1; use_graph False).  The handle packs its own copy of the operators
+        (one copy of the parameters + ~40 launches), so it is loaded at the SECOND forward on the same parameters: a training loop that
+        predicts once per optimiser step, or a validation pass that only asks for features, never pays for it; a slice / block / volume
+        prediction does once."""
         from . import net_graph
         self._g_fwd += 1
-        if self._g_fwd < 2:
+        if self._g_fwd < 2 or not net_graph.ENABLED or not self.use_graph or self._gparams is None:
             return None
-        if not net_graph.ENABLED or not self.use_graph or self.norm != 'batch' or self.weight_dtype or not (2 <= self.levels <= 6) or self._gparams is None:
+        spec = self._graph_spec()
+        if spec is None:
             return None
         if self._g is None:
-            self._g = net_graph.NetGraph(self.dim, self.levels, self.base, self.cin, self.ncls, self.dt, self.device)
+            self._g = net_graph.NetGraph(self.dim, self.levels, self.base, self.cin, self.ncls, device=self.device, **spec)
         if self._g_dirty:
             self._g.set_params(self._gparams)
             self._g_dirty = False
             self._ws_cache.clear()         # the handle has its own workspace: the Python sequence's buffers go back to the allocator
         return self._g
 
+    def _new_params(self, params):
+        """load_eval: the handle, if any, takes these parameters at the second forward on them."""
+        self._gparams, self._g_dirty, self._g_fwd = params, True, 0
+
     # ------------------------------------------------------------------ weights
     def stage_names(self):
-        names = [f'enc{l}' for l in range(self.levels)] + [f'dec{l}' for l in range(self.levels - 2, -1, -1)]
-        return names
+        return topology.stage_names(self.levels)
 
     def stage_io(self, prefix):
-        l = int(prefix[3:])
-        if prefix.startswith('enc'):
-            ci = self.cin if l == 0 else self.ch[l - 1]
-        else:
-            ci = 2 * self.ch[l]
-        return ci, self.ch[l]
+        return topology.stage_io(prefix, self.cin, self.ch)[:2]
 
     def _source(self, params, name):
         """fp32 device tensor the pack kernel reads: the parameter itself when it already lives on the device
@@ -129,32 +102,82 @@ class Engine:
         st.copy_(t)
         return st
 
+    def _sources(self, params, names):
+        """({name: _source}, the signature of their addresses: the operators' descriptor tables are rebuilt when a source moves)."""
+        src = {n: self._source(params, n) for n in names}
+        return src, tuple(t.data_ptr() for t in src.values())
+
+    def _require_loaded(self):
+        if self.packed is None:
+            raise RuntimeError(f'{type(self).__name__}.load_eval() has not been called')
+
+    # ------------------------------------------------------------------ workspace
+    def level_dims(self, D, H, W):
+        return topology.level_dims(self.dim, self.levels, D, H, W)
+
+    def check_shape(self, D, H, W):
+        check_spatial(self.dim, self.levels, D, H, W)
+
+    def workspace(self, N, D, H, W):
+        key = (N, D, H, W)
+        ws = self._ws_cache.get(key)
+        if ws is None:
+            self.check_shape(D, H, W)
+            ws = self._build_workspace(N, self.level_dims(D, H, W))
+            if len(self._ws_cache) >= self.workspaces_kept:
+                self._ws_cache.clear()
+            self._ws_cache[key] = ws
+        return ws
+
+    def _out_strides(self, out_strides, D, H, W):
+        """The caller's output strides (n, c, d, h, w), by default contiguous NC(D)HW."""
+        v = D * H * W
+        return out_strides or (self.ncls * v, v, H * W, W, 1)
+
+
+class Engine(ForwardEngine):
+    workspaces_kept = 5        # (EngineX2 likewise; every other engine keeps one)
+
+    def __init__(self, dim=2, levels=4, base=32, cin=1, ncls=2, act_dtype=torch.float16, device='cuda',
+                 weight_dtype=None, norm='batch', groups=8, act_quant=None):
+        # norm='group': GroupNorm(groups) + ReLU after every stage conv instead of (folded) BatchNorm -- per-sample statistics, so the
+        # convs write their raw output and a statistics + normalise pass follows (iunet_gn_relu_fwd)
+        super().__init__(dim, levels, base, cin, ncls, device, norm, groups)
+        self.act_dtype = act_dtype
+        if weight_dtype not in (None, 'fp8_e4m3'):
+            raise ValueError("weight_dtype must be None (= activation dtype) or 'fp8_e4m3'")
+        self.weight_dtype = weight_dtype      # 'fp8_e4m3': inference weights on the OCP e4m3 grid (config C5)
+        # act_quant (fp8 weights only).  True (default, "W8A8"): the stage convs run on the fp8 matrix cores -- gfx950 has no mixed
+        # fp8 x bf16 MFMA, so their 16-bit activations are ALSO rounded to unscaled e4m3 (3 mantissa bits, saturating at +-448) on
+        # the way into LDS; measured on C5: mean |dp| 1.5e-2 against fp32, class map equal on ~95 % (tests/test_gpu_f8.py).
+        # False ("W8A16", BASELINE C5's literal "fp8 weights / bf16 activations"): the operators are e4m3 VALUES times a per-channel
+        # power of two, stored in the activation dtype and multiplied on the 16-bit matrix cores with unquantised activations.
+        if act_quant is not None and not weight_dtype:
+            raise ValueError("act_quant selects between the two fp8-weight modes: give weight_dtype='fp8_e4m3'")
+        self.act_quant = bool(weight_dtype) if act_quant is None else bool(act_quant)
+        if norm == 'group' and weight_dtype:
+            raise NotImplementedError('the fp8 operator format folds the norm into the weights: BatchNorm only')
+        self.dt = nv.DTYPE_CODE[act_dtype]
+        self._f8_ws = None
+
+    def _graph_spec(self):
+        if self.norm != 'batch' or self.weight_dtype or not (2 <= self.levels <= 6):
+            return None
+        return dict(mode=self.dt)
+
     def load_eval(self, params):
         """Fold eval-mode BatchNorm into the stage convs and pack everything into MFMA fragment order: ONE
         launch over a device-resident descriptor table (iunet_pack_batch), rebuilt only when a source tensor
         moves.  `params`: {name: fp32 tensor}."""
-        if not hasattr(self, '_stage'):
-            self._stage, self._eval_sig, self._eval_table = {}, None, None
-        self._gparams, self._g_dirty, self._g_fwd = params, True, 0
-        src = {}
-        for prefix in self.stage_names():
-            for j in (1, 2):
-                src[f'{prefix}.conv{j}.weight'] = self._source(params, f'{prefix}.conv{j}.weight')
-                for k in ('weight', 'bias', 'running_mean', 'running_var'):
-                    src[f'{prefix}.bn{j}.{k}'] = self._source(params, f'{prefix}.bn{j}.{k}')
-        for l in range(self.levels - 1):
-            src[f'dec{l}.up.weight'] = self._source(params, f'dec{l}.up.weight')
-            src[f'dec{l}.up.bias'] = self._source(params, f'dec{l}.up.bias')
-        src['head.weight'] = self._source(params, 'head.weight')
-        src['head.bias'] = self._source(params, 'head.bias')
-        sig = tuple(t.data_ptr() for t in src.values())
+        self._new_params(params)
+        src, sig = self._sources(params, topology.param_names(self.stage_names(), topology.up_convs(self.levels)))
         if sig != self._eval_sig:
             P, descs, keep_q = {}, [], []
             for prefix in self.stage_names():
                 ci, co = self.stage_io(prefix)
                 for j, (a, b) in enumerate(((ci, co), (co, co)), 1):
                     w = src[f'{prefix}.conv{j}.weight']
-                    bn = [src[f'{prefix}.bn{j}.{k}'] for k in ('weight', 'bias', 'running_mean', 'running_var')]
+                    bn = [src[f'{prefix}.bn{j}.{k}'] for k in topology.BN_KEYS]
                     if self.norm == 'group':                 # nothing folds: raw operator, gamma / beta go to the norm pass
                         if prefix == 'enc0' and j == 1:
                             dst = torch.empty(nv.lib().iunet_pack_first_conv_elems(b, a, self.taps), dtype=self.act_dtype,
@@ -207,53 +230,35 @@ class Engine:
                             and os.environ.get('IUNET_F8_Q', '1') != '0' and nv.lib().iunet_f8_pack_order(27, self.ch[0]) == 1)
         return self._qp
 
-    def level_dims(self, D, H, W):
-        out = []
+    def _build_workspace(self, N, dims):
+        mk = lambda c, v: torch.empty(N * c * v, dtype=self.act_dtype, device=self.device)
+        # fp8 network on the K = 128 path: every tensor that only fp8 convolutions read is stored as e4m3 planes (one byte per
+        # element: include/iunet.h, format 1); what a transposed conv or the head reads (b) stays 16-bit
+        mq = (lambda c, v: torch.empty(N * c * v, dtype=torch.uint8, device=self.device)) if self.q_planes() else mk
+        ws = {'dims': dims}
         for l in range(self.levels):
-            f = 2 ** l
-            out.append((D // f if self.dim == 3 else 1, H // f, W // f))
-        return out
-
-    def check_shape(self, D, H, W):
-        check_spatial(self.dim, self.levels, D, H, W)
-
-    def workspace(self, N, D, H, W):
-        key = (N, D, H, W)
-        ws = self._ws_cache.get(key)
-        if ws is None:
-            self.check_shape(D, H, W)
-            dims = self.level_dims(D, H, W)
-            mk = lambda c, v: torch.empty(N * c * v, dtype=self.act_dtype, device=self.device)
-            # fp8 network on the K = 128 path: every tensor that only fp8 convolutions read is stored as e4m3 planes (one byte per
-            # element: include/iunet.h, format 1); what a transposed conv or the head reads (b) stays 16-bit
-            mq = (lambda c, v: torch.empty(N * c * v, dtype=torch.uint8, device=self.device)) if self.q_planes() else mk
-            ws = {'dims': dims}
-            for l in range(self.levels):
-                v = _vox(dims[l])
-                ws[f'a{l}'] = mq(self.ch[l], v)
-                ws[f'b{l}'] = mk(self.ch[l], v)
-                if l < self.levels - 1:
-                    ws[f'cat{l}'] = mq(2 * self.ch[l], v)
-                if l > 0:
-                    ws[f'pin{l}'] = mq(self.ch[l - 1], v)
-            if self.norm == 'group':
-                f32 = lambda n: torch.empty(n, dtype=torch.float32, device=self.device)
-                ws['raw'] = mk(max(self.ch[l] * _vox(dims[l]) for l in range(self.levels)), 1)
-                # fused form (one sample at a time): raw outputs of a stage's two convs, the convs' statistics rows, two
-                # (scale, shift, mean, invstd) sets
-                one = max(self.ch[l] * _vox(dims[l]) for l in range(self.levels))
-                ws['rawA'] = torch.empty(one, dtype=self.act_dtype, device=self.device)
-                ws['rawB'] = torch.empty(one, dtype=self.act_dtype, device=self.device)
-                parts = max(max(nv.lib().iunet_conv3_num_tiles(self.dim, 1, *dims[l]),
-                                nv.lib().iunet_conv3_stats_parts(self.dim, 1, *dims[l], self.ch[l], 2)) * self.ch[l] for l in range(self.levels))
-                ws['gstats'] = f32(2 * parts)
-                ws['gnA'] = [f32(max(self.ch)) for _ in range(4)]
-                ws['gnB'] = [f32(max(self.ch)) for _ in range(4)]
-                ws['gn'] = [f32(N * max(self.ch)) for _ in range(4)]
-                ws['gnslab'] = f32(max(nv.lib().iunet_gn_num_parts(N, _vox(dims[l])) * self.ch[l] * 2 for l in range(self.levels)))
-            if len(self._ws_cache) > 4:
-                self._ws_cache.clear()
-            self._ws_cache[key] = ws
+            v = _vox(dims[l])
+            ws[f'a{l}'] = mq(self.ch[l], v)
+            ws[f'b{l}'] = mk(self.ch[l], v)
+            if l < self.levels - 1:
+                ws[f'cat{l}'] = mq(2 * self.ch[l], v)
+            if l > 0:
+                ws[f'pin{l}'] = mq(self.ch[l - 1], v)
+        if self.norm == 'group':
+            f32 = lambda n: torch.empty(n, dtype=torch.float32, device=self.device)
+            ws['raw'] = mk(max(self.ch[l] * _vox(dims[l]) for l in range(self.levels)), 1)
+            # fused form (one sample at a time): raw outputs of a stage's two convs, the convs' statistics rows, two
+            # (scale, shift, mean, invstd) sets
+            one = max(self.ch[l] * _vox(dims[l]) for l in range(self.levels))
+            ws['rawA'] = torch.empty(one, dtype=self.act_dtype, device=self.device)
+            ws['rawB'] = torch.empty(one, dtype=self.act_dtype, device=self.device)
+            parts = max(max(nv.lib().iunet_conv3_num_tiles(self.dim, 1, *dims[l]),
+                            nv.lib().iunet_conv3_stats_parts(self.dim, 1, *dims[l], self.ch[l], 2)) * self.ch[l] for l in range(self.levels))
+            ws['gstats'] = f32(2 * parts)
+            ws['gnA'] = [f32(max(self.ch)) for _ in range(4)]
+            ws['gnB'] = [f32(max(self.ch)) for _ in range(4)]
+            ws['gn'] = [f32(N * max(self.ch)) for _ in range(4)]
+            ws['gnslab'] = f32(max(nv.lib().iunet_gn_num_parts(N, _vox(dims[l])) * self.ch[l] * 2 for l in range(self.levels)))
         return ws
 
     # ------------------------------------------------------------------ forward (inference)
@@ -378,8 +383,7 @@ class Engine:
         scaled by 1/255 as predict.py:30 does); `x_strides` = element strides (n, c, d, h, w).
         Outputs (all optional): logits / probs fp32 written with `out_strides` (n, c, d, h, w),
         cls uint8 [N, D*H*W]."""
-        if self.packed is None:
-            raise RuntimeError('Engine.load_eval() has not been called')
+        self._require_loaded()
         g = self._graph()
         if g is not None and not features_only and self.probe is None:
             # the whole forward as one C call (csrc/net.hip: the same launches on the same operators, sequenced in C++)
@@ -439,11 +443,8 @@ class Engine:
         if features_only:
             return ws['b0']                       # input of the head, NHWC8c
         hw, hb = self.packed['head']
-        if out_strides is None:
-            v = _vox(dims[0])
-            out_strides = (self.ncls * v, v, H * W, W, 1)          # contiguous NC(D)HW
         nv.call('iunet_head_fwd', self.dt, P(ws['b0']), ch[0] * _vox(dims[0]), ch[0], nv.ptr(hw), nv.ptr(hb),
-                self.ncls, nv.ptr(logits), nv.ptr(probs), nv.ptr(cls), nv.ll_array(out_strides),
+                self.ncls, nv.ptr(logits), nv.ptr(probs), nv.ptr(cls), nv.ll_array(self._out_strides(out_strides, D, H, W)),
                 float(divisor), int(bool(accumulate)), N, D, H, W, s)
 
     # ------------------------------------------------------------------ layout helpers (tests / debugging)
@@ -465,15 +466,12 @@ class EncoderOnly:
     """What the forward engines of the encoder-only decoders (LinkNet, DeepLabV3, Segformer) share in both numeric forms: the U-Net's
     encoder with X^l written to x{l}, a workspace laid out by the architecture's `_bufs(dims, N)` -> (activation element counts, fp32
     element counts), and no C-sequenced handle."""
+    workspaces_kept = 1
 
-    def enc_names(self):
-        return [f'enc{l}' for l in range(self.levels)]
+    def stage_names(self):
+        return topology.encoder_names(self.levels)
 
-    def enc_io(self, prefix):
-        l = int(prefix[3:])
-        return (self.cin if l == 0 else self.ch[l - 1]), self.ch[l]
-
-    def _graph(self):
+    def _graph_spec(self):
         return None          # (every forward is sequenced from Python)
 
     def bytes_per_slice(self, input_size):
@@ -482,17 +480,11 @@ class EncoderOnly:
         act, f32 = self._bufs([(1, S >> l, S >> l) for l in range(self.levels)], 1)
         return sum(act.values()) * self._es + sum(f32.values()) * 4
 
-    def workspace(self, N, D, H, W):
-        key = (N, D, H, W)
-        ws = self._ws_cache.get(key)
-        if ws is None:
-            check_spatial(self.dim, self.levels, D, H, W)
-            dims = self.level_dims(D, H, W)
-            act, f32 = self._bufs(dims, N)
-            ws = {k: torch.empty(n, dtype=self.act_dtype, device=self.device) for k, n in act.items()}
-            ws.update({k: torch.empty(n, dtype=torch.float32, device=self.device) for k, n in f32.items()})
-            ws['dims'] = dims
-            self._ws_cache = {key: ws}
+    def _build_workspace(self, N, dims):
+        act, f32 = self._bufs(dims, N)
+        ws = {k: torch.empty(n, dtype=self.act_dtype, device=self.device) for k, n in act.items()}
+        ws.update({k: torch.empty(n, dtype=torch.float32, device=self.device) for k, n in f32.items()})
+        ws['dims'] = dims
         return ws
 
     def _P(self, t, off_elems=0):
@@ -500,8 +492,7 @@ class EncoderOnly:
 
     def _encoder(self, x, x_strides, N, D, H, W):
         """The encoder into x{l} of the workspace, which it returns (the decoder's launches follow)."""
-        if self.packed is None:
-            raise RuntimeError(f'{type(self).__name__}.load_eval() has not been called')
+        self._require_loaded()
         ws = self.workspace(N, D, H, W)
         self._encoder_forward(ws, x, x_strides, N)
         return ws
@@ -534,11 +525,8 @@ class CoarseLogits:
         if features_only:
             return lc
         dc = self.workspace(N, D, H, W)['dims'][self.coarse_level]
-        if out_strides is None:
-            v = D * H * W
-            out_strides = (self.ncls * v, v, H * W, W, 1)
         nv.call('iunet_dl_up_head', self.dim, nv.ptr(lc), self.ncls, dc[0], dc[1], dc[2], 2 ** self.coarse_level, nv.ptr(logits), nv.ptr(probs),
-                nv.ptr(cls), nv.ll_array(out_strides), float(divisor), int(bool(accumulate)), N, nv.stream())
+                nv.ptr(cls), nv.ll_array(self._out_strides(out_strides, D, H, W)), float(divisor), int(bool(accumulate)), N, nv.stream())
 
 
 class EncoderEngine(EncoderOnly, Engine):
@@ -555,15 +543,13 @@ class EncoderEngine(EncoderOnly, Engine):
 
     def load_eval(self, params):
         """Fold eval-mode BatchNorm into every conv and pack all operators."""
-        if not hasattr(self, '_stage'):
-            self._stage = {}
         src = lambda n: self._source(params, n)
         P, descs, keep = {}, [], []
-        for prefix in self.enc_names():
-            ci, co = self.enc_io(prefix)
+        for prefix in self.stage_names():
+            ci, co = self.stage_io(prefix)
             for j, (a, b) in enumerate(((ci, co), (co, co)), 1):
                 w = src(f'{prefix}.conv{j}.weight')
-                bn = [src(f'{prefix}.bn{j}.{k}') for k in ('weight', 'bias', 'running_mean', 'running_var')]
+                bn = [src(f'{prefix}.bn{j}.{k}') for k in topology.BN_KEYS]
                 keep += [w] + bn
                 bias = torch.empty(b, dtype=torch.float32, device=self.device)
                 if prefix == 'enc0' and j == 1:

@@ -27,6 +27,7 @@ import torch
 
 from . import _native as nv
 from .engine_x2 import EngineX2
+from .topology import channels
 
 THRESHOLD = 4e-4          # on max |logit_x2m - logit_fp16x2| of the calibration tile; the gate itself is 1e-3 against the CPU fp32 path
 RECAL_EVERY = 16          # weight loads between two calibrations while the weights keep moving
@@ -48,7 +49,7 @@ class EngineAuto:
         self.dim, self.levels, self.base, self.cin, self.ncls = dim, levels, base, cin, ncls
         self.device = torch.device(device)
         self.policy, self.threshold, self.recal_every = policy, float(threshold), int(recal_every)
-        self.ch = [base * 2 ** l for l in range(levels)]
+        self.ch = channels(base, levels)          # (the limits are the forms' own: a form's constructor refuses, at the first load)
         self._engines = {}                 # form name -> engine
         self._loaded = {}                  # form name -> weight-load index its operators were prepared at
         self.mode = None if policy == 'auto' else policy           # form of the next forward (None: not calibrated yet -> x2m runs the calibration)

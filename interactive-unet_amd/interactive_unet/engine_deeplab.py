@@ -14,6 +14,7 @@ import torch
 from . import _native as nv
 from .engine import BN_EPS, CoarseLogits, EncoderEngine, _vox
 from .engine_f32 import EncoderEngineF32
+from .topology import BN_KEYS
 
 BRANCHES = ('aspp.b0', 'aspp.b1', 'aspp.b2', 'aspp.b3')
 
@@ -55,13 +56,13 @@ class _DeepLab(CoarseLogits):
             cin = 4 * C if prefix == 'aspp.project' else cin_tot
             kw = (1 if ksz == 1 else self.kvol) * cin
             w = src(f'{prefix}.conv.weight')
-            g = [src(f'{prefix}.bn.{k}') for k in ('weight', 'bias', 'running_mean', 'running_var')]
+            g = [src(f'{prefix}.bn.{k}') for k in BN_KEYS]
             dst = torch.empty(C * kw, dtype=self._pack_dtype, device=self.device)
             bias = torch.empty(C, dtype=torch.float32, device=self.device)
             nv.call('iunet_dl_pack', dtype_code, self.dim, 0, ksz, nv.ptr(w), nv.ptr(g[0]), nv.ptr(g[1]), nv.ptr(g[2]), nv.ptr(g[3]), BN_EPS,
                     nv.ptr(dst), nv.ptr(bias), C, cin, cin_tot, 0, 0, kw, nv.stream())
             P[prefix] = (dst, bias, kw, g + [w])               # (the sources stay alive until the pack has run)
-        P['pool'] = [src('aspp.pool.conv.weight')] + [src(f'aspp.pool.bn.{k}') for k in ('weight', 'bias', 'running_mean', 'running_var')]
+        P['pool'] = [src('aspp.pool.conv.weight')] + [src(f'aspp.pool.bn.{k}') for k in BN_KEYS]
         P['proj_src'] = [src('aspp.project.conv.weight'), src('aspp.project.bn.weight'), src('aspp.project.bn.running_var')]
         P['head'] = (src('head.weight').reshape(self.ncls, C).contiguous(), src('head.bias'))
         return P

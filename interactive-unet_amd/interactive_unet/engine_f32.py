@@ -13,40 +13,18 @@ import ctypes
 import torch
 
 from . import _native as nv
-from .engine import BN_EPS, EncoderOnly, _vox, check_spatial
+from .engine import BN_EPS, EncoderOnly, ForwardEngine, _vox
+from .topology import BN_KEYS
 
 
-class EngineF32:
+class EngineF32(ForwardEngine):
     act_dtype = torch.float32
     weight_dtype = None
+    limits_cin = False         # (the 16-bit and split-precision forms refuse cin outside 1..4; this one never has)
 
     def __init__(self, dim=2, levels=4, base=32, cin=1, ncls=2, device='cuda', norm='batch', groups=8):
-        if norm not in ('batch', 'group'):
-            raise ValueError("norm must be 'batch' or 'group'")
-        if norm == 'group' and base % groups:
-            raise ValueError(f'{groups} groups do not divide {base} channels')
-        self.norm, self.groups = norm, groups
-        if dim not in (2, 3):
-            raise ValueError('dim must be 2 or 3')
-        if base % 32 != 0:
-            raise NotImplementedError('native U-Net needs base channels to be a multiple of 32')
-        if not (2 <= ncls <= 10):
-            raise NotImplementedError('native U-Net supports 2..10 classes (app.py:162)')
-        self.dim, self.levels, self.base, self.cin, self.ncls = dim, levels, base, cin, ncls
-        self.device = torch.device(device)
-        self.ch = [base * 2 ** l for l in range(levels)]
-        self.taps, self.npos = 3 ** dim, 2 ** dim
-        self.packed = None
-        self._ws_cache = {}
-        nv.lib()
-
-    def stage_names(self):
-        return [f'enc{l}' for l in range(self.levels)] + [f'dec{l}' for l in range(self.levels - 2, -1, -1)]
-
-    def stage_io(self, prefix):
-        l = int(prefix[3:])
-        ci = (self.cin if l == 0 else self.ch[l - 1]) if prefix.startswith('enc') else 2 * self.ch[l]
-        return ci, self.ch[l]
+        super().__init__(dim, levels, base, cin, ncls, device, norm, groups)
+        self.use_graph = False     # (no handle mode in fp32)
 
     def load_eval(self, params):
         """Fold eval-mode BatchNorm (fp32, the oracle's operation order) and pack every operator."""
@@ -57,7 +35,7 @@ class EngineF32:
             ci, co = self.stage_io(prefix)
             for j, (a, b) in enumerate(((ci, co), (co, co)), 1):
                 w = src(f'{prefix}.conv{j}.weight')
-                bn = [src(f'{prefix}.bn{j}.{k}') for k in ('weight', 'bias', 'running_mean', 'running_var')]
+                bn = [src(f'{prefix}.bn{j}.{k}') for k in BN_KEYS]
                 dst, bias = f32(lib.iunet_f32_pack_conv_elems(b, a, self.taps)), f32(b)
                 if self.norm == 'group':          # raw operator; gamma / beta go to the normalisation pass
                     nv.call('iunet_f32_pack_conv', nv.ptr(w), nv.ptr(dst), None, None, None, None, None, BN_EPS, b, a, self.taps, 0, s)
@@ -76,38 +54,28 @@ class EngineF32:
         torch.cuda.current_stream().synchronize()          # the staging copies above may be freed by the caller
         self.packed = P
 
-    def level_dims(self, D, H, W):
-        return [((D >> l) if self.dim == 3 else 1, H >> l, W >> l) for l in range(self.levels)]
-
-    def workspace(self, N, D, H, W):
-        key = (N, D, H, W)
-        ws = self._ws_cache.get(key)
-        if ws is None:
-            check_spatial(self.dim, self.levels, D, H, W)
-            dims = self.level_dims(D, H, W)
-            mk = lambda c, v: torch.empty(N * c * v, dtype=torch.float32, device=self.device)
-            ws = {'dims': dims}
-            for l in range(self.levels):
-                v = _vox(dims[l])
-                ws[f'a{l}'] = mk(self.ch[l], v)
-                if l < self.levels - 1:
-                    ws[f'cat{l}'] = mk(2 * self.ch[l], v)
-                ws[f'b{l}'] = mk(self.ch[l], v)
-                if l > 0:
-                    ws[f'pin{l}'] = mk(self.ch[l - 1], v)
-            if self.norm == 'group':
-                ws['raw'] = mk(max(self.ch[l] * _vox(dims[l]) for l in range(self.levels)), 1)
-                ws['gnslab'] = torch.empty(max(nv.lib().iunet_gn_precise_slab_bytes(N, self.ch[l], _vox(dims[l])) for l in range(self.levels)),
-                                           dtype=torch.uint8, device=self.device)
-                ws['gnsc'], ws['gnsh'] = mk(N * max(self.ch), 1), mk(N * max(self.ch), 1)
-            self._ws_cache = {key: ws}
+    def _build_workspace(self, N, dims):
+        mk = lambda c, v: torch.empty(N * c * v, dtype=torch.float32, device=self.device)
+        ws = {'dims': dims}
+        for l in range(self.levels):
+            v = _vox(dims[l])
+            ws[f'a{l}'] = mk(self.ch[l], v)
+            if l < self.levels - 1:
+                ws[f'cat{l}'] = mk(2 * self.ch[l], v)
+            ws[f'b{l}'] = mk(self.ch[l], v)
+            if l > 0:
+                ws[f'pin{l}'] = mk(self.ch[l - 1], v)
+        if self.norm == 'group':
+            ws['raw'] = mk(max(self.ch[l] * _vox(dims[l]) for l in range(self.levels)), 1)
+            ws['gnslab'] = torch.empty(max(nv.lib().iunet_gn_precise_slab_bytes(N, self.ch[l], _vox(dims[l])) for l in range(self.levels)),
+                                       dtype=torch.uint8, device=self.device)
+            ws['gnsc'], ws['gnsh'] = mk(N * max(self.ch), 1), mk(N * max(self.ch), 1)
         return ws
 
     def infer(self, x, x_strides, N, D, H, W, logits=None, probs=None, cls=None, out_strides=None,
               divisor=1.0, accumulate=False, features_only=False):
         """engine.Engine.infer with fp32 arithmetic end to end (same arguments and output contract)."""
-        if self.packed is None:
-            raise RuntimeError('EngineF32.load_eval() has not been called')
+        self._require_loaded()
         ws = self.workspace(N, D, H, W)
         dims, L, ch, s = ws['dims'], self.levels, self.ch, nv.stream()
         Pt = lambda t, off=0: ctypes.c_void_p(t.data_ptr() + 4 * off)
@@ -150,11 +118,8 @@ class EngineF32:
         if features_only:
             return b_of(0)                          # planar fp32 [N][C0][vox]
         hw, hb = self.packed['head']
-        if out_strides is None:
-            v = _vox(dims[0])
-            out_strides = (self.ncls * v, v, H * W, W, 1)
         nv.call('iunet_f32_head_fwd', Pt(b_of(0)), ch[0] * _vox(dims[0]), ch[0], nv.ptr(hw), nv.ptr(hb), self.ncls,
-                nv.ptr(logits), nv.ptr(probs), nv.ptr(cls), nv.ll_array(out_strides), float(divisor),
+                nv.ptr(logits), nv.ptr(probs), nv.ptr(cls), nv.ll_array(self._out_strides(out_strides, D, H, W)), float(divisor),
                 int(bool(accumulate)), N, D, H, W, s)
 
 
@@ -166,17 +131,16 @@ class EncoderEngineF32(EncoderOnly, EngineF32):
     def __init__(self, dim=2, levels=4, base=32, cin=1, ncls=2, device='cuda'):
         EngineF32.__init__(self, dim, levels, base, cin, ncls, device)
         self._es, self._pack_dtype = 4, torch.float32
-        self.use_graph = False
 
     def load_eval(self, params):
         f32 = lambda n: torch.empty(n, dtype=torch.float32, device=self.device)
         src = lambda name: params[name].detach().to(self.device, torch.float32).contiguous()
         lib, s, P = nv.lib(), nv.stream(), {}
-        for prefix in self.enc_names():
-            ci, co = self.enc_io(prefix)
+        for prefix in self.stage_names():
+            ci, co = self.stage_io(prefix)
             for j, (a, b) in enumerate(((ci, co), (co, co)), 1):
                 w = src(f'{prefix}.conv{j}.weight')
-                bn = [src(f'{prefix}.bn{j}.{k}') for k in ('weight', 'bias', 'running_mean', 'running_var')]
+                bn = [src(f'{prefix}.bn{j}.{k}') for k in BN_KEYS]
                 dst, bias = f32(lib.iunet_f32_pack_conv_elems(b, a, self.taps)), f32(b)
                 nv.call('iunet_f32_pack_conv', nv.ptr(w), nv.ptr(dst), nv.ptr(bias), nv.ptr(bn[0]), nv.ptr(bn[1]),
                         nv.ptr(bn[2]), nv.ptr(bn[3]), BN_EPS, b, a, self.taps, 0, s)

@@ -13,6 +13,7 @@ import torch
 from . import _native as nv
 from .engine import BN_EPS, EncoderEngine, _vox
 from .engine_f32 import EncoderEngineF32
+from .topology import BN_KEYS
 
 
 class _Link:
@@ -42,7 +43,7 @@ class _Link:
             m = self.ch[l + 1] // 4
             for key, bn, kind, co, ci in (('conv1', 'bn1', 0, m, self.ch[l + 1]), ('up', 'bn2', 2, m, m), ('conv2', 'bn3', 0, self.ch[l], m)):
                 w = src(f'dec{l}.{key}.weight')
-                g = [src(f'dec{l}.{bn}.{k}') for k in ('weight', 'bias', 'running_mean', 'running_var')]
+                g = [src(f'dec{l}.{bn}.{k}') for k in BN_KEYS]
                 dst = torch.empty(nv.lib().iunet_lk_pack_elems(self.dim, kind, co, ci), dtype=self._pack_dtype, device=self.device)
                 bias = torch.empty(co, dtype=torch.float32, device=self.device)
                 nv.call('iunet_lk_pack', dtype_code, self.dim, kind, nv.ptr(w), nv.ptr(g[0]), nv.ptr(g[1]), nv.ptr(g[2]), nv.ptr(g[3]),
@@ -69,11 +70,8 @@ class LinkNetEngine(_Link, EncoderEngine):
         if features_only:
             return ws['d0']
         hw, hb = self.packed['head']
-        if out_strides is None:
-            v = _vox(dims[0])
-            out_strides = (self.ncls * v, v, H * W, W, 1)
         nv.call('iunet_head_fwd', self.dt, P(ws['d0']), ch[0] * _vox(dims[0]), ch[0], nv.ptr(hw), nv.ptr(hb),
-                self.ncls, nv.ptr(logits), nv.ptr(probs), nv.ptr(cls), nv.ll_array(out_strides),
+                self.ncls, nv.ptr(logits), nv.ptr(probs), nv.ptr(cls), nv.ll_array(self._out_strides(out_strides, D, H, W)),
                 float(divisor), int(bool(accumulate)), N, D, H, W, s)
 
     def _lk(self, kind, key, l, xp, x_ss, yp, y_ss, N, d, ci, co, s, skip=(None, 0)):
@@ -106,9 +104,6 @@ class LinkNetEngineF32(_Link, EncoderEngineF32):
         if features_only:
             return ws['d0']
         hw, hb = self.packed['head']
-        if out_strides is None:
-            v = _vox(dims[0])
-            out_strides = (self.ncls * v, v, H * W, W, 1)
         nv.call('iunet_f32_head_fwd', P(ws['d0']), ch[0] * _vox(dims[0]), ch[0], nv.ptr(hw), nv.ptr(hb), self.ncls,
-                nv.ptr(logits), nv.ptr(probs), nv.ptr(cls), nv.ll_array(out_strides), float(divisor),
+                nv.ptr(logits), nv.ptr(probs), nv.ptr(cls), nv.ll_array(self._out_strides(out_strides, D, H, W)), float(divisor),
                 int(bool(accumulate)), N, D, H, W, s)

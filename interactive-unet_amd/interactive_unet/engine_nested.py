@@ -17,7 +17,8 @@ import ctypes
 import torch
 
 from . import _native as nv
-from .engine import BN_EPS, Engine, _vox, check_spatial
+from . import topology
+from .engine import BN_EPS, Engine, _vox
 from .engine_f32 import EngineF32
 from .unet import nested_nodes
 
@@ -37,23 +38,15 @@ def _level_bufs(levels, ch, dims, N, es):
 
 class _Nested:
     """What the two nested engines share: names, shapes, workspace sizes."""
-
-    def _nested_init(self):
-        self.nodes = nested_nodes(self.levels)
-        self.use_graph = False
+    workspaces_kept = 1
 
     def stage_names(self):
-        return [f'enc{l}' for l in range(self.levels)] + [f'dec{i}_{j}' for i, j in self.nodes]
+        return topology.nested_stage_names(self.levels)
 
-    def stage_io(self, prefix):
-        if prefix.startswith('enc'):
-            l = int(prefix[3:])
-            return (self.cin if l == 0 else self.ch[l - 1]), self.ch[l]
-        i, j = (int(t) for t in prefix[3:].split('_'))
-        return (j + 1) * self.ch[i], self.ch[i]
-
-    def _graph(self):
-        return None          # (the fp32 form has no handle mode)
+    def _build_workspace(self, N, dims):
+        ws = {k: torch.empty(n, dtype=self.act_dtype, device=self.device) for k, n in _level_bufs(self.levels, self.ch, dims, N, 0).items()}
+        ws['dims'] = dims
+        return ws
 
     def bytes_per_slice(self, input_size):
         """Workspace bytes of one 2-D slice of input_size^2 (predict.find_max_batch_size)."""
@@ -75,47 +68,25 @@ class NestedEngine(_Nested, Engine):
         if act_dtype not in (torch.float16, torch.bfloat16):
             raise NotImplementedError("NestedEngine runs fp16 / bf16 activations (NestedEngineF32: the fp32 form)")
         Engine.__init__(self, dim, levels, base, cin, ncls, act_dtype, device)
-        self._nested_init()
-        self.use_graph = True      # False: every forward sequenced from Python (tests compare the two)
+        self.nodes = nested_nodes(self.levels)
         self._es = 2
 
-    def _graph(self):
-        """The C++-sequenced nested forward (net_graph.NetGraph over iunet_net_create_nested) on this engine's current parameters, from the
-        SECOND forward on them (engine.Engine._graph's rule), or None (IUNET_PY_GRAPH=1, use_graph False, nothing loaded yet)."""
-        from . import net_graph
-        self._g_fwd += 1
-        if self._g_fwd < 2 or not net_graph.ENABLED or not self.use_graph or self._gparams is None:
-            return None
-        if self._g is None:
-            self._g = net_graph.NetGraph(self.dim, self.levels, self.base, self.cin, self.ncls, self.dt, self.device, nested=True)
-        if self._g_dirty:
-            self._g.set_params(self._gparams)
-            self._g_dirty = False
-            self._ws_cache.clear()         # the handle has its own workspace
-        return self._g
+    def _graph_spec(self):
+        """The nested handle (iunet_net_create_nested), at every level count the module allows."""
+        return dict(mode=self.dt, nested=True)
 
     def load_eval(self, params):
         """Fold eval-mode BatchNorm into every stage conv and pack all operators (one launch over a descriptor table, rebuilt when a
         source tensor moves), as Engine.load_eval does for the U-Net."""
-        if not hasattr(self, '_stage'):
-            self._stage, self._eval_sig, self._eval_table = {}, None, None
-        self._gparams, self._g_dirty, self._g_fwd = params, True, 0
-        names = []
-        for prefix in self.stage_names():
-            for j in (1, 2):
-                names += [f'{prefix}.conv{j}.weight'] + [f'{prefix}.bn{j}.{k}' for k in ('weight', 'bias', 'running_mean', 'running_var')]
-        for i, j in self.nodes:
-            names += [f'dec{i}_{j}.up.weight', f'dec{i}_{j}.up.bias']
-        names += ['head.weight', 'head.bias']
-        src = {n: self._source(params, n) for n in names}
-        sig = tuple(t.data_ptr() for t in src.values())
+        self._new_params(params)
+        src, sig = self._sources(params, topology.param_names(self.stage_names(), topology.nested_up_convs(self.levels)))
         if sig != self._eval_sig:
             P, descs = {}, []
             for prefix in self.stage_names():
                 ci, co = self.stage_io(prefix)
                 for j, (a, b) in enumerate(((ci, co), (co, co)), 1):
                     w = src[f'{prefix}.conv{j}.weight']
-                    bn = [src[f'{prefix}.bn{j}.{k}'] for k in ('weight', 'bias', 'running_mean', 'running_var')]
+                    bn = [src[f'{prefix}.bn{j}.{k}'] for k in topology.BN_KEYS]
                     bias = torch.empty(b, dtype=torch.float32, device=self.device)
                     if prefix == 'enc0' and j == 1:
                         dst = torch.empty(nv.lib().iunet_pack_first_conv_elems(b, a, self.taps), dtype=self.act_dtype, device=self.device)
@@ -135,22 +106,10 @@ class NestedEngine(_Nested, Engine):
             self.packed = P
         self._eval_table.run()
 
-    def workspace(self, N, D, H, W):
-        key = (N, D, H, W)
-        ws = self._ws_cache.get(key)
-        if ws is None:
-            self.check_shape(D, H, W)
-            dims = self.level_dims(D, H, W)
-            ws = {k: torch.empty(n, dtype=self.act_dtype, device=self.device) for k, n in _level_bufs(self.levels, self.ch, dims, N, 0).items()}
-            ws['dims'] = dims
-            self._ws_cache = {key: ws}
-        return ws
-
     def infer(self, x, x_strides, N, D, H, W, logits=None, probs=None, cls=None, out_strides=None,
               divisor=1.0, accumulate=False, features_only=False):
         """engine.Engine.infer's contract on the nested graph (features_only: the head's input X^{0,L-1}, NHWC8c, contiguous)."""
-        if self.packed is None:
-            raise RuntimeError('NestedEngine.load_eval() has not been called')
+        self._require_loaded()
         g = self._graph()
         if g is not None and not features_only and self.probe is None:
             self.check_shape(D, H, W)
@@ -187,11 +146,8 @@ class NestedEngine(_Nested, Engine):
         if features_only:
             return ws['b0']
         hw, hb = self.packed['head']
-        if out_strides is None:
-            v = _vox(dims[0])
-            out_strides = (self.ncls * v, v, H * W, W, 1)
         nv.call('iunet_head_fwd', self.dt, P(ws['b0']), ch[0] * _vox(dims[0]), ch[0], nv.ptr(hw), nv.ptr(hb),
-                self.ncls, nv.ptr(logits), nv.ptr(probs), nv.ptr(cls), nv.ll_array(out_strides),
+                self.ncls, nv.ptr(logits), nv.ptr(probs), nv.ptr(cls), nv.ll_array(self._out_strides(out_strides, D, H, W)),
                 float(divisor), int(bool(accumulate)), N, D, H, W, s)
 
 
@@ -201,7 +157,7 @@ class NestedEngineF32(_Nested, EngineF32):
 
     def __init__(self, dim=2, levels=4, base=32, cin=1, ncls=2, device='cuda'):
         EngineF32.__init__(self, dim, levels, base, cin, ncls, device)
-        self._nested_init()
+        self.nodes = nested_nodes(self.levels)
         self._es = 4
 
     def load_eval(self, params):
@@ -212,7 +168,7 @@ class NestedEngineF32(_Nested, EngineF32):
             ci, co = self.stage_io(prefix)
             for j, (a, b) in enumerate(((ci, co), (co, co)), 1):
                 w = src(f'{prefix}.conv{j}.weight')
-                bn = [src(f'{prefix}.bn{j}.{k}') for k in ('weight', 'bias', 'running_mean', 'running_var')]
+                bn = [src(f'{prefix}.bn{j}.{k}') for k in topology.BN_KEYS]
                 dst, bias = f32(lib.iunet_f32_pack_conv_elems(b, a, self.taps)), f32(b)
                 nv.call('iunet_f32_pack_conv', nv.ptr(w), nv.ptr(dst), nv.ptr(bias), nv.ptr(bn[0]), nv.ptr(bn[1]),
                         nv.ptr(bn[2]), nv.ptr(bn[3]), BN_EPS, b, a, self.taps, 0, s)
@@ -227,22 +183,10 @@ class NestedEngineF32(_Nested, EngineF32):
         torch.cuda.current_stream().synchronize()          # the staging copies above may be freed by the caller
         self.packed = P
 
-    def workspace(self, N, D, H, W):
-        key = (N, D, H, W)
-        ws = self._ws_cache.get(key)
-        if ws is None:
-            check_spatial(self.dim, self.levels, D, H, W)
-            dims = self.level_dims(D, H, W)
-            ws = {k: torch.empty(n, dtype=torch.float32, device=self.device) for k, n in _level_bufs(self.levels, self.ch, dims, N, 0).items()}
-            ws['dims'] = dims
-            self._ws_cache = {key: ws}
-        return ws
-
     def infer(self, x, x_strides, N, D, H, W, logits=None, probs=None, cls=None, out_strides=None,
               divisor=1.0, accumulate=False, features_only=False):
         """engine_f32.EngineF32.infer's contract on the nested graph (features_only: X^{0,L-1}, planar fp32)."""
-        if self.packed is None:
-            raise RuntimeError('NestedEngineF32.load_eval() has not been called')
+        self._require_loaded()
         ws = self.workspace(N, D, H, W)
         dims, L, ch, s = ws['dims'], self.levels, self.ch, nv.stream()
         P = lambda t: ctypes.c_void_p(t.data_ptr())
@@ -278,9 +222,6 @@ class NestedEngineF32(_Nested, EngineF32):
         if features_only:
             return ws['b0']
         hw, hb = self.packed['head']
-        if out_strides is None:
-            v = _vox(dims[0])
-            out_strides = (self.ncls * v, v, H * W, W, 1)
         nv.call('iunet_f32_head_fwd', P(ws['b0']), ch[0] * _vox(dims[0]), ch[0], nv.ptr(hw), nv.ptr(hb), self.ncls,
-                nv.ptr(logits), nv.ptr(probs), nv.ptr(cls), nv.ll_array(out_strides), float(divisor),
+                nv.ptr(logits), nv.ptr(probs), nv.ptr(cls), nv.ll_array(self._out_strides(out_strides, D, H, W)), float(divisor),
                 int(bool(accumulate)), N, D, H, W, s)

@@ -14,6 +14,7 @@ import torch
 from . import _native as nv
 from .engine import BN_EPS, CoarseLogits, EncoderEngine, _vox
 from .engine_f32 import EncoderEngineF32
+from .topology import BN_KEYS
 
 T_LEVEL = 2          # the target grid T is level 2's grid (stride 4)
 
@@ -63,7 +64,7 @@ class _Segformer(CoarseLogits):
     def _pack_decoder(self, src, dtype_code):
         """The collapsed decoder operator with fuse.bn folded: {sf: (operator [C][K], bias [C], kept sources), head}."""
         wf, w, b, keep = pack_args(src, self.levels)
-        g = [src(f'fuse.bn.{k}') for k in ('weight', 'bias', 'running_mean', 'running_var')]
+        g = [src(f'fuse.bn.{k}') for k in BN_KEYS]
         dst = torch.empty(self.C * self.K, dtype=self._pack_dtype, device=self.device)
         bias = torch.empty(self.C, dtype=torch.float32, device=self.device)
         nv.call('iunet_sf_pack', dtype_code, self.levels, self.C, nv.int_array(self.ch), wf, w, b, nv.ptr(g[0]), nv.ptr(g[1]), nv.ptr(g[2]),

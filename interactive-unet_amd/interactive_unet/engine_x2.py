@@ -25,115 +25,48 @@ import os
 import torch
 
 from . import _native as nv
-from .engine import BN_EPS, _vox, check_spatial
+from . import topology
+from .engine import BN_EPS, ForwardEngine, _vox
 
 
-class EngineX2:
+class EngineX2(ForwardEngine):
     act_dtype = 'fp16x2'
     weight_dtype = None
+    workspaces_kept = 5        # (engine.Engine likewise; every other engine keeps one)
 
     def __init__(self, dim=2, levels=4, base=32, cin=1, ncls=2, device='cuda', act_scale=64.0, mixed=None, norm='batch', groups=8):
-        if norm not in ('batch', 'group'):
-            raise ValueError("norm must be 'batch' or 'group'")
-        if norm == 'group' and base % groups:
-            raise ValueError(f'{groups} groups do not divide {base} channels')
         # norm='group': GroupNorm(groups) + ReLU after every stage conv (north_star "GroupNorm/BN").  Nothing folds: the stage convs write
         # their raw output as split words (epilogue without bias / ReLU) and csrc/gn_precise.hip normalises it with per-(sample, group)
         # statistics taken in double, writing the consumer's format (fp16x2: hi + lo planes; x2m: hi + lo8 planes).  What the BatchNorm
         # network fuses into conv epilogues -- the max-pool, the head -- runs as its own launch here (the statistics come first)
-        self.norm, self.groups = norm, groups
-        if dim not in (2, 3):
-            raise ValueError('dim must be 2 or 3')
-        if base % 32 != 0:
-            raise NotImplementedError('native U-Net needs base channels to be a multiple of 32')
-        if not (1 <= cin <= 4):
-            raise NotImplementedError('native U-Net supports 1..4 input channels')
-        if not (2 <= ncls <= 10):
-            raise NotImplementedError('native U-Net supports 2..10 classes (app.py:162)')
-        self.dim, self.levels, self.base, self.cin, self.ncls = dim, levels, base, cin, ncls
+        super().__init__(dim, levels, base, cin, ncls, device, norm, groups)
         self.act_scale = float(act_scale)
         # cross terms of the stage convs on the fp8 matrix cores (csrc/conv3_x2m.hip; 3-D: 4 filter columns x 32 virtual channels per
         # K = 128 instruction, 2-D: 4 taps x 32)
         self.mixed = os.environ.get('IUNET_X2M', '1') != '0' if mixed is None else bool(mixed)
-        self.device = torch.device(device)
-        self.ch = [base * 2 ** l for l in range(levels)]
-        self.taps, self.npos = 3 ** dim, 2 ** dim
-        self.packed = None
-        self._ws_cache = {}
-        self.probe = None          # {'name': layer, 'events': []}: timing hook of one layer's launches (bench.py)
-        self.use_graph = True      # False: every forward sequenced from Python (tests compare the two)
-        self._g, self._gparams, self._g_dirty, self._g_last, self._g_fwd = None, None, False, None, 0      # the C++-sequenced forward (_graph)
-        nv.lib()
+        self._bufs, self._g_last = {}, None
         # range flag: every producer of the forward raises it (atomicMax, no synchronisation) to 0x7bff when a stored hi word saturated at 65504
         self._sat = torch.zeros(1, dtype=torch.int32, device=self.device)
 
-    def _graph(self):
-        """The C++-sequenced forward (net_graph.NetGraph) on this engine's current parameters, or None where the handle level does not
-        apply (GroupNorm, fp8 operators, IUNET_PY_GRAPH=1).  The handle packs its own copy of the operators (one copy of the parameters
-        + ~40 launches), so it is loaded at the SECOND forward on the same parameters: a training loop that predicts once per optimiser
-        step, or a validation pass that only asks for features, never pays for it; a slice / block / volume prediction does once."""
-        from . import net_graph
-        self._g_fwd += 1
-        if self._g_fwd < 2:
-            return None
-        if not net_graph.ENABLED or not self.use_graph or self.weight_dtype or not (2 <= self.levels <= 6) or self._gparams is None:
+    def _graph_spec(self):
+        if self.weight_dtype or not (2 <= self.levels <= 6):
             return None
         if self.mixed and self.norm == 'group':
             return None                    # (the handle sequences GroupNorm in the fp16x2 form only: iunet_net_create_ex, mode 2)
-        if self._g is None:
-            self._g = net_graph.NetGraph(self.dim, self.levels, self.base, self.cin, self.ncls, 3 if self.mixed else 2, self.device, act_scale=self.act_scale,
-                                         norm=self.norm, groups=self.groups)
-        if self._g_dirty:
-            self._g.set_params(self._gparams)
-            self._g_dirty = False
-            self._ws_cache.clear()         # the handle has its own workspace: the Python sequence's buffers go back to the allocator
-        return self._g
-
-    def stage_names(self):
-        return [f'enc{l}' for l in range(self.levels)] + [f'dec{l}' for l in range(self.levels - 2, -1, -1)]
-
-    def stage_io(self, prefix):
-        l = int(prefix[3:])
-        ci = (self.cin if l == 0 else self.ch[l - 1]) if prefix.startswith('enc') else 2 * self.ch[l]
-        return ci, self.ch[l]
+        return dict(mode=3 if self.mixed else 2, act_scale=self.act_scale, norm=self.norm, groups=self.groups)
 
     # ------------------------------------------------------------------ weights
-    def _source(self, params, name):
-        """fp32 device tensor the preparation kernel reads: the parameter itself when it already lives on the device, otherwise a
-        persistent staging copy (engine.Engine._source)."""
-        t = params[name].detach()
-        if t.device == self.device and t.dtype == torch.float32 and t.is_contiguous():
-            return t
-        st = self._stage.get(name)
-        if st is None or st.shape != t.shape:
-            st = self._stage[name] = torch.empty(t.shape, dtype=torch.float32, device=self.device)
-        st.copy_(t)
-        return st
-
     def load_eval(self, params):
         """Fold eval-mode BatchNorm (fp32, the oracle's operation order), scale, split and pack every operator: THREE launches over
         device-resident descriptor tables (iunet_x2_prep_batch: first conv, transposed convs and -- fp16x2 -- the stage convs;
         iunet_x2m_prep_batch: the x2m stage convs; iunet_pack_batch: the fragment orders), rebuilt only when a source tensor moves.  Every
         buffer is allocated once: a re-pack after an optimiser step is launches only (no allocation, no synchronisation).
         IUNET_X2_PREP_PER_LAYER=1: the per-layer calls the tables replace (two launches per operator; same bits: tests/test_gpu_x2m.py)."""
-        if not hasattr(self, '_stage'):
-            self._stage, self._bufs, self._eval_sig, self._eval_tables = {}, {}, None, None
-        self._gparams, self._g_dirty, self._g_fwd = params, True, 0
+        self._new_params(params)
         self.reset_saturation()
         dev = self.device
         lib, A = nv.lib(), self.act_scale
-        src = {}
-        for prefix in self.stage_names():
-            for j in (1, 2):
-                src[f'{prefix}.conv{j}.weight'] = self._source(params, f'{prefix}.conv{j}.weight')
-                for k in ('weight', 'bias', 'running_mean', 'running_var'):
-                    src[f'{prefix}.bn{j}.{k}'] = self._source(params, f'{prefix}.bn{j}.{k}')
-        for l in range(self.levels - 1):
-            src[f'dec{l}.up.weight'] = self._source(params, f'dec{l}.up.weight')
-            src[f'dec{l}.up.bias'] = self._source(params, f'dec{l}.up.bias')
-        src['head.weight'] = self._source(params, 'head.weight')
-        src['head.bias'] = self._source(params, 'head.bias')
-        sig = tuple(t.data_ptr() for t in src.values())
+        src, sig = self._sources(params, topology.param_names(self.stage_names(), topology.up_convs(self.levels)))
         if sig != self._eval_sig:
             P, d_x2, d_x2m, d_pack, per_layer = {}, [], [], [], []
 
@@ -150,7 +83,7 @@ class EngineX2:
                     name = f'{prefix}.conv{j}'
                     first = prefix == 'enc0' and j == 1
                     w = src[f'{name}.weight']
-                    bn = [src[f'{prefix}.bn{j}.{k}'] for k in ('weight', 'bias', 'running_mean', 'running_var')]
+                    bn = [src[f'{prefix}.bn{j}.{k}'] for k in topology.BN_KEYS]
                     gn = self.norm == 'group'
                     if self.mixed and not first:
                         # x2m: w_hi in the padded K16 order (3-D) / the cross-pair order (2-D: three k-groups per 32-channel step)
@@ -211,49 +144,35 @@ class EngineX2:
             t.run()
 
     # ------------------------------------------------------------------ workspace
-    def level_dims(self, D, H, W):
-        return [((D >> l) if self.dim == 3 else 1, H >> l, W >> l) for l in range(self.levels)]
-
-    def check_shape(self, D, H, W):
-        check_spatial(self.dim, self.levels, D, H, W)
-
-    def workspace(self, N, D, H, W):
-        key = (N, D, H, W)
-        ws = self._ws_cache.get(key)
-        if ws is None:
-            self.check_shape(D, H, W)
-            dims = self.level_dims(D, H, W)
-            # (zero-filled once: buffers the current launch sequence skips -- b0 behind the fused head, a0 behind the one-launch first
-            #  stage -- must not show up as garbage in max_stored(); the workspaces are cached, the fill is not on the hot path)
-            mk = lambda c, v: torch.zeros(N * 2 * c * v, dtype=torch.float16, device=self.device)     # hi + lo planes
-            mk8 = lambda c, v: torch.zeros(N * c * v, dtype=torch.uint8, device=self.device)          # lo8 planes: 1 byte per element (hi8 is made in LDS from the hi words)
-            mkh = lambda c, v: torch.zeros(N * c * v, dtype=torch.float16, device=self.device)        # hi planes only
-            ws = {'dims': dims}
-            for l in range(self.levels):
-                v = _vox(dims[l])
-                if self.mixed:       # a, cat, pin: read by 3x3x3 convs only (hi + lo8); b: by a transposed conv or the head (hi + lo)
-                    ws[f'a{l}'], ws[f'a{l}m'] = mkh(self.ch[l], v), mk8(self.ch[l], v)
-                    ws[f'b{l}'] = mk(self.ch[l], v)
-                    if l < self.levels - 1:
-                        ws[f'cat{l}'], ws[f'cat{l}m'] = mkh(2 * self.ch[l], v), mk8(2 * self.ch[l], v)
-                    if l > 0:
-                        ws[f'pin{l}'], ws[f'pin{l}m'] = mkh(self.ch[l - 1], v), mk8(self.ch[l - 1], v)
-                    continue
-                ws[f'a{l}'] = mk(self.ch[l], v)
+    def _build_workspace(self, N, dims):
+        # (zero-filled once: buffers the current launch sequence skips -- b0 behind the fused head, a0 behind the one-launch first
+        #  stage -- must not show up as garbage in max_stored(); the workspaces are cached, the fill is not on the hot path)
+        mk = lambda c, v: torch.zeros(N * 2 * c * v, dtype=torch.float16, device=self.device)     # hi + lo planes
+        mk8 = lambda c, v: torch.zeros(N * c * v, dtype=torch.uint8, device=self.device)          # lo8 planes: 1 byte per element (hi8 is made in LDS from the hi words)
+        mkh = lambda c, v: torch.zeros(N * c * v, dtype=torch.float16, device=self.device)        # hi planes only
+        ws = {'dims': dims}
+        for l in range(self.levels):
+            v = _vox(dims[l])
+            if self.mixed:       # a, cat, pin: read by 3x3x3 convs only (hi + lo8); b: by a transposed conv or the head (hi + lo)
+                ws[f'a{l}'], ws[f'a{l}m'] = mkh(self.ch[l], v), mk8(self.ch[l], v)
                 ws[f'b{l}'] = mk(self.ch[l], v)
                 if l < self.levels - 1:
-                    ws[f'cat{l}'] = mk(2 * self.ch[l], v)
+                    ws[f'cat{l}'], ws[f'cat{l}m'] = mkh(2 * self.ch[l], v), mk8(2 * self.ch[l], v)
                 if l > 0:
-                    ws[f'pin{l}'] = mk(self.ch[l - 1], v)
-            if self.norm == 'group':
-                ws['raw'] = torch.zeros(N * 2 * max(self.ch[l] * _vox(dims[l]) for l in range(self.levels)), dtype=torch.float16, device=self.device)
-                ws['gnslab'] = torch.empty(max(nv.lib().iunet_gn_precise_slab_bytes(N, self.ch[l], _vox(dims[l])) for l in range(self.levels)),
-                                           dtype=torch.uint8, device=self.device)
-                ws['gnsc'] = torch.empty(N * max(self.ch), dtype=torch.float32, device=self.device)
-                ws['gnsh'] = torch.empty(N * max(self.ch), dtype=torch.float32, device=self.device)
-            if len(self._ws_cache) > 4:
-                self._ws_cache.clear()
-            self._ws_cache[key] = ws
+                    ws[f'pin{l}'], ws[f'pin{l}m'] = mkh(self.ch[l - 1], v), mk8(self.ch[l - 1], v)
+                continue
+            ws[f'a{l}'] = mk(self.ch[l], v)
+            ws[f'b{l}'] = mk(self.ch[l], v)
+            if l < self.levels - 1:
+                ws[f'cat{l}'] = mk(2 * self.ch[l], v)
+            if l > 0:
+                ws[f'pin{l}'] = mk(self.ch[l - 1], v)
+        if self.norm == 'group':
+            ws['raw'] = torch.zeros(N * 2 * max(self.ch[l] * _vox(dims[l]) for l in range(self.levels)), dtype=torch.float16, device=self.device)
+            ws['gnslab'] = torch.empty(max(nv.lib().iunet_gn_precise_slab_bytes(N, self.ch[l], _vox(dims[l])) for l in range(self.levels)),
+                                       dtype=torch.uint8, device=self.device)
+            ws['gnsc'] = torch.empty(N * max(self.ch), dtype=torch.float32, device=self.device)
+            ws['gnsh'] = torch.empty(N * max(self.ch), dtype=torch.float32, device=self.device)
         return ws
 
     # ------------------------------------------------------------------ forward (inference)
@@ -301,8 +220,7 @@ class EngineX2:
         2-D net over the slices along three axes, probabilities accumulated) as one batch of 3 S slices instead of three forwards of S:
         a third of the launches, three times the work per launch at the deep levels.  Same bits as the views run one by one (the x2m
         conv keeps one summation order per voxel whatever the batch).  x2m form; other forms: the views one by one."""
-        if self.packed is None:
-            raise RuntimeError('EngineX2.load_eval() has not been called')
+        self._require_loaded()
         fuse = self.mixed and self.probe is None and self.norm == 'batch' and bool(nv.lib().iunet_x2m_head_fusable(self.ncls, self.ch[0]))
         if not fuse or len(views) == 1:
             for (x, xs, n), o in zip(views, outs):
@@ -316,8 +234,7 @@ class EngineX2:
     def infer(self, x, x_strides, N, D, H, W, logits=None, probs=None, cls=None, out_strides=None,
               divisor=1.0, accumulate=False, features_only=False):
         """engine.Engine.infer in split precision (same arguments and output contract)."""
-        if self.packed is None:
-            raise RuntimeError('EngineX2.load_eval() has not been called')
+        self._require_loaded()
         g = self._graph()
         if g is not None and not features_only and self.probe is None:
             # the whole forward as one C call (csrc/net.hip: the same launches on the same operators, sequenced in C++)
@@ -382,11 +299,8 @@ class EngineX2:
     def _head(self, ws, N, D, H, W, logits, probs, cls, out_strides, divisor, accumulate, s):
         dims, ch = ws['dims'], self.ch
         hw, hb = self.packed['head']
-        if out_strides is None:
-            v = _vox(dims[0])
-            out_strides = (self.ncls * v, v, H * W, W, 1)
         nv.call('iunet_x2_head_fwd', nv.ptr(ws['b0']), 2 * ch[0] * _vox(dims[0]), ch[0] // 8, ch[0], nv.ptr(hw), nv.ptr(hb),
-                self.act_scale, self.ncls, nv.ptr(logits), nv.ptr(probs), nv.ptr(cls), nv.ll_array(out_strides),
+                self.act_scale, self.ncls, nv.ptr(logits), nv.ptr(probs), nv.ptr(cls), nv.ll_array(self._out_strides(out_strides, D, H, W)),
                 float(divisor), int(bool(accumulate)), N, D, H, W, s)
 
     def _conv3m(self, name, xp, x_ss, x8p, x8_ss, yp, y_ss, y_lo, y8p, y8_ss, N, d, ci, co, s, pool=None):
@@ -491,7 +405,7 @@ class EngineX2:
                 hl = [dict(zip(('logits', 'probs', 'cls', 'out_strides', 'divisor', 'accumulate'), head))] if heads is None else heads
                 n0 = 0
                 for (_, _, vn), o in zip(views, hl):          # the last conv, head in its epilogue, per view: that view's output strides
-                    out_strides = o.get('out_strides') or (self.ncls * v, v, H * W, W, 1)
+                    out_strides = self._out_strides(o.get('out_strides'), D, H, W)
                     nv.call('iunet_x2m_conv_head_fwd', self.dim, ctypes.c_void_p(ws['a0'].data_ptr() + n0 * c * v * 2), c * v,
                             ctypes.c_void_p(ws['a0m'].data_ptr() + n0 * c * v), c * v, nv.ptr(w16), nv.ptr(w8), nv.ptr(osc),
                             nv.ptr(b), nv.ptr(hw), nv.ptr(hb), self.act_scale, self.ncls, nv.ptr(o.get('logits')), nv.ptr(o.get('probs')),

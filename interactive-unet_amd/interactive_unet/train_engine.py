@@ -14,17 +14,102 @@ import os
 import torch
 
 from . import _native as nv
-from .engine import BN_EPS, check_spatial
+from . import topology
+from .engine import BN_EPS
+from .topology import _vox, check_spatial
 
 LOSS_KINDS = {'ce': 0, 'dice': 1, 'iou': 2, 'mcc': 3, 'dice_ce': 4, 'iou_ce': 5, 'mcc_ce': 6}
 BN_MOMENTUM = 0.1
 
 
-def _vox(d):
-    return d[0] * d[1] * d[2]
+def metrics(out4, sync):
+    """What a step returns: the device tensor [Loss, Dice, IoU, MCC] (overwritten by the next step: clone to keep) or, sync, its values
+    (a host read)."""
+    if not sync:
+        return out4
+    o = out4.tolist()
+    return {'Loss': o[0], 'Dice': o[1], 'IoU': o[2], 'MCC': o[3]}
 
 
-class TrainEngine:
+class TrainEngineBase:
+    """What every training engine is on the host side, whatever its numeric form or architecture: the network's shape (topology.py), the
+    flat fp32 master parameters with their gradient and AdamW moments, the steps' input preparation and the version check that re-packs
+    the operators after someone else moved the weights.  A subclass has `repack()`."""
+
+    def _flatten(self):
+        """Re-home every trainable parameter as a view of one flat fp32 master tensor
+        (single AdamW launch, single all-reduce); gradients get the same layout."""
+        m = self.model
+        names = [n for n in m._names if not (n.endswith('running_mean') or n.endswith('running_var'))]
+        sizes = [m.tensor(n).numel() for n in names]
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=self.dev)
+        off, self.offsets = 0, {}
+        for n, s in zip(names, sizes):
+            t = m.tensor(n)
+            flat[off:off + s].copy_(t.detach().reshape(-1))
+            t.data = flat[off:off + s].view(t.shape)
+            self.offsets[n] = (off, s)
+            off += s
+        self.flat, self.names = flat, names
+        self.grad, self.m, self.v = torch.zeros_like(flat), torch.zeros_like(flat), torch.zeros_like(flat)
+
+    def _bucket_bounds(self, first_dec):
+        """The data-parallel all-reduce's bucket boundaries in the flat order (encoder, decoder, head): `first_dec`, the decoder's first
+        parameter, starts the tail bucket; the bottom encoder level's parameters (its two convs hold almost half of the net) are a bucket
+        of their own, reduced while the upper encoder levels still run their backward -- only if they are one run that ends where the
+        decoder starts."""
+        self._dec_start = self.offsets[first_dec][0] if first_dec in self.offsets else 0
+        bottom = [self.offsets[n] for n in self.names if n.startswith(f'enc{self.levels - 1}.')]
+        lo = min((o for o, _ in bottom), default=0)
+        self._bottom_start = lo if bottom and lo + sum(s for _, s in bottom) == self._dec_start else None
+
+    def p(self, name):
+        return self.model.tensor(name)
+
+    def g(self, name):
+        off, s = self.offsets[name]
+        return self.grad[off:off + s]
+
+    def stage_names(self):
+        return topology.stage_names(self.levels)
+
+    def stage_io(self, prefix):
+        return topology.stage_io(prefix, self.cin, self.ch)
+
+    def up_convs(self):
+        return topology.up_convs(self.levels)
+
+    def _prep(self, X, y, w, convert_x=True):
+        """-> (X, y, w, N, D, H, W, voxels, X's strides) on the device; convert_x: X in a dtype the first conv reads."""
+        X = X.to(self.dev).contiguous()
+        y = y.to(self.dev).contiguous()
+        w = None if w is None else w.to(self.dev).contiguous()
+        if y.dtype not in (torch.float16, torch.float32):
+            y = y.float()
+        N = X.shape[0]
+        sp = tuple(X.shape[2:])
+        D, H, W = sp if self.dim == 3 else (1,) + sp
+        vox = D * H * W
+        if convert_x and X.dtype not in nv.IN_DTYPE_CODE:
+            X = X.float()
+        return X, y, w, N, D, H, W, vox, (self.cin * vox, vox, H * W, W, 1)
+
+    def _repack_more(self):
+        """sync_weights: what holds packed operators beside repack()'s."""
+
+    def sync_weights(self):
+        """Re-pack the operators when something other than optimizer_step changed the parameters (an external optimiser stepping
+        the module's parameters -- UNet.configure_optimizers -- or load_state_dict): torch's version counters tell."""
+        ver = sum(self.p(n)._version for n in self.names)
+        if ver != getattr(self, '_seen_version', None):
+            if getattr(self, '_seen_version', None) is not None:
+                self.repack()
+                self._repack_more()
+                self.model._packed_sig = None
+            self._seen_version = ver
+
+
+class TrainEngine(TrainEngineBase):
     def __init__(self, model, lr=None, loss_kind='mcc_ce', betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
                  loss_scale=None, process_group=None):
         self.model = model
@@ -32,7 +117,7 @@ class TrainEngine:
         if self.dev.type != 'cuda':
             raise RuntimeError('native training runs on the GPU only (no CPU fallback)')
         nv.lib()
-        self.dim, self.levels, self.ch = model.dim, model.levels, [model.base * 2 ** l for l in range(model.levels)]
+        self.dim, self.levels, self.ch = model.dim, model.levels, topology.channels(model.base, model.levels)
         self.cin, self.ncls = model.num_channels, model.num_classes
         self.T = model.act_dtype
         if self.T not in nv.DTYPE_CODE:
@@ -78,6 +163,7 @@ class TrainEngine:
                         and bool(nv.lib().iunet_head_bn_bwd_ok(self.ch[0], self.ncls)))
         self._bw_ready = {}
         self._flatten()
+        self._bucket_bounds(self._first_decoder_param())
         if self.pg is not None:
             # every rank continues from rank 0's weights and BatchNorm statistics (each rank's module drew its own
             # initialisation, or read a checkpoint that rank 0 is about to replace)
@@ -116,55 +202,8 @@ class TrainEngine:
         return int(self.state.view(torch.int32)[3].item()) == 0
 
     # ------------------------------------------------------------------ parameters
-    def _flatten(self):
-        """Re-home every trainable parameter as a view of one flat fp32 master tensor
-        (single AdamW launch, single all-reduce); gradients get the same layout."""
-        m = self.model
-        names = [n for n in m._names if not (n.endswith('running_mean') or n.endswith('running_var'))]
-        sizes = [m.tensor(n).numel() for n in names]
-        total = sum(sizes)
-        flat = torch.empty(total, dtype=torch.float32, device=self.dev)
-        off = 0
-        self.offsets = {}
-        for n, s in zip(names, sizes):
-            t = m.tensor(n)
-            flat[off:off + s].copy_(t.detach().reshape(-1))
-            t.data = flat[off:off + s].view(t.shape)
-            self.offsets[n] = (off, s)
-            off += s
-        self.flat = flat
-        self.grad = torch.zeros_like(flat)
-        self.m = torch.zeros_like(flat)
-        self.v = torch.zeros_like(flat)
-        self.names = names
-        # first element of the decoder + head parameters (they follow the encoder in the flat order): bucket boundary of
-        # the data-parallel all-reduce
-        first_dec = f'dec{self.levels - 2}.up.weight'
-        self._dec_start = self.offsets[first_dec][0] if first_dec in self.offsets else 0
-        # the bottom encoder level's parameters (its two convs hold almost half of the net): a bucket of their own, reduced while
-        # the upper encoder levels still run their backward -- only if they are one run that ends where the decoder starts
-        bottom = [self.offsets[n] for n in names if n.startswith(f'enc{self.levels - 1}.')]
-        lo = min((o for o, _ in bottom), default=0)
-        self._bottom_start = lo if bottom and lo + sum(s for _, s in bottom) == self._dec_start else None
-
-    def p(self, name):
-        return self.model.tensor(name)
-
-    def g(self, name):
-        off, s = self.offsets[name]
-        return self.grad[off:off + s]
-
-    def stage_names(self):
-        return [f'enc{l}' for l in range(self.levels)] + [f'dec{l}' for l in range(self.levels - 2, -1, -1)]
-
-    def stage_io(self, prefix):
-        l = int(prefix[3:])
-        ci = (self.cin if l == 0 else self.ch[l - 1]) if prefix.startswith('enc') else 2 * self.ch[l]
-        return ci, self.ch[l], l
-
-    def up_convs(self):
-        """(prefix, level l) of every transposed conv ch[l+1] -> ch[l], in parameter order."""
-        return [(f'dec{l}', l) for l in range(self.levels - 2, -1, -1)]
+    def _first_decoder_param(self):
+        return f'dec{self.levels - 2}.up.weight'
 
     def _alloc_packed(self):
         self.pk = {}
@@ -222,7 +261,7 @@ class TrainEngine:
             return ws
         check_spatial(self.dim, self.levels, D, H, W)
         L, ch = self.levels, self.ch
-        dims = [((D >> l) if self.dim == 3 else 1, H >> l, W >> l) for l in range(L)]
+        dims = topology.level_dims(self.dim, L, D, H, W)
         act = lambda c, v: torch.empty(N * c * v, dtype=self.T, device=self.dev)
         f32 = lambda n: torch.empty(n, dtype=torch.float32, device=self.dev)
         lib = nv.lib()
@@ -617,20 +656,6 @@ class TrainEngine:
         self.model._packed_sig = None          # weights changed behind torch's version counters
 
     # ------------------------------------------------------------------ public steps
-    def _prep(self, X, y, w):
-        X = X.to(self.dev).contiguous()
-        y = y.to(self.dev).contiguous()
-        w = None if w is None else w.to(self.dev).contiguous()
-        if y.dtype not in (torch.float16, torch.float32):
-            y = y.float()
-        N = X.shape[0]
-        sp = tuple(X.shape[2:])
-        D, H, W = sp if self.dim == 3 else (1,) + sp
-        vox = D * H * W
-        if X.dtype not in nv.IN_DTYPE_CODE:
-            X = X.float()
-        return X, y, w, N, D, H, W, vox, (self.cin * vox, vox, H * W, W, 1)
-
     def train_step(self, X, y, w=None, sync=True):
         """One optimisation step (unet.py:88-102 + backward + AdamW).  X [N,C,*sp], y / w
         [N,ncls,*sp] (fp16 or fp32, the loader's contract loader.py:142-154)."""
@@ -658,10 +683,7 @@ class TrainEngine:
             self.backward(ws, X, xs, y, w, tdt, N)
             self.optimizer_step()
             out4 = ws['out4']
-        if sync:
-            o = out4.tolist()
-            return {'Loss': o[0], 'Dice': o[1], 'IoU': o[2], 'MCC': o[3]}
-        return out4
+        return metrics(out4, sync)
 
     def _handle(self):
         """The C++-sequenced step (TrainHandle over iunet_train_*), or None where it does not apply: a timing probe attached,
@@ -702,17 +724,9 @@ class TrainEngine:
             self._eval_sig = sig                                 # runs from its second batch as one C call per batch (net_graph)
         return self._eval_eng
 
-    def sync_weights(self):
-        """Re-pack the operators when something other than optimizer_step changed the parameters (an external optimiser stepping
-        the module's parameters -- UNet.configure_optimizers -- or load_state_dict): torch's version counters tell."""
-        ver = sum(self.p(n)._version for n in self.names)
-        if ver != getattr(self, '_seen_version', None):
-            if getattr(self, '_seen_version', None) is not None:
-                self.repack()
-                if getattr(self, '_h', None) is not None:
-                    self._h.repack()
-                self.model._packed_sig = None
-            self._seen_version = ver
+    def _repack_more(self):
+        if getattr(self, '_h', None) is not None:
+            self._h.repack()
 
     def step_forward(self, X, y, w=None):
         """Forward half of a training step (unet.py:88-102): -> (out4 = [Loss, Dice, IoU, MCC] device tensor, state for
@@ -767,18 +781,11 @@ class TrainEngine:
             tdt = {torch.float32: 0, torch.float16: 1}[y.dtype]
             if w is not None and w.dtype != y.dtype:
                 w = w.to(y.dtype)
-            out4 = g.eval_step(X, xs, N, D, H, W, y, w, tdt, self.kind)
-            if not sync:
-                return out4
-            o = out4.tolist()
-            return {'Loss': o[0], 'Dice': o[1], 'IoU': o[2], 'MCC': o[3]}
+            return metrics(g.eval_step(X, xs, N, D, H, W, y, w, tdt, self.kind), sync)
         feat = eng.infer(X, xs, N, D, H, W, features_only=True)
         ws = self.workspace(N, D, H, W)
         self.loss_forward(ws, feat, y, w, N, vox)
-        if not sync:
-            return ws['out4']                 # device tensor [loss, dice, iou, mcc], overwritten by the next step: clone to keep
-        o = ws['out4'].tolist()
-        return {'Loss': o[0], 'Dice': o[1], 'IoU': o[2], 'MCC': o[3]}
+        return metrics(ws['out4'], sync)
 
 
 
@@ -803,7 +810,7 @@ class EncoderTrainEngine(TrainEngine):
         super().__init__(model, lr=lr, loss_kind=loss_kind, betas=betas, eps=eps, weight_decay=weight_decay, loss_scale=loss_scale)
 
     def stage_names(self):
-        return [f'enc{l}' for l in range(self.levels)]
+        return topology.encoder_names(self.levels)
 
     def up_convs(self):
         return []
@@ -835,7 +842,7 @@ class EncoderTrainEngine(TrainEngine):
             return ws
         check_spatial(self.dim, self.levels, D, H, W)
         L, ch, lib = self.levels, self.ch, nv.lib()
-        dims = [((D >> l) if self.dim == 3 else 1, H >> l, W >> l) for l in range(L)]
+        dims = topology.level_dims(self.dim, L, D, H, W)
         ws = {'dims': dims}
         mx = {'stats': 0, 'wslab': 0, 'bn': 0, 'dy': 0, 'coef': max(ch)}
         for l in range(L):
@@ -970,10 +977,7 @@ class CoarseTrainEngine(EncoderTrainEngine):
         lc = self._eval_engine().coarse_logits(X, xs, N, D, H, W)
         ws = self.workspace(N, D, H, W)
         self._up_loss(ws, lc, y, w, N)
-        if not sync:
-            return ws['out4']
-        o = ws['out4'].tolist()
-        return {'Loss': o[0], 'Dice': o[1], 'IoU': o[2], 'MCC': o[3]}
+        return metrics(ws['out4'], sync)
 
 _HOOK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int)       # iunet_train_hook
 

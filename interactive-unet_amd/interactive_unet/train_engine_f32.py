@@ -18,13 +18,14 @@ import ctypes
 import torch
 
 from . import _native as nv
+from . import topology
 from .engine import BN_EPS, _vox, check_spatial
-from .train_engine import LOSS_KINDS
+from .train_engine import LOSS_KINDS, TrainEngineBase, metrics
 
 BN_MOMENTUM = 0.1
 
 
-class TrainEngineF32:
+class TrainEngineF32(TrainEngineBase):
     T = torch.float32
     loss_scale = 1.0
 
@@ -36,7 +37,7 @@ class TrainEngineF32:
         if getattr(model, 'norm', 'batch') != 'batch' or getattr(model, 'weight_dtype', None):
             raise NotImplementedError('the fp32 training form covers the BatchNorm network with unquantised weights')
         nv.lib()
-        self.dim, self.levels, self.ch = model.dim, model.levels, [model.base * 2 ** l for l in range(model.levels)]
+        self.dim, self.levels, self.ch = model.dim, model.levels, topology.channels(model.base, model.levels)
         self.cin, self.ncls = model.num_channels, model.num_classes
         self.taps, self.npos = 3 ** self.dim, 2 ** self.dim
         self.lr = model.lr if lr is None else lr
@@ -53,37 +54,6 @@ class TrainEngineF32:
         self._eval_eng = None
         self.repack()
         model._packed_sig = None
-
-    # ------------------------------------------------------------------ parameters (train_engine.TrainEngine._flatten)
-    def _flatten(self):
-        m = self.model
-        names = [n for n in m._names if not (n.endswith('running_mean') or n.endswith('running_var'))]
-        sizes = [m.tensor(n).numel() for n in names]
-        flat = torch.empty(sum(sizes), dtype=torch.float32, device=self.dev)
-        off, self.offsets = 0, {}
-        for n, s in zip(names, sizes):
-            t = m.tensor(n)
-            flat[off:off + s].copy_(t.detach().reshape(-1))
-            t.data = flat[off:off + s].view(t.shape)
-            self.offsets[n] = (off, s)
-            off += s
-        self.flat, self.names = flat, names
-        self.grad, self.m, self.v = torch.zeros_like(flat), torch.zeros_like(flat), torch.zeros_like(flat)
-
-    def p(self, name):
-        return self.model.tensor(name)
-
-    def g(self, name):
-        off, s = self.offsets[name]
-        return self.grad[off:off + s]
-
-    def stage_names(self):
-        return [f'enc{l}' for l in range(self.levels)] + [f'dec{l}' for l in range(self.levels - 2, -1, -1)]
-
-    def stage_io(self, prefix):
-        l = int(prefix[3:])
-        ci = (self.cin if l == 0 else self.ch[l - 1]) if prefix.startswith('enc') else 2 * self.ch[l]
-        return ci, self.ch[l], l
 
     # ------------------------------------------------------------------ operators
     def _pack(self, key, w, cout, cin, taps, transposed=0):
@@ -128,7 +98,7 @@ class TrainEngineF32:
             return ws
         check_spatial(self.dim, self.levels, D, H, W)
         L, ch = self.levels, self.ch
-        dims = [((D >> l) if self.dim == 3 else 1, H >> l, W >> l) for l in range(L)]
+        dims = topology.level_dims(self.dim, L, D, H, W)
         f32 = lambda n: torch.empty(int(n), dtype=torch.float32, device=self.dev)
         ws = {'dims': dims}
         big = 0
@@ -316,28 +286,9 @@ class TrainEngineF32:
         self.model._packed_sig = None
 
     # ------------------------------------------------------------------ public steps (train_engine.TrainEngine's surface)
-    def sync_weights(self):
-        ver = sum(self.p(n)._version for n in self.names)
-        if ver != getattr(self, '_seen_version', None):
-            if getattr(self, '_seen_version', None) is not None:
-                self.repack()
-                self.model._packed_sig = None
-            self._seen_version = ver
-
-    def _prep(self, X, y, w):
-        X = X.to(self.dev).contiguous()
-        y = y.to(self.dev).contiguous()
-        w = None if w is None else w.to(self.dev).contiguous()
-        if y.dtype not in (torch.float16, torch.float32):
-            y = y.float()
-        N = X.shape[0]
-        sp = tuple(X.shape[2:])
-        D, H, W = sp if self.dim == 3 else (1,) + sp
-        return X, y, w, N, D, H, W, D * H * W
-
     def step_forward(self, X, y, w=None):
         self.sync_weights()
-        X, y, w, N, D, H, W, vox = self._prep(X, y, w)
+        X, y, w, N, D, H, W, vox, _ = self._prep(X, y, w, convert_x=False)      # (forward_train converts X itself)
         ws = self.forward_train(X, N, D, H, W)
         tdt, w = self.loss_forward(ws, ws['b0'], y, w, N, vox)
         return ws['out4'], (ws, y, w, tdt, N)
@@ -357,28 +308,20 @@ class TrainEngineF32:
         ws, y, w, tdt, N = state
         self.backward(ws, y, w, tdt, N)
         self.optimizer_step()
-        if sync:
-            o = out4.tolist()
-            return {'Loss': o[0], 'Dice': o[1], 'IoU': o[2], 'MCC': o[3]}
-        return out4
+        return metrics(out4, sync)
 
     def eval_step(self, X, y, w=None, sync=True):
         """validation_step (unet.py:104-116): eval-mode BatchNorm (running statistics), fp32 forward (engine_f32.EngineF32)"""
         self.sync_weights()
-        X, y, w, N, D, H, W, vox = self._prep(X, y, w)
-        if X.dtype not in nv.IN_DTYPE_CODE:
-            X = X.float()
+        X, y, w, N, D, H, W, vox, xs = self._prep(X, y, w)
         if self._eval_eng is None:
             from .engine_f32 import EngineF32
             self._eval_eng = EngineF32(self.dim, self.levels, self.model.base, self.cin, self.ncls, self.dev)
         self._eval_eng.load_eval(self.model.named_tensors())
-        feat = self._eval_eng.infer(X, (self.cin * vox, vox, H * W, W, 1), N, D, H, W, features_only=True)
+        feat = self._eval_eng.infer(X, xs, N, D, H, W, features_only=True)
         ws = self.workspace(N, D, H, W)
         self.loss_forward(ws, feat, y, w, N, vox)
-        if not sync:
-            return ws['out4']                 # device tensor [loss, dice, iou, mcc], overwritten by the next step: clone to keep
-        o = ws['out4'].tolist()
-        return {'Loss': o[0], 'Dice': o[1], 'IoU': o[2], 'MCC': o[3]}
+        return metrics(ws['out4'], sync)
 
 
 def make_train_engine(model, **kw):

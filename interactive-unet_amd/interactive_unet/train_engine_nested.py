@@ -21,6 +21,7 @@ import ctypes
 import torch
 
 from . import _native as nv
+from . import topology
 from .engine import check_spatial
 from .train_engine import TrainEngine, _vox
 from .unet import nested_nodes
@@ -40,27 +41,15 @@ class NestedTrainEngine(TrainEngine):
         super().__init__(model, lr=lr, loss_kind=loss_kind, betas=betas, eps=eps, weight_decay=weight_decay, loss_scale=loss_scale,
                          process_group=process_group)
 
-    def _flatten(self):
-        super()._flatten()
-        # the data-parallel buckets: every node + the head (the tail from dec0_1, the first node), the bottom encoder level before it
-        self._dec_start = self.offsets['dec0_1.up.weight'][0]
-        bottom = [self.offsets[n] for n in self.names if n.startswith(f'enc{self.levels - 1}.')]
-        lo = min(o for o, _ in bottom)
-        self._bottom_start = lo if lo + sum(s for _, s in bottom) == self._dec_start else None
+    def _first_decoder_param(self):
+        return 'dec0_1.up.weight'       # the first node: every node + the head are the data-parallel tail bucket, enc{L-1} the bottom one
 
     # ------------------------------------------------------------------ graph
     def stage_names(self):
-        return [f'enc{l}' for l in range(self.levels)] + [f'dec{i}_{j}' for i, j in self.nodes]
-
-    def stage_io(self, prefix):
-        if prefix.startswith('enc'):
-            l = int(prefix[3:])
-            return (self.cin if l == 0 else self.ch[l - 1]), self.ch[l], l
-        i, j = (int(t) for t in prefix[3:].split('_'))
-        return (j + 1) * self.ch[i], self.ch[i], i
+        return topology.nested_stage_names(self.levels)
 
     def up_convs(self):
-        return [(f'dec{i}_{j}', i) for i, j in self.nodes]
+        return topology.nested_up_convs(self.levels)
 
     # ------------------------------------------------------------------ workspace
     def workspace(self, N, D, H, W):
@@ -70,7 +59,7 @@ class NestedTrainEngine(TrainEngine):
             return ws
         check_spatial(self.dim, self.levels, D, H, W)
         L, ch, lib = self.levels, self.ch, nv.lib()
-        dims = [((D >> l) if self.dim == 3 else 1, H >> l, W >> l) for l in range(L)]
+        dims = topology.level_dims(self.dim, L, D, H, W)
         act = lambda c, v: torch.empty(N * c * v, dtype=self.T, device=self.dev)
         f32 = lambda n: torch.empty(n, dtype=torch.float32, device=self.dev)
         ws = {'dims': dims}
