@@ -868,6 +868,33 @@ int iunet_sf_adjoint(int dtype, int nd, const void* u, long long u_ss, int Dt, i
 int iunet_sf_param_grads(int L, int C, const int* ch, const void* wf, const void* const* w, const void* const* b, const void* G, const void* rs,
                          int N, void* const* dw, void* const* db, void* dwf, void* stream);
 
+/* ---- UPerNet decoder (csrc/upernet.hip; unet.param_shapes(..., architecture='UPerNet')): the kernels that move data between grids.  Its
+ * convs run on the iunet_dl_* entry points.  Tensors: NHWC8c (dtype 0 f16 / 1 bf16) or planar fp32 [N][C][vox] (dtype 2), sample strides in
+ * elements; a channel slot of a wider tensor is the pointer offset c * vox (c a multiple of 8) with the wider tensor's sample stride.
+ * Sums are fp32 in a fixed order with one rounding: a repeated call is bit-equal. */
+/* dst = [base +] R(act(src)): linear resampling (F.interpolate, align_corners=False: 4 taps in 2-D, 8 in 3-D) from the grid Ds Hs Ws to
+ * Dt Ht Wt, any pair of sizes.  scale / shift (both or neither): src is read through relu(scale[c] x + shift[c]) with iunet_bn_relu_fwd's
+ * bits.  base (or NULL): a tensor on the target grid added to the sum -- as stored, or through relu(base_scale[c] y + base_shift[c]) where
+ * the pair is given.  base may be dst itself. */
+int iunet_pn_resize(int dtype, int nd, const void* src, long long src_ss, int Ds, int Hs, int Ws, const void* scale, const void* shift,
+                    const void* base, long long base_ss, const void* base_scale, const void* base_shift, void* dst, long long dst_ss, int Dt,
+                    int Ht, int Wt, int C, int N, void* stream);
+/* dx = [dx +] R^T(u): u on the target grid Dt Ht Wt, dx on the source grid Ds Hs Ws; accumulate 1 adds to what dx holds (fp32 sum, one
+ * rounding).  dtype 0 / 1. */
+int iunet_pn_resize_adjoint(int dtype, int nd, const void* u, long long u_ss, int Dt, int Ht, int Wt, void* dx, long long dx_ss, int Ds, int Hs,
+                            int Ws, int C, int N, int accumulate, void* stream);
+/* the four adaptive average pools of x (F.adaptive_avg_pool{2,3}d to s bins per spatial axis, s = 1, 2, 3, 6) in one launch: out[k] on the
+ * grid s^nd (2-D: 1 x s x s) with sample stride out_ss[k].  dtype 0 / 1 / 2. */
+int iunet_pn_pool(int dtype, int nd, const void* x, long long x_ss, int D, int H, int W, void* const* out, const long long* out_ss, int C, int N,
+                  void* stream);
+/* dx = du + the sum over the four sizes of pool_s^T(da[k]) (du: a gradient on x's grid, or NULL); dtype 0 / 1 */
+int iunet_pn_pool_bwd(int dtype, int nd, const void* du, long long du_ss, const void* const* da, const long long* da_ss, void* dx, long long dx_ss,
+                      int D, int H, int W, int C, int N, void* stream);
+/* backward of q = relu(y + bias[c]) (the 1-bin branch has no norm): dy = dz where the stored q is positive, dbias[c] = the sum of dy (fp32,
+ * overwritten); dtype 0 / 1 */
+int iunet_pn_bias_relu_bwd(int dtype, const void* dz, long long dz_ss, const void* y, long long y_ss, const void* bias, void* dy, long long dy_ss,
+                           void* dbias, int C, int N, long long vox, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,8 +4,8 @@
 the native canonical U-Net (engine.py) instead of segmentation_models_pytorch.
 
 architecture='U-Net', 'U-Net++' (the canonical nested form: engine_nested.py, train_engine_nested.py), 'LinkNet' (engine_linknet.py,
-train_engine_linknet.py), 'DeepLabV3' (engine_deeplab.py, train_engine_deeplab.py) and 'Segformer' (engine_segformer.py,
-train_engine_segformer.py) exist natively;
+train_engine_linknet.py), 'DeepLabV3' (engine_deeplab.py, train_engine_deeplab.py), 'Segformer' (engine_segformer.py,
+train_engine_segformer.py) and 'UPerNet' (engine_upernet.py, train_engine_upernet.py) exist natively;
 `encoder_name` is accepted and ignored (the canonical nets have their own plain conv encoder), `pretrained` is a no-op with a warning (no imagenet
 weights for a from-scratch encoder; no network access).  Extra keyword arguments (dim, levels,
 base, act_dtype, infer_dtype) select the 3-D / wider variants of BASELINE.json's configs.
@@ -42,7 +42,8 @@ NESTED = 'U-Net++'
 LINKNET = 'LinkNet'
 DEEPLAB = 'DeepLabV3'
 SEGFORMER = 'Segformer'
-ARCHITECTURES = ('U-Net', NESTED, LINKNET, DEEPLAB, SEGFORMER)
+UPERNET = 'UPerNet'
+ARCHITECTURES = ('U-Net', NESTED, LINKNET, DEEPLAB, SEGFORMER, UPERNET)
 
 
 def nested_nodes(levels):
@@ -60,7 +61,10 @@ def param_shapes(dim=2, levels=4, base=32, cin=1, ncls=2, architecture='U-Net', 
     3^d, aspp.pool 1x1 after the global mean, aspp.project 1x1 over the 5 C concat; C = decoder_channels), dec.conv 3^d C -> C, each conv
     without bias and with a BatchNorm `<prefix>.bn`, then the head C -> ncls.  architecture='Segformer': the encoder, then mlp{l} (nn.Linear
     ch[l] -> C, weight [C, ch[l]], bias [C]) for l = 0 .. L-1, fuse (conv 1x1 L C -> C without bias over the deepest-first concat, BatchNorm
-    `fuse.bn`), then the head C -> ncls; C = decoder_channels."""
+    `fuse.bn`), then the head C -> ncls; C = decoder_channels.  architecture='UPerNet' (B = L-1, Cq = ch[B] / 4): the encoder, then the pyramid
+    pooling branches psp.b1 (conv 1x1 ch[B] -> Cq WITH bias, no norm: one value per channel), psp.b2 / psp.b3 / psp.b6 (conv 1x1 without
+    bias, BatchNorm), psp.out (conv 3^d 2 ch[B] -> C, BatchNorm), the laterals lat{l} (conv 1x1 ch[l] -> C, BatchNorm) for l = B-1 .. 2,
+    fuse (conv 3^d (L-2) C -> C over the deepest-first concat, BatchNorm), then the head C -> ncls."""
     if architecture not in ARCHITECTURES:
         raise NotImplementedError(f'architecture {architecture!r}: the native networks are {ARCHITECTURES}')
     ch = [base * 2 ** l for l in range(levels)]
@@ -82,6 +86,20 @@ def param_shapes(dim=2, levels=4, base=32, cin=1, ncls=2, architecture='U-Net', 
         shapes['fuse.conv.weight'] = (C, levels * C) + k1
         for k in ('weight', 'bias', 'running_mean', 'running_var'):
             shapes[f'fuse.bn.{k}'] = (C,)
+        shapes['head.weight'] = (ncls, C) + k1
+        shapes['head.bias'] = (ncls,)
+        return shapes
+    if architecture == UPERNET:
+        C, Cb = decoder_channels, ch[-1]
+        convs = [(f'psp.b{s}', (Cb // 4, Cb) + k1) for s in (1, 2, 3, 6)] + [('psp.out', (C, 2 * Cb) + k3)]
+        convs += [(f'lat{l}', (C, ch[l]) + k1) for l in range(levels - 2, 1, -1)] + [('fuse', (C, (levels - 2) * C) + k3)]
+        for prefix, shp in convs:
+            shapes[f'{prefix}.conv.weight'] = shp
+            if prefix == 'psp.b1':
+                shapes[f'{prefix}.conv.bias'] = (shp[0],)
+                continue
+            for k in ('weight', 'bias', 'running_mean', 'running_var'):
+                shapes[f'{prefix}.bn.{k}'] = (shp[0],)
         shapes['head.weight'] = (ncls, C) + k1
         shapes['head.bias'] = (ncls,)
         return shapes
@@ -135,6 +153,9 @@ NATIVE = {
                     engines=('engine_segformer', 'SegformerEngine', 'SegformerEngineF32',
                              lambda m: dict(decoder_channels=m.decoder_segmentation_channels)),
                     train=('train_engine_segformer', 'SegformerTrainEngine')),
+    UPERNET: dict(levels=(4, 6), shape=True, width='decoder_channels', aspp=False,
+                  engines=('engine_upernet', 'UPerNetEngine', 'UPerNetEngineF32', lambda m: dict(decoder_channels=m.decoder_channels)),
+                  train=('train_engine_upernet', 'UPerNetTrainEngine')),
 }
 
 
@@ -235,8 +256,8 @@ class UNet(nn.Module):
                  decoder_segmentation_channels=256):
         super().__init__()
         if architecture not in ARCHITECTURES:
-            raise NotImplementedError(f"architecture {architecture!r}: only 'U-Net', 'U-Net++', 'LinkNet', 'DeepLabV3' and 'Segformer' have a native MI355X "
-                                      f"implementation (the reference builds the others through smp, unet.py:33-54)")
+            raise NotImplementedError(f"architecture {architecture!r}: only 'U-Net', 'U-Net++', 'LinkNet', 'DeepLabV3', 'Segformer' and 'UPerNet' have a native "
+                                      f"MI355X implementation (the reference builds the others through smp, unet.py:33-54)")
         if architecture in NATIVE:
             _check_native(architecture, levels, base, num_channels, num_classes, act_dtype, weight_dtype, norm, infer_dtype, infer_policy,
                           decoder_channels=decoder_channels, decoder_atrous_rates=decoder_atrous_rates,
@@ -257,6 +278,9 @@ class UNet(nn.Module):
             self.decoder_aspp_dropout = float(decoder_aspp_dropout)
             self.hparams.update(decoder_channels=decoder_channels, decoder_atrous_rates=list(self.decoder_atrous_rates),
                                 decoder_aspp_dropout=self.decoder_aspp_dropout)
+        if architecture == UPERNET:         # (only DeepLabV3 and UPerNet modules carry the decoder width)
+            self.decoder_channels = decoder_channels
+            self.hparams.update(decoder_channels=decoder_channels)
         self.decoder_segmentation_channels = None
         if architecture == SEGFORMER:       # (only Segformer modules carry it)
             self.decoder_segmentation_channels = decoder_segmentation_channels
@@ -291,7 +315,7 @@ class UNet(nn.Module):
         self.norm, self.groups = norm, groups
         self._names = []
         for name, shp in param_shapes(dim, levels, base, num_channels, num_classes, architecture,
-                                      decoder_channels if architecture == DEEPLAB else
+                                      decoder_channels if architecture in (DEEPLAB, UPERNET) else
                                       decoder_segmentation_channels if architecture == SEGFORMER else 256).items():
             t = torch.empty(shp, dtype=torch.float32)
             key = name.replace('.', '__')
