@@ -830,7 +830,8 @@ int iunet_dl_up_head(int nd, const void* lc, int ncls, int Dc, int Hc, int Wc, i
                      const long long* out_strides, float divisor, int accumulate, int N, void* stream);
 /* training: the upsampled logits' softmax + loss sums + loss / metrics / coefficients (iunet_head_loss_fwd's out4 / coef); the backward
  * writes the fine dlogits (dfine, N ncls vox floats), then the interpolation's adjoint as a gather into dcoarse (tmp: N ncls Df Hf Wc floats);
- * lscale: the device loss scale */
+ * lscale: the device loss scale.  After the call dfine still holds the fine dlogits in 2-D; in 3-D the adjoint's H pass has written its
+ * output over the first N ncls Df Hc Wc floats of dfine (the rest is the fine dlogits still) */
 int iunet_dl_up_loss_num_parts(int N, long long vox);
 int iunet_dl_up_loss_fwd(int nd, const void* lc, int ncls, int Dc, int Hc, int Wc, int s, const void* target, const void* weight, int tdtype,
                          int kind, void* slab, void* out4, void* coef, int N, void* stream);
