@@ -896,6 +896,51 @@ int iunet_pn_pool_bwd(int dtype, int nd, const void* du, long long du_ss, const 
 int iunet_pn_bias_relu_bwd(int dtype, const void* dz, long long dz_ss, const void* y, long long y_ss, const void* bias, void* dy, long long dy_ss,
                            void* dbias, int C, int N, long long vox, void* stream);
 
+/* ---- MA-Net decoder (csrc/manet.hip): position attention on the coarsest grid and the gated nearest upsampling of a decoder block.  Tensors:
+ * NHWC8c (dtype 0 f16 / 1 bf16) or planar fp32 [N][C][vox] (dtype 2), sample strides in elements.  Sums are fp32 in a fixed order, no float
+ * atomics: a repeated call is bit-equal.  T tokens = the voxels of the grid, any number up to 65536; Cb a multiple of 128 up to 512. */
+/* Y = X + A V + bv with A = the row softmax of S[i][j] = sum_k (Kc[i][k] + bk[k]) (Q[j][k] + bq[k]) over 64 channels (no scale factor): flash
+ * style on the 16-bit MFMA, Q + bq and Kc + bk rounded to the activation type on load, P rounded to it for the second product, Y rounded
+ * once.  q, k: [T][64]; v, x, y: [T][Cb]; bq, bk [64], bv [Cb] fp32; lse: fp32 [N][T], the log of a row's sum of exp(S). */
+int iunet_ma_attn_fwd(int dtype, const void* q, long long q_ss, const void* bq, const void* k, long long k_ss, const void* bk, const void* v,
+                      long long v_ss, const void* x, long long x_ss, const void* bv, void* y, long long y_ss, void* lse, int Cb, int T, int N,
+                      void* stream);
+/* the same on planar fp32 (f32-input MFMA: fp32 products in an fma chain, P kept in fp32) */
+int iunet_ma_f32_attn_fwd(const void* q, long long q_ss, const void* bq, const void* k, long long k_ss, const void* bk, const void* v,
+                          long long v_ss, const void* x, long long x_ss, const void* bv, void* y, long long y_ss, void* lse, int Cb, int T, int N,
+                          void* stream);
+/* From dy (the gradient of Y): dq, dk [T][64] and dv [T][Cb], the gradients of Q, Kc and V; X's share is dy itself, dbq is zero (a row's
+ * softmax does not see a term that is constant along it), dbk / dbv are the column sums of dk / dy (iunet_dl_chansum).  Two launches: one owns
+ * row blocks (delta[n][i] = sum_j P dP, fp32 [N][T] workspace, then dk), one owns column blocks (dv, dq); both recompute P from q, k and lse. */
+int iunet_ma_attn_bwd(int dtype, const void* q, long long q_ss, const void* bq, const void* k, long long k_ss, const void* bk, const void* v,
+                      long long v_ss, const void* dy, long long dy_ss, const void* lse, void* delta, void* dq, long long dq_ss, void* dk,
+                      long long dk_ss, void* dv, long long dv_ss, int Cb, int T, int N, void* stream);
+/* The two squeeze-and-excitation branches of a decoder block (hl: on the mean of h, ll: on the mean of the skip; fp32 [N][C] each):
+ * z = relu(W1 mean + b1) [m], sig = sigmoid(W2 z + b2) [C], g[n][c] = sig_hl + sig_ll.  w1 [m][C], w2 [C][m].  hid: [N][2][m] (z), sig: [N][2][C],
+ * kept for the backward.  All fp32. */
+int iunet_ma_gate(const void* mean_h, const void* mean_skip, const void* w1_hl, const void* b1_hl, const void* w2_hl, const void* b2_hl,
+                  const void* w1_ll, const void* b1_ll, const void* w2_ll, const void* b2_ll, void* g, void* hid, void* sig, int C, int m, int N,
+                  void* stream);
+/* dg [N][C] -> the eight parameter gradients (overwritten; sums over the batch in sample order) and dmean_h, dmean_skip [N][C].  dhid: fp32
+ * [N][2][m] workspace. */
+int iunet_ma_gate_bwd(const void* dg, const void* mean_h, const void* mean_skip, const void* w1_hl, const void* w2_hl, const void* w1_ll,
+                      const void* w2_ll, const void* hid, const void* sig, void* dhid, void* dw1_hl, void* db1_hl, void* dw2_hl, void* db2_hl,
+                      void* dw1_ll, void* db1_ll, void* dw2_ll, void* db2_ll, void* dmean_h, void* dmean_skip, int C, int m, int N, void* stream);
+/* dst slot (on the grid 2D x 2H x 2W; 2-D: 1 x 2H x 2W) = nearest_up2(h) g[n][c], h on D x H x W read as stored or, with scale / shift (both
+ * or neither), through relu(scale[c] y + shift[c]) with iunet_bn_relu_fwd's bits; one more rounding.  dtype 0 / 1 / 2. */
+int iunet_ma_up_gate(int dtype, int nd, const void* h, long long h_ss, const void* scale, const void* shift, const void* g, void* dst,
+                     long long dst_ss, int D, int H, int W, int C, int N, void* stream);
+/* its backward from du (the slot's gradient, fine grid), dtype 0 / 1: dg[n][c] = sum du up(h) (fp32, overwritten; part: an fp32 workspace of
+ * iunet_ma_up_gate_dg_parts x N x C floats for the partial sums of the parts of the grid, added in order -- may be NULL where that is 1);
+ * dh = g (the sum of du over a voxel's 2^nd children) + dmean_h[n][c] / (D H W) (dmean_h may be NULL), the gradient of the activation h;
+ * iunet_ma_add_mean_grad: dx += dmean[n][c] / vox, the skip's share of its gate's gradient. */
+int iunet_ma_up_gate_dg_parts(int nd, int N, int D, int H, int W, int C);
+int iunet_ma_up_gate_dg(int dtype, int nd, const void* du, long long du_ss, const void* h, long long h_ss, const void* scale, const void* shift,
+                        void* part, void* dg, int D, int H, int W, int C, int N, void* stream);
+int iunet_ma_up_gate_bwd(int dtype, int nd, const void* du, long long du_ss, const void* g, const void* dmean_h, void* dh, long long dh_ss, int D,
+                         int H, int W, int C, int N, void* stream);
+int iunet_ma_add_mean_grad(int dtype, void* dx, long long dx_ss, const void* dmean, int C, int N, long long vox, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

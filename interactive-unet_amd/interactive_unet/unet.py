@@ -5,7 +5,8 @@ the native canonical U-Net (engine.py) instead of segmentation_models_pytorch.
 
 architecture='U-Net', 'U-Net++' (the canonical nested form: engine_nested.py, train_engine_nested.py), 'LinkNet' (engine_linknet.py,
 train_engine_linknet.py), 'DeepLabV3' (engine_deeplab.py, train_engine_deeplab.py), 'Segformer' (engine_segformer.py,
-train_engine_segformer.py) and 'UPerNet' (engine_upernet.py, train_engine_upernet.py) exist natively;
+train_engine_segformer.py), 'UPerNet' (engine_upernet.py, train_engine_upernet.py) and 'MA-Net' (engine_manet.py, train_engine_manet.py)
+exist natively;
 `encoder_name` is accepted and ignored (the canonical nets have their own plain conv encoder), `pretrained` is a no-op with a warning (no imagenet
 weights for a from-scratch encoder; no network access).  Extra keyword arguments (dim, levels,
 base, act_dtype, infer_dtype) select the 3-D / wider variants of BASELINE.json's configs.
@@ -43,7 +44,9 @@ LINKNET = 'LinkNet'
 DEEPLAB = 'DeepLabV3'
 SEGFORMER = 'Segformer'
 UPERNET = 'UPerNet'
-ARCHITECTURES = ('U-Net', NESTED, LINKNET, DEEPLAB, SEGFORMER, UPERNET)
+MANET = 'MA-Net'
+ARCHITECTURES = ('U-Net', NESTED, LINKNET, DEEPLAB, SEGFORMER, UPERNET, MANET)
+MANET_QK = 64          # width of MA-Net's queries and keys
 
 
 def nested_nodes(levels):
@@ -64,7 +67,11 @@ def param_shapes(dim=2, levels=4, base=32, cin=1, ncls=2, architecture='U-Net', 
     `fuse.bn`), then the head C -> ncls; C = decoder_channels.  architecture='UPerNet' (B = L-1, Cq = ch[B] / 4): the encoder, then the pyramid
     pooling branches psp.b1 (conv 1x1 ch[B] -> Cq WITH bias, no norm: one value per channel), psp.b2 / psp.b3 / psp.b6 (conv 1x1 without
     bias, BatchNorm), psp.out (conv 3^d 2 ch[B] -> C, BatchNorm), the laterals lat{l} (conv 1x1 ch[l] -> C, BatchNorm) for l = B-1 .. 2,
-    fuse (conv 3^d (L-2) C -> C over the deepest-first concat, BatchNorm), then the head C -> ncls."""
+    fuse (conv 3^d (L-2) C -> C over the deepest-first concat, BatchNorm), then the head C -> ncls.  architecture='MA-Net' (B = L-1): the
+    encoder, then the position attention block pab.top / pab.center (conv 1x1 ch[B] -> 64 WITH bias: queries, keys), pab.bottom (conv 3^d
+    ch[B] -> ch[B] WITH bias: values), pab.out (conv 3^d ch[B] -> ch[B], BatchNorm); for l = B-1 .. 0 the block dec{l}: hl3 (conv 3^d ch[l+1]
+    -> ch[l+1], BatchNorm), hl1 (conv 1x1 ch[l+1] -> ch[l], BatchNorm), the gates se_hl / se_ll (fc1 [m, ch[l]] + bias, fc2 [ch[l], m] + bias,
+    m = max(ch[l] / 16, 1)) and the stage conv{1,2} / bn{1,2} on concat(skip, gated upsampling), 2 ch[l] -> ch[l]; then the head."""
     if architecture not in ARCHITECTURES:
         raise NotImplementedError(f'architecture {architecture!r}: the native networks are {ARCHITECTURES}')
     ch = [base * 2 ** l for l in range(levels)]
@@ -103,6 +110,30 @@ def param_shapes(dim=2, levels=4, base=32, cin=1, ncls=2, architecture='U-Net', 
         shapes['head.weight'] = (ncls, C) + k1
         shapes['head.bias'] = (ncls,)
         return shapes
+    if architecture == MANET:
+        Cb = ch[-1]
+
+        def conv_bn(prefix, shp):
+            shapes[f'{prefix}.conv.weight'] = shp
+            for k in ('weight', 'bias', 'running_mean', 'running_var'):
+                shapes[f'{prefix}.bn.{k}'] = (shp[0],)
+        for prefix, shp in (('pab.top', (MANET_QK, Cb) + k1), ('pab.center', (MANET_QK, Cb) + k1), ('pab.bottom', (Cb, Cb) + k3)):
+            shapes[f'{prefix}.conv.weight'] = shp
+            shapes[f'{prefix}.conv.bias'] = (shp[0],)
+        conv_bn('pab.out', (Cb, Cb) + k3)
+        for l in range(levels - 2, -1, -1):
+            m = max(ch[l] // 16, 1)
+            conv_bn(f'dec{l}.hl3', (ch[l + 1], ch[l + 1]) + k3)
+            conv_bn(f'dec{l}.hl1', (ch[l], ch[l + 1]) + k1)
+            for se in ('se_hl', 'se_ll'):
+                shapes[f'dec{l}.{se}.fc1.weight'] = (m, ch[l])
+                shapes[f'dec{l}.{se}.fc1.bias'] = (m,)
+                shapes[f'dec{l}.{se}.fc2.weight'] = (ch[l], m)
+                shapes[f'dec{l}.{se}.fc2.bias'] = (ch[l],)
+            stage(f'dec{l}', 2 * ch[l], ch[l])
+        shapes['head.weight'] = (ncls, ch[0]) + k1
+        shapes['head.bias'] = (ncls,)
+        return shapes
     if architecture == DEEPLAB:
         C, Cb = decoder_channels, ch[-1]
         for prefix, shp in (('aspp.b0', (C, Cb) + k1), ('aspp.b1', (C, Cb) + k3), ('aspp.b2', (C, Cb) + k3), ('aspp.b3', (C, Cb) + k3),
@@ -138,7 +169,7 @@ def param_shapes(dim=2, levels=4, base=32, cin=1, ncls=2, architecture='U-Net', 
 
 # The architectures beside the U-Net: their native limits (the level range; whether base, input channels and classes are limited; the
 # decoder-width argument; DeepLabV3's ASPP arguments), their forward engines (module, 16-bit class, fp32 class, constructor keywords) and
-# their training engine (module, class)
+# their training engine (module, class); bottom: the most channels the coarsest level may have
 NATIVE = {
     NESTED: dict(levels=(2, 9), shape=False, width=None, aspp=False,
                  engines=('engine_nested', 'NestedEngine', 'NestedEngineF32', lambda m: {}), train=('train_engine_nested', 'NestedTrainEngine')),
@@ -156,6 +187,8 @@ NATIVE = {
     UPERNET: dict(levels=(4, 6), shape=True, width='decoder_channels', aspp=False,
                   engines=('engine_upernet', 'UPerNetEngine', 'UPerNetEngineF32', lambda m: dict(decoder_channels=m.decoder_channels)),
                   train=('train_engine_upernet', 'UPerNetTrainEngine')),
+    MANET: dict(levels=(3, 5), shape=True, width=None, aspp=False, bottom=512,
+                engines=('engine_manet', 'MANetEngine', 'MANetEngineF32', lambda m: {}), train=('train_engine_manet', 'MANetTrainEngine')),
 }
 
 
@@ -183,6 +216,8 @@ def _check_native(architecture, levels, base, cin, ncls, act_dtype, weight_dtype
              f'{lo} .. {hi} levels']
     if spec['shape']:
         parts += ['base a multiple of 32', '1 .. 4 input channels', '2 .. 10 classes']
+    if spec.get('bottom'):
+        parts.append(f"at most {spec['bottom']} channels on the coarsest level")
     if spec['width']:
         parts.append(f"{spec['width']} a multiple of 32 in 32 .. 512")
     if spec['aspp']:
@@ -202,6 +237,8 @@ def _check_native(architecture, levels, base, cin, ncls, act_dtype, weight_dtype
         raise NotImplementedError(f'{architecture} with {levels} levels: {what}')
     if spec['shape'] and (not (lo <= levels <= hi) or base % 32 or not (1 <= cin <= 4) or not (2 <= ncls <= 10)):
         raise NotImplementedError(f'{architecture} with {levels} levels, base {base}, {cin} input channels, {ncls} classes: {what}')
+    if spec.get('bottom') and base * 2 ** (levels - 1) > spec['bottom']:
+        raise NotImplementedError(f'{architecture} with base {base} at {levels} levels ({base * 2 ** (levels - 1)} channels on the coarsest level): {what}')
     width = decoder.get(spec['width'])
     if spec['width'] and (not isinstance(width, int) or isinstance(width, bool) or width % 32 or not (32 <= width <= 512)):
         raise NotImplementedError(f"{architecture} with {spec['width']}={width!r}: {what}")
@@ -256,7 +293,7 @@ class UNet(nn.Module):
                  decoder_segmentation_channels=256):
         super().__init__()
         if architecture not in ARCHITECTURES:
-            raise NotImplementedError(f"architecture {architecture!r}: only 'U-Net', 'U-Net++', 'LinkNet', 'DeepLabV3', 'Segformer' and 'UPerNet' have a native "
+            raise NotImplementedError(f"architecture {architecture!r}: only 'U-Net', 'U-Net++', 'LinkNet', 'DeepLabV3', 'Segformer', 'UPerNet' and 'MA-Net' have a native "
                                       f"MI355X implementation (the reference builds the others through smp, unet.py:33-54)")
         if architecture in NATIVE:
             _check_native(architecture, levels, base, num_channels, num_classes, act_dtype, weight_dtype, norm, infer_dtype, infer_policy,
@@ -336,11 +373,17 @@ class UNet(nn.Module):
             for name in self._names:
                 t = self.tensor(name)
                 shp = t.shape
-                if name.endswith('conv1.weight') or name.endswith('conv2.weight') or name == 'head.weight' or name.endswith('.conv.weight'):
+                if name in ('pab.top.conv.weight', 'pab.center.conv.weight'):
+                    # MA-Net's queries and keys: unit gain, and the 1 / sqrt(K) the logits S = Kc Q^T do not carry split between the two
+                    # (He-normal weights put S in the hundreds: a one-hot softmax that passes no gradient to either)
+                    t.copy_(torch.randn(shp, generator=g) * math.sqrt(1.0 / shp[1]) * MANET_QK ** -0.25)
+                elif name.endswith('conv1.weight') or name.endswith('conv2.weight') or name == 'head.weight' or name.endswith('.conv.weight'):
                     fan_in = shp[1] * math.prod(shp[2:])
                     t.copy_(torch.randn(shp, generator=g) * math.sqrt(2.0 / fan_in))      # He-normal
                 elif name.startswith('mlp') and name.endswith('.weight'):
                     t.copy_(torch.randn(shp, generator=g) * math.sqrt(2.0 / shp[1]))       # He-normal, fan-in ch[l]
+                elif name.endswith('fc1.weight') or name.endswith('fc2.weight'):
+                    t.copy_(torch.randn(shp, generator=g) * math.sqrt(1.0 / shp[1]))       # MA-Net's gates: fan-in scaling
                 elif name.endswith('up.weight'):
                     t.copy_(torch.randn(shp, generator=g) * math.sqrt(1.0 / shp[0]))
                 elif name.endswith('running_var') or name.endswith('bn1.weight') or name.endswith('bn2.weight') or name.endswith('bn3.weight') \
