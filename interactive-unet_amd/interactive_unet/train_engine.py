@@ -80,7 +80,13 @@ class TrainEngineBase:
         return topology.up_convs(self.levels)
 
     def _prep(self, X, y, w, convert_x=True):
-        """-> (X, y, w, N, D, H, W, voxels, X's strides) on the device; convert_x: X in a dtype the first conv reads."""
+        """-> (X, y, w, N, D, H, W, voxels, X's strides) on the device; convert_x: X in a dtype the first conv reads.  The first conv
+        indexes X by the model's channel count and the loss kernels index y and w by its class count over X's grid: a batch of any
+        other shape is refused here, before anything is copied or launched (whatever loader made it, new or resumed model)."""
+        want = (X.shape[0], self.ncls) + tuple(X.shape[2:])
+        if X.dim() != self.dim + 2 or X.shape[1] != self.cin or tuple(y.shape) != want or (w is not None and tuple(w.shape) != want):
+            raise ValueError(f'batch X {tuple(X.shape)}, y {tuple(y.shape)}, w {None if w is None else tuple(w.shape)}: the {self.dim}-D model has '
+                             f'{self.cin} input channel(s) and {self.ncls} classes, so X is [N, {self.cin}, ...] and y, w are [N, {self.ncls}, ...] over X\'s grid')
         X = X.to(self.dev).contiguous()
         y = y.to(self.dev).contiguous()
         w = None if w is None else w.to(self.dev).contiguous()
