@@ -468,6 +468,23 @@ int iunet_zoom_nearest_u8(const void* src, const int* src_dims, const long long*
 int iunet_augment_desc_bytes(void);
 int iunet_augment_batch(const void* descs, int B, int ch, int C, int OH, int OW, const void* lut_f16, void* X, void* y, void* w,
                         void* stream);
+/* The same batch with the reference's three further transforms (loader.py:115-123; defined bit for bit by
+ * tests/augment_ref.py): ElasticTransform(NEAREST), ColorJitter(brightness, contrast), RandomChoice([GaussianBlur(5),
+ * GaussianNoise()]).  descs: as above.  extras: device array of B descriptors (struct AugExtraDesc in csrc/augment.hip, mirrored
+ * by interactive_unet/loader.py; iunet_augment_extra_desc_bytes() = its size): flags (1 elastic, 2 jitter), kind (0 neither,
+ * 1 blur, 2 noise), the elastic Philox key (low, high word) and float32(alpha / 2), brightness, contrast, contrast_first, the 25
+ * blur weights float32(k_i k_j), the noise key and sigma.  use: which transforms occur anywhere in the batch (bits 1 elastic,
+ * 2 jitter, 4 blur, 8 noise): a launch nobody needs is left out, and a sample's transform whose bit is missing is off.
+ * lut_f32: 256 float32 values float32(v / 255); taps_f32: the K float32 taps of the elastic Gaussian (needed with elastic in
+ * use only; K odd, 1 .. 129, and both output sides must exceed K / 2; with blur in use both must exceed 2: the borders reflect
+ * without edge repeat).  ws: iunet_augment_extra_ws_bytes(B, ch, OH, OW) bytes of device scratch (negative: the shape is
+ * refused; OH, OW <= 65535).  Up to five kernels and one memset on `stream`, nothing is copied to the host.  y, w and X equal
+ * the definition bit for bit, X on noise samples up to the device's logf / cosf (one fp16 step). */
+long long iunet_augment_extra_desc_bytes(void);
+long long iunet_augment_extra_ws_bytes(int B, int ch, int OH, int OW);
+int iunet_augment_batch_extra(const void* descs, const void* extras, int use, int B, int ch, int C, int OH, int OW,
+                              const void* lut_f16, const void* lut_f32, const void* taps_f32, int K,
+                              void* ws, long long ws_bytes, void* X, void* y, void* w, void* stream);
 
 /* ---- 3-D patch batch producer (volumedata.py:68-80 + loader.py:48-82 in 3-D) --------------------- */
 /* One launch = one batch of random oblique patches for the dim = 3 training step: for sample b, X[b] = image (spline order 0

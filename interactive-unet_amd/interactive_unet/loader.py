@@ -4,7 +4,10 @@ every batch -- normalisation (loader.py:32-42), RandomHorizontalFlip / RandomVer
 RandomResizedCrop((512, 512), NEAREST) (loader.py:125-133) and the float16 conversion (loader.py:150-152) -- is ONE gather
 launch (libiunet: iunet_augment_batch).  The random parameters are drawn on the host from torch's generator in the order
 torchvision's v2 transforms draw them (flip, flip, angle, crop box); the reference runs the same chain per sample on the CPU
-with num_workers=0 (loader.py:95-99).
+with num_workers=0 (loader.py:95-99).  The three transforms the reference's authors switch on and off (loader.py:115-123:
+ElasticTransform, ColorJitter, RandomChoice([GaussianBlur(5), GaussianNoise()])) are keywords of `UNetDataset` / `get_data_loader`,
+off by default; switched on, `draw_extra` draws their parameters after each sample's four and the batch goes through
+iunet_augment_batch_extra's short pipeline instead, still without a copy to the host.
 
 File reading (TIFF / PNG through PIL) and `colored_to_categorical` are caller-side format code; `annotations_from_arrays`
 takes arrays directly.  `reslice=True` (load_resliced_annotations, dead code in the reference: trainer.py:18) is not provided.
@@ -36,6 +39,16 @@ class AugDesc(ctypes.Structure):
                 ('yg', ctypes.c_void_p), ('H', ctypes.c_int), ('W', ctypes.c_int), ('hflip', ctypes.c_int), ('vflip', ctypes.c_int),
                 ('kind', ctypes.c_int), ('ci', ctypes.c_int), ('cj', ctypes.c_int), ('ch', ctypes.c_int), ('cw', ctypes.c_int),
                 ('r', ctypes.c_float * 6), ('keep_dark', ctypes.c_int)]
+
+
+USE_ELASTIC, USE_JITTER, USE_BLUR, USE_NOISE = 1, 2, 4, 8      # iunet_augment_batch_extra's `use` bits; AugExtraDesc.flags has the first two
+
+
+class AugExtraDesc(ctypes.Structure):
+    """Mirror of csrc/augment.hip: AugExtraDesc (36 four-byte fields, no padding)."""
+    _fields_ = [('flags', ctypes.c_int), ('kind', ctypes.c_int), ('ekey', ctypes.c_uint * 2), ('a2', ctypes.c_float),
+                ('brightness', ctypes.c_float), ('contrast', ctypes.c_float), ('contrast_first', ctypes.c_int),
+                ('w2', ctypes.c_float * 25), ('nkey', ctypes.c_uint * 2), ('sigma_n', ctypes.c_float)]
 
 
 def colored_to_categorical(colored_mask):
@@ -123,6 +136,74 @@ def draw_params(H, W, gen=None):
     return hflip, vflip, angle, resized_crop_params(H, W, gen)
 
 
+def _key(gen):
+    """A 64-bit Philox key: one randint(0, 2^32, (2,)), low word first."""
+    lo, hi = torch.randint(0, 2 ** 32, (2,), generator=gen).tolist()
+    return lo | hi << 32
+
+
+def draw_extra(gen=None, elastic=False, color_jitter=False, blur_or_noise=False, elastic_alpha=50.0, noise_sigma=0.1):
+    """One sample's parameters of the three further transforms of loader.py:115-123, drawn after the four
+    draws of `draw_params`, each transform only where it is switched on: elastic: the key; color_jitter: rand < 0.5 -> contrast
+    first, brightness ~ U(0.75, 1.25), contrast ~ U(0.5, 2.0); blur_or_noise: randint(0, 2): 0 blur, then sigma ~ U(0.1, 2.0);
+    1 noise, then the key.  Returns the dict `UNetDataset.batch(extra=...)` takes per sample (a missing entry = off); with
+    everything off nothing is drawn."""
+    extra = {}
+    if elastic:
+        extra['elastic'] = {'key': _key(gen), 'alpha': float(elastic_alpha)}
+    if color_jitter:
+        contrast_first = bool(torch.rand(1, generator=gen).item() < 0.5)
+        brightness = _uniform(0.75, 1.25, gen)
+        extra['color_jitter'] = {'brightness': brightness, 'contrast': _uniform(0.5, 2.0, gen), 'contrast_first': contrast_first}
+    if blur_or_noise:
+        if torch.randint(0, 2, (1,), generator=gen).item() == 0:
+            extra['blur_or_noise'] = {'kind': 'blur', 'sigma': _uniform(0.1, 2.0, gen)}
+        else:
+            extra['blur_or_noise'] = {'kind': 'noise', 'key': _key(gen), 'sigma': float(noise_sigma)}
+    return extra
+
+
+def gaussian_taps(sigma, K=None):
+    """The normalised Gaussian taps, float64 rounded to float32; K = int(8 sigma + 1) made odd unless given."""
+    if K is None:
+        K = int(8 * sigma + 1)
+        K += 1 - K % 2
+    x = np.arange(K, dtype=np.float64) - (K - 1) / 2
+    g = np.exp(-0.5 * (x / float(sigma)) ** 2)
+    return (g / g.sum()).astype(np.float32)
+
+
+def _fill_extra(d, extra):
+    """One AugExtraDesc from a sample's dict; returns the sample's `use` bits."""
+    use = 0
+    if 'elastic' in extra:
+        e = extra['elastic']
+        d.flags |= USE_ELASTIC
+        d.ekey[0], d.ekey[1] = int(e['key']) & 0xFFFFFFFF, (int(e['key']) >> 32) & 0xFFFFFFFF
+        d.a2 = float(e['alpha']) / 2
+        use |= USE_ELASTIC
+    if 'color_jitter' in extra:
+        cj = extra['color_jitter']
+        d.flags |= USE_JITTER
+        d.brightness, d.contrast, d.contrast_first = float(cj['brightness']), float(cj['contrast']), int(bool(cj['contrast_first']))
+        use |= USE_JITTER
+    bn = extra.get('blur_or_noise')
+    if bn is not None:
+        if bn['kind'] == 'blur':
+            k = gaussian_taps(bn['sigma'], 5)
+            d.kind = 1
+            d.w2[:] = (k[:, None] * k[None, :]).reshape(-1).tolist()          # float32 products
+            use |= USE_BLUR
+        elif bn['kind'] == 'noise':
+            d.kind = 2
+            d.nkey[0], d.nkey[1] = int(bn['key']) & 0xFFFFFFFF, (int(bn['key']) >> 32) & 0xFFFFFFFF
+            d.sigma_n = float(bn['sigma'])
+            use |= USE_NOISE
+        else:
+            raise ValueError(f"blur_or_noise kind {bn['kind']!r}: 'blur' or 'noise'")
+    return use
+
+
 def _rotation(angle, H, W):
     """(kind, r[6]) of torchvision's rotate(angle, NEAREST, expand=False, center=None): the fast paths for multiples of 90
     degrees, else theta^T / (W/2, H/2) of the inverse rotation about the centre, formed in float32 as _affine_grid does."""
@@ -144,9 +225,12 @@ class UNetDataset:
     """loader.py:103-154.  `annotations`: the list from load_annotations / annotations_from_arrays."""
 
     def __init__(self, annotations, resliced_annotations=None, reslice=False, reslice_factor=2, augment=False, generator=None,
-                 out_size=OUT_SIZE, keep_dark=False):
+                 out_size=OUT_SIZE, keep_dark=False, elastic=False, color_jitter=False, blur_or_noise=False, elastic_alpha=50.0,
+                 elastic_sigma=5.0, noise_sigma=0.1):
         if reslice:
             raise NotImplementedError('reslice=True (load_resliced_annotations) is not provided; the reference never enables it')
+        if (elastic or color_jitter or blur_or_noise) and not augment:
+            raise ValueError('elastic / color_jitter / blur_or_noise are augmentations: they need augment=True')
         self.annotations = annotations
         self.resliced_annotations = resliced_annotations
         self.reslice, self.reslice_factor, self.augment = reslice, reslice_factor, augment
@@ -155,7 +239,11 @@ class UNetDataset:
         # the image is 0 (the Suggestor's tensors, suggestor.py:60-65, carry no such masking)
         self.out_size = (out_size, out_size) if isinstance(out_size, int) else tuple(out_size)
         self.keep_dark = bool(keep_dark)
+        # the three further transforms of loader.py:115-123, off by default: nothing more is drawn or launched
+        self.elastic, self.color_jitter, self.blur_or_noise = bool(elastic), bool(color_jitter), bool(blur_or_noise)
+        self.elastic_alpha, self.elastic_sigma, self.noise_sigma = float(elastic_alpha), float(elastic_sigma), float(noise_sigma)
         self._grids, self._lut = {}, None
+        self._lut32 = self._taps = self._ws = None
 
     def __len__(self):
         return len(self.annotations)
@@ -166,17 +254,25 @@ class UNetDataset:
             self._grids[key] = torch.linspace((1.0 - n) * 0.5, (n - 1.0) * 0.5, steps=n).to(device)
         return self._grids[key]
 
-    def batch(self, indices, params=None):
-        """The batch loader.py's DataLoader would collate from __getitem__(i) for i in indices, in one launch.  `params`:
-        optional list of (hflip, vflip, angle, crop) per sample (drawn from the generator when None)."""
+    def batch(self, indices, params=None, extra=None):
+        """The batch loader.py's DataLoader would collate from __getitem__(i) for i in indices.  `params`: optional list of
+        (hflip, vflip, angle, crop) per sample (drawn from the generator when None).  `extra`: optional list, per sample, of the
+        dict `draw_extra` returns ('elastic': {key, alpha}, 'color_jitter': {brightness, contrast, contrast_first},
+        'blur_or_noise': {kind: 'blur', sigma} or {kind: 'noise', key, sigma}; a missing entry = off), drawn after each sample's
+        `params` when None and a transform is switched on.  With the three transforms off and no `extra` the batch is ONE gather
+        launch (iunet_augment_batch); else the pipeline of iunet_augment_batch_extra."""
         ann = [self.annotations[i] for i in indices]
         dev = ann[0][0].device
         ch, C = int(ann[0][0].shape[2]), int(ann[0][1].shape[2])
+        extras_on = self.elastic or self.color_jitter or self.blur_or_noise
+        if extra is not None and not self.augment:
+            raise ValueError('extra: the further transforms need augment=True')
         if self.augment:
             OH, OW = self.out_size
         else:
             OH, OW = int(ann[0][0].shape[0]), int(ann[0][0].shape[1])
         descs = (AugDesc * len(ann))()
+        drawn = []
         for k, (image, mask, weight) in enumerate(ann):
             H, W = int(image.shape[0]), int(image.shape[1])
             if int(image.shape[2]) != ch or int(mask.shape[2]) != C or (not self.augment and (H, W) != (OH, OW)):
@@ -184,6 +280,9 @@ class UNetDataset:
             if self.augment:
                 hflip, vflip, angle, crop = params[k] if params is not None else draw_params(H, W, self.generator)
                 kind, r = _rotation(angle, H, W)
+                if extra is None and extras_on:
+                    drawn.append(draw_extra(self.generator, self.elastic, self.color_jitter, self.blur_or_noise, self.elastic_alpha,
+                                            self.noise_sigma))
             else:
                 hflip, vflip, kind, r, crop = False, False, 1, [0.0] * 6, (0, 0, H, W)
             d = descs[k]
@@ -196,13 +295,36 @@ class UNetDataset:
                 d.r[q] = r[q]
         if self._lut is None or self._lut.device != dev:
             self._lut = torch.from_numpy((np.arange(256) / 255).astype('float32')).to(torch.float16).to(dev)   # loader.py:37-39, :150
-        raw = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
         B = len(ann)
         X = torch.empty((B, ch, OH, OW), dtype=torch.float16, device=dev)
         y = torch.empty((B, C, OH, OW), dtype=torch.float16, device=dev)
         w = torch.empty((B, C, OH, OW), dtype=torch.float16, device=dev)
+        if extra is None and not drawn:
+            raw = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
+            with torch.cuda.device(dev):
+                nv.call('iunet_augment_batch', nv.ptr(raw), B, ch, C, OH, OW, nv.ptr(self._lut), nv.ptr(X), nv.ptr(y), nv.ptr(w), nv.stream())
+            return X, y, w
+        extra = drawn if extra is None else list(extra)
+        if len(extra) != B:
+            raise ValueError(f'extra: {len(extra)} entries for a batch of {B}')
+        extras = (AugExtraDesc * B)()
+        use = 0
+        for d, e in zip(extras, extra):
+            use |= _fill_extra(d, e or {})
+        assert nv.lib().iunet_augment_extra_desc_bytes() == ctypes.sizeof(AugExtraDesc), 'AugExtraDesc layout mismatch with libiunet'
+        if self._lut32 is None or self._lut32.device != dev:
+            self._lut32 = torch.from_numpy((np.arange(256) / 255).astype('float32')).to(dev)
+        if self._taps is None or self._taps[0] != (self.elastic_sigma, dev):
+            self._taps = ((self.elastic_sigma, dev), torch.from_numpy(gaussian_taps(self.elastic_sigma)).to(dev))
+        taps = self._taps[1]
+        need = nv.answer(nv.lib().iunet_augment_extra_ws_bytes(B, ch, OH, OW))
+        if self._ws is None or self._ws.device != dev or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        raw = torch.frombuffer(bytearray(bytes(descs) + bytes(extras)), dtype=torch.uint8).to(dev)      # one upload: AugDesc is a multiple of 8 bytes
         with torch.cuda.device(dev):
-            nv.call('iunet_augment_batch', nv.ptr(raw), B, ch, C, OH, OW, nv.ptr(self._lut), nv.ptr(X), nv.ptr(y), nv.ptr(w), nv.stream())
+            nv.call('iunet_augment_batch_extra', nv.ptr(raw), ctypes.c_void_p(raw.data_ptr() + ctypes.sizeof(descs)), use, B, ch, C, OH, OW,
+                    nv.ptr(self._lut), nv.ptr(self._lut32), nv.ptr(taps), int(taps.numel()), nv.ptr(self._ws),
+                    int(self._ws.numel()), nv.ptr(X), nv.ptr(y), nv.ptr(w), nv.stream())
         return X, y, w
 
     def __getitem__(self, idx):
@@ -227,11 +349,13 @@ class DeviceLoader:
 
 
 def get_data_loader(set_type='train', num_classes=2, batch_size=2, reslice=False, reslice_factor=2, augment=True, shuffle=True,
-                    annotations=None, generator=None):
-    """loader.py:84-101 (`annotations`: skip the file read and use these)."""
+                    annotations=None, generator=None, elastic=False, color_jitter=False, blur_or_noise=False):
+    """loader.py:84-101 (`annotations`: skip the file read and use these; elastic / color_jitter / blur_or_noise: the three
+    transforms of loader.py:115-123 the reference's authors switch on and off, at its parameters)."""
     if annotations is None:
         annotations = load_annotations(set_type=set_type)
-    dataset = UNetDataset(annotations, None, reslice=reslice, reslice_factor=reslice_factor, augment=augment, generator=generator)
+    dataset = UNetDataset(annotations, None, reslice=reslice, reslice_factor=reslice_factor, augment=augment, generator=generator,
+                          elastic=elastic, color_jitter=color_jitter, blur_or_noise=blur_or_noise)
     return DeviceLoader(dataset, batch_size=batch_size, shuffle=shuffle, generator=generator)
 
 

@@ -22,10 +22,11 @@ from .train_engine_f32 import make_train_engine
 METRICS = ('Loss', 'Dice', 'IoU', 'MCC')
 
 
-def _loaders(num_classes, batch_size, reslice, reslice_factor):
+def _loaders(num_classes, batch_size, reslice, reslice_factor, elastic=False, color_jitter=False, blur_or_noise=False):
     from . import loader                           # the device batch producer (loader.py:84-101)
     tr = loader.get_data_loader(set_type='train', num_classes=num_classes, batch_size=batch_size, reslice=reslice,
-                                reslice_factor=reslice_factor, augment=True, shuffle=True)
+                                reslice_factor=reslice_factor, augment=True, shuffle=True, elastic=elastic, color_jitter=color_jitter,
+                                blur_or_noise=blur_or_noise)          # the training loader only: validation stays unaugmented
     va = loader.get_data_loader(set_type='val', num_classes=num_classes, batch_size=batch_size, reslice=False,
                                 reslice_factor=reslice_factor, augment=False, shuffle=False)
     return tr, va
@@ -61,15 +62,24 @@ def _mean(rows):
 
 def train_model(lr=0.0001, batch_size=1, epochs=10, num_channels=1, num_classes=2, loss_function_name='MCC + CE',
                 architecture='U-Net', encoder_name='mit_b0', pretrained=True, reslice=False, reslice_factor=2,
-                train_loader=None, val_loader=None, dim=2, act_dtype=None, process_group=None, patch_size=64, patches_per_epoch=100):
+                train_loader=None, val_loader=None, dim=2, act_dtype=None, process_group=None, patch_size=64, patches_per_epoch=100,
+                elastic=False, color_jitter=False, blur_or_noise=False):
     """dim=3 without loaders: `patches_per_epoch` patches of `patch_size` (an int or (SZ, SY, SX)) per epoch from the annotation
-    volumes under data/ (loader.get_volume_loader): augmented for training, a fixed axis-aligned set for validation."""
+    volumes under data/ (loader.get_volume_loader): augmented for training, a fixed axis-aligned set for validation.
+    elastic / color_jitter / blur_or_noise: the three transforms the reference's authors switch on and off (loader.py:115-123), for
+    the 2-D training loader this function builds."""
     model_path = os.path.join('model', 'model.ckpt')
+    if elastic or color_jitter or blur_or_noise:
+        if dim == 3:
+            raise ValueError('elastic / color_jitter / blur_or_noise: the 3-D patch producer does not have them (dim=2 only)')
+        if train_loader is not None and val_loader is not None:
+            raise ValueError('elastic / color_jitter / blur_or_noise configure the loader train_model builds: with loaders of your own, '
+                             'set them there (loader.get_data_loader)')
     volumes = dim == 3 and (train_loader is None or val_loader is None)
     if volumes and not os.path.isfile(model_path):  # a new model has the default depth: refused before anything touches the GPU
         _check_patch_size(patch_size, inspect.signature(unet.UNet.__init__).parameters['levels'].default)
     elif not volumes and (train_loader is None or val_loader is None):
-        train_loader, val_loader = _loaders(num_classes, batch_size, reslice, reslice_factor)
+        train_loader, val_loader = _loaders(num_classes, batch_size, reslice, reslice_factor, elastic, color_jitter, blur_or_noise)
     loss_function = metrics.loss_name_to_function(loss_function_name)
     device = torch.device('cuda', torch.cuda.current_device())
 
