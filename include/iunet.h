@@ -501,6 +501,26 @@ int iunet_augment_batch_extra(const void* descs, const void* extras, int use, in
 long long iunet_patch_desc_bytes(void);
 int iunet_patch_batch(const void* descs, int B, int ch, int C, int SZ, int SY, int SX, int order, const void* lut_f16, void* X,
                       void* y, void* w, void* stream);
+/* The same batch with elastic deformation, intensity jitter and "Gaussian blur or Gaussian noise" (the three further transforms of
+ * loader.py:115-123 in 3-D; defined bit for bit by tests/patch_augment_ref.py).  descs: as above.  extras:
+ * device array of B descriptors (struct PatchExtraDesc in csrc/patch_augment.hip, mirrored by interactive_unet/loader.py;
+ * iunet_patch_extra_desc_bytes() = its size), 16 four-byte fields: flags (1 elastic, 2 jitter), kind (0 neither, 1 blur, 2 noise),
+ * the elastic Philox key (low, high word) and float32(alpha / 2), brightness, contrast, contrast_first, the five blur taps, the
+ * noise key and sigma.  use: which transforms occur anywhere in the batch (bits 1 elastic, 2 jitter, 4 blur, 8 noise): a launch
+ * nobody needs is left out, and a sample's transform whose bit is missing is off.  The elastic displacement (three Philox noise
+ * fields smoothed along x, y, z with the K taps, times alpha / 2, in voxels) is added to the centred patch coordinate before
+ * m t + c, so image, mask and weight are sampled once, at the displaced coordinate.  taps_f32: the K float32 taps of the elastic
+ * Gaussian on the device (needed with elastic in use only; K odd, 1 .. 129, every patch extent must exceed K / 2 and
+ * B * SY <= 65535; with blur in use every extent must exceed 2: the borders reflect without edge repeat).  ws:
+ * iunet_patch_extra_ws_bytes(B, ch, SZ, SY, SX) bytes of device scratch (negative: the shape is refused).  Every range
+ * iunet_patch_batch refuses is refused here.  Up to seven kernels and one memset on `stream`, nothing is copied to the host.  With
+ * use = 0 the bits are iunet_patch_batch's; y, w and X equal the definition bit for bit, X on noise samples up to the device's
+ * logf / cosf (one fp16 step). */
+long long iunet_patch_extra_desc_bytes(void);
+long long iunet_patch_extra_ws_bytes(int B, int ch, int SZ, int SY, int SX);
+int iunet_patch_batch_extra(const void* descs, const void* extras, int use, int B, int ch, int C, int SZ, int SY, int SX, int order,
+                            const void* lut_f16, const void* taps_f32, int K, void* ws, long long ws_bytes, void* X, void* y,
+                            void* w, void* stream);
 
 /* ---- training step (replaces autograd + AMP + AdamW under unet.py:71-102, trainer.py:56-63) -- */
 /* BatchNorm batch statistics: slab = partial (sum, sumsq) [nparts][C][2] written by the conv

@@ -16,7 +16,10 @@ The 3-D producer is the 3-D form of VolumeData.sample + l
 loader.py:48-82) for the dim = 3 network: `load_volume_annotations` / `volume_annotations_from_arrays` keep the image, mask and
 weight VOLUMES as uint8 on the GPU, `VolumeDataset` draws random oblique patches around annotated voxels (`patch_candidates`,
 `draw_patch_params`) and every batch -- image at spline order 1, mask and weight at order 0, one-hot, dark rule, fp16 -- is ONE
-gather launch (libiunet: iunet_patch_batch).  `get_volume_loader` wraps it in the same `DeviceLoader`.
+gather launch (libiunet: iunet_patch_batch).  `get_volume_loader` wraps it in the same `DeviceLoader`.  The same three further
+transforms are keywords of `VolumeDataset` / `get_volume_loader`, off by default: switched on, `draw_extra`
+draws their parameters after each sample's `draw()` and the batch goes through iunet_patch_batch_extra's pipeline -- the elastic
+displacement is added to the patch coordinate before the one gather, the intensity transforms follow it -- without a copy to the host.
 """
 import ctypes
 import glob
@@ -367,6 +370,43 @@ class PatchDesc(ctypes.Structure):
                 ('keep_dark', ctypes.c_int)]
 
 
+class PatchExtraDesc(ctypes.Structure):
+    """Mirror of csrc/patch_augment.hip: PatchExtraDesc (16 four-byte fields, no padding)."""
+    _fields_ = [('flags', ctypes.c_int), ('kind', ctypes.c_int), ('ekey', ctypes.c_uint * 2), ('a2', ctypes.c_float),
+                ('brightness', ctypes.c_float), ('contrast', ctypes.c_float), ('contrast_first', ctypes.c_int),
+                ('taps', ctypes.c_float * 5), ('nkey', ctypes.c_uint * 2), ('sigma_n', ctypes.c_float)]
+
+
+def _fill_patch_extra(d, extra):
+    """One PatchExtraDesc from a sample's dict (what `draw_extra` returns); returns the sample's `use` bits."""
+    use = 0
+    if 'elastic' in extra:
+        e = extra['elastic']
+        d.flags |= USE_ELASTIC
+        d.ekey[0], d.ekey[1] = int(e['key']) & 0xFFFFFFFF, (int(e['key']) >> 32) & 0xFFFFFFFF
+        d.a2 = float(e['alpha']) / 2
+        use |= USE_ELASTIC
+    if 'color_jitter' in extra:
+        cj = extra['color_jitter']
+        d.flags |= USE_JITTER
+        d.brightness, d.contrast, d.contrast_first = float(cj['brightness']), float(cj['contrast']), int(bool(cj['contrast_first']))
+        use |= USE_JITTER
+    bn = extra.get('blur_or_noise')
+    if bn is not None:
+        if bn['kind'] == 'blur':
+            d.kind = 1
+            d.taps[:] = gaussian_taps(bn['sigma'], 5).tolist()
+            use |= USE_BLUR
+        elif bn['kind'] == 'noise':
+            d.kind = 2
+            d.nkey[0], d.nkey[1] = int(bn['key']) & 0xFFFFFFFF, (int(bn['key']) >> 32) & 0xFFFFFFFF
+            d.sigma_n = float(bn['sigma'])
+            use |= USE_NOISE
+        else:
+            raise ValueError(f"blur_or_noise kind {bn['kind']!r}: 'blur' or 'noise'")
+    return use
+
+
 def volume_annotations_from_arrays(volumes, device='cuda'):
     """volumes: iterable of (image uint8 [Z, Y, X] or [Z, Y, X, ch], mask uint8 [Z, Y, X] class ids, weight uint8 [Z, Y, X] or
     [Z, Y, X, 2]: what VolumeData.build_annotation_volumes / Slicer.update_volume produce).  Returns the list VolumeDataset works
@@ -474,10 +514,14 @@ class VolumeDataset:
     """`count` random patches per epoch of the volumes of load_volume_annotations / volume_annotations_from_arrays (the 3-D form
     of load_resliced_annotations, loader.py:48-82: a uniformly drawn volume per sample, VolumeData.sample's orders -- image
     `order`, mask and weight 0).  augment=True: new patches at every call; augment=False: `count` axis-aligned patches drawn once
-    here from `generator`, the same every epoch."""
+    here from `generator`, the same every epoch.  elastic / color_jitter / blur_or_noise: the three further transforms (DESIGN.md
+    section 18), off by default -- nothing more is drawn or launched; they need augment=True."""
 
     def __init__(self, volumes, num_classes, patch_size=64, count=100, weight_channel=0, augment=True, sampling_mode='random', order=1,
-                 generator=None, keep_dark=False):
+                 generator=None, keep_dark=False, elastic=False, color_jitter=False, blur_or_noise=False, elastic_alpha=50.0,
+                 elastic_sigma=5.0, noise_sigma=0.1):
+        if (elastic or color_jitter or blur_or_noise) and not augment:
+            raise ValueError('elastic / color_jitter / blur_or_noise are augmentations: they need augment=True')
         self.volumes = [tuple(v) for v in volumes]
         if not self.volumes:
             raise ValueError('no annotation volumes')
@@ -496,7 +540,9 @@ class VolumeDataset:
         for image, mask, weight in self.volumes:
             cands, probs = patch_candidates(mask, self._weight(weight))
             self.candidates.append(([c.cpu() for c in cands], probs))
-        self._lut = None
+        self.elastic, self.color_jitter, self.blur_or_noise = bool(elastic), bool(color_jitter), bool(blur_or_noise)
+        self.elastic_alpha, self.elastic_sigma, self.noise_sigma = float(elastic_alpha), float(elastic_sigma), float(noise_sigma)
+        self._lut = self._taps = self._ws = None
         self._fixed = None if augment else [self.draw() for _ in range(self.count)]
 
     def _weight(self, weight):
@@ -526,32 +572,71 @@ class VolumeDataset:
                 d.c[q] = c[q]
         return descs
 
-    def batch(self, indices, params=None):
-        """(X [B, ch, SZ, SY, SX], y, w [B, C, SZ, SY, SX]) fp16 for len(indices) samples in one launch.  `params`: optional list of
-        (volume index, m[9], c[3]) per sample; else drawn from the generator (augment=True) or the fixed set's entries `indices`."""
-        if params is None:
+    def batch(self, indices, params=None, extra=None):
+        """(X [B, ch, SZ, SY, SX], y, w [B, C, SZ, SY, SX]) fp16 for len(indices) samples.  `params`: optional list of (volume index,
+        m[9], c[3]) per sample; else drawn from the generator (augment=True) or the fixed set's entries `indices`.  `extra`: optional
+        list, per sample, of the dict `draw_extra` returns (a missing entry = off), drawn after each sample's `draw()` when None and
+        a transform is switched on.  With the three transforms off and no `extra` the batch is ONE launch (iunet_patch_batch); else
+        the pipeline of iunet_patch_batch_extra."""
+        extras_on = self.elastic or self.color_jitter or self.blur_or_noise
+        if extra is not None and not self.augment:
+            raise ValueError('extra: the further transforms need augment=True')
+        drawn = None
+        if extra is None and extras_on:
+            given, params, drawn = params, [], []
+            for k in range(len(indices)):                              # per sample: draw(), then draw_extra
+                params.append(given[k] if given is not None else self.draw())
+                drawn.append(draw_extra(self.generator, self.elastic, self.color_jitter, self.blur_or_noise, self.elastic_alpha,
+                                        self.noise_sigma))
+        elif params is None:
             params = [self.draw() for _ in indices] if self.augment else [self._fixed[i] for i in indices]
         dev = self.volumes[0][0].device
         assert nv.lib().iunet_patch_desc_bytes() == ctypes.sizeof(PatchDesc), 'PatchDesc layout mismatch with libiunet'
         if self._lut is None:
             self._lut = torch.from_numpy((np.arange(256) / 255).astype('float32')).to(torch.float16).to(dev)
-        raw = torch.frombuffer(bytearray(bytes(self.descriptors(params))), dtype=torch.uint8).to(dev)
+        descs = self.descriptors(params)
         B, ch, C = len(params), int(self.volumes[0][0].shape[3]), self.num_classes
         X = torch.empty((B, ch) + self.patch, dtype=torch.float16, device=dev)
         y = torch.empty((B, C) + self.patch, dtype=torch.float16, device=dev)
         w = torch.empty((B, C) + self.patch, dtype=torch.float16, device=dev)
+        if extra is None and drawn is None:
+            raw = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
+            with torch.cuda.device(dev):
+                nv.call('iunet_patch_batch', nv.ptr(raw), B, ch, C, *self.patch, self.order, nv.ptr(self._lut), nv.ptr(X), nv.ptr(y), nv.ptr(w),
+                        nv.stream())
+            return X, y, w
+        extra = drawn if extra is None else list(extra)
+        if len(extra) != B:
+            raise ValueError(f'extra: {len(extra)} entries for a batch of {B}')
+        extras = (PatchExtraDesc * B)()
+        use = 0
+        for d, e in zip(extras, extra):
+            use |= _fill_patch_extra(d, e or {})
+        assert nv.lib().iunet_patch_extra_desc_bytes() == ctypes.sizeof(PatchExtraDesc), 'PatchExtraDesc layout mismatch with libiunet'
+        if self._taps is None or self._taps[0] != (self.elastic_sigma, dev):
+            self._taps = ((self.elastic_sigma, dev), torch.from_numpy(gaussian_taps(self.elastic_sigma)).to(dev))
+        taps = self._taps[1]
+        need = nv.answer(nv.lib().iunet_patch_extra_ws_bytes(B, ch, *self.patch))
+        if self._ws is None or self._ws.device != dev or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        raw = torch.frombuffer(bytearray(bytes(descs) + bytes(extras)), dtype=torch.uint8).to(dev)      # one upload: PatchDesc is a multiple of 8 bytes
         with torch.cuda.device(dev):
-            nv.call('iunet_patch_batch', nv.ptr(raw), B, ch, C, *self.patch, self.order, nv.ptr(self._lut), nv.ptr(X), nv.ptr(y), nv.ptr(w),
-                    nv.stream())
+            nv.call('iunet_patch_batch_extra', nv.ptr(raw), ctypes.c_void_p(raw.data_ptr() + ctypes.sizeof(descs)), use, B, ch, C, *self.patch,
+                    self.order, nv.ptr(self._lut), nv.ptr(taps), int(taps.numel()), nv.ptr(self._ws), int(self._ws.numel()), nv.ptr(X),
+                    nv.ptr(y), nv.ptr(w), nv.stream())
         return X, y, w
 
 
 def get_volume_loader(set_type='train', num_classes=2, batch_size=2, patch_size=64, count=100, augment=True, shuffle=True, volumes=None,
-                      generator=None):
+                      generator=None, elastic=False, color_jitter=False, blur_or_noise=False, elastic_alpha=50.0, elastic_sigma=5.0,
+                      noise_sigma=0.1):
     """The 3-D counterpart of get_data_loader: `count` patches per epoch from the annotation volumes (`volumes`: skip the file read
-    and use these).  set_type 'train' reads weight channel 0, anything else channel 1 (loader.py:56-59)."""
+    and use these).  set_type 'train' reads weight channel 0, anything else channel 1 (loader.py:56-59).  elastic / color_jitter /
+    blur_or_noise: the three further transforms, off by default; trainer.train_model(dim=3) takes such a
+    loader as `train_loader`."""
     if volumes is None:
         volumes = load_volume_annotations()
     dataset = VolumeDataset(volumes, num_classes, patch_size=patch_size, count=count, weight_channel=0 if set_type == 'train' else 1,
-                            augment=augment, generator=generator)
+                            augment=augment, generator=generator, elastic=elastic, color_jitter=color_jitter, blur_or_noise=blur_or_noise,
+                            elastic_alpha=elastic_alpha, elastic_sigma=elastic_sigma, noise_sigma=noise_sigma)
     return DeviceLoader(dataset, batch_size=batch_size, shuffle=shuffle, generator=generator)
