@@ -491,12 +491,12 @@ int iunet_augment_batch_extra(const void* descs, const void* extras, int use, in
  * or 1), y[b] = one-hot of the class-id mask and w[b] = weight (both order 0, weight repeated over the C classes) of the
  * SZ x SY x SX patch whose voxel t (centred patch coordinates) sits at source coordinate m t + c; zero outside the volume;
  * mask and weight zero where image channel 0 is 0 at the nearest voxel unless keep_dark; fp16 of float32(uint8 / 255).
- * descs: device array of B descriptors (struct PatchDesc in csrc/patch_batch.hip, mirrored by interactive_unet/loader.py;
+ * descs: device array of B descriptors (struct PatchDesc in csrc/patch_gather.h, mirrored by interactive_unet/loader.py;
  * iunet_patch_desc_bytes() = its size), one per sample, so a batch can mix volumes of different shapes: image uint8
  * [Z][Y][X][ch], mask uint8 [Z][Y][X] class ids (an id >= C sets no channel), weight uint8 [Z][Y][X] read with an element
  * stride, Z, Y, X, m[9] (row-major; rows = source axes z, y, x, columns = patch axes z, y, x), c[3], keep_dark.
  * lut_f16: 256 fp16 values on the device.  X [B][ch][SZ][SY][SX], y and w [B][C][SZ][SY][SX] fp16.  1 <= ch <= 4,
- * 1 <= C <= 16, B * SZ <= 65535.  The arithmetic is stated in csrc/patch_batch.hip and restated in tests/patch_ref.py:
+ * 1 <= C <= 16, B * SZ <= 65535.  The arithmetic is stated in csrc/patch_gather.h and restated in tests/patch_ref.py:
  * bit-exact.  (The size comes back as long long: it is an answer, not a status.) */
 long long iunet_patch_desc_bytes(void);
 int iunet_patch_batch(const void* descs, int B, int ch, int C, int SZ, int SY, int SX, int order, const void* lut_f16, void* X,

@@ -21,7 +21,9 @@
 //                                             [B][ch][OH][OW] and (jitter) their 256-bin histogram
 //   jitter_table_kernel   (jitter in `use`)   T[b][256]: the exact mean from the histogram, brightness and contrast in drawn order
 //   augment_finish_kernel                     X = fp16 of T[G], of its 5 x 5 blur, or of clamp(T[G] + sigma_n z)
-#include "common.h"
+// What this pipeline has in common with the 3-D patch producer's (patch_augment.hip) -- Philox, the jitter, the contrast mean, the
+// histogram, the two elastic passes, the entry point's checks -- is in augment_common.h.
+#include "augment_common.h"
 
 #pragma clang fp contract(off)
 
@@ -76,21 +78,21 @@ __device__ __forceinline__ long long aug_source(const AugDesc& d, int OH, int OW
   return (long long)ry * d.W + rx;
 }
 
-// one lane per output pixel (four pixels per lane with 8-byte stores measured slower: 38 vs 25 us per batch of 8 -- the rows are
-// only 512 pixels wide and the rotated gather loses its coalescing)
-__global__ __launch_bounds__(256) void augment_batch_kernel(AugParams p) {
-  const int ox = blockIdx.x * 256 + threadIdx.x, oy = blockIdx.y, b = blockIdx.z;
-  if (ox >= p.OW) return;
-  const AugDesc d = p.descs[b];
+// Output pixel o (its offset in the [OH][OW] plane) of sample b, read at position (py, px) of the chain; ok_in false: (py, px) is
+// outside already (displaced out of the output).  y and w are stored here in final form; every image byte (0 outside) goes to
+// sink(its offset in [B][ch][OH][OW], byte).  P: the kernel's parameter struct -- ch, C, OH, OW, lut, y, w are read from it.
+template <typename P, typename Sink>
+__device__ __forceinline__ void aug_gather_pixel(const AugDesc& d, const P& p, int b, int py, int px, bool ok_in, long long o, Sink&& sink) {
   bool ok;
-  const long long src = aug_source(d, p.OH, p.OW, oy, ox, ok);
-  const long long plane = (long long)p.OH * p.OW, o = (long long)oy * p.OW + ox;
+  const long long src = aug_source(d, p.OH, p.OW, py, px, ok);
+  ok = ok && ok_in;
+  const long long plane = (long long)p.OH * p.OW;
   const f16 zero = p.lut[0];
   bool lit = false;                                   // image[0] != 0 at the source pixel
   for (int c = 0; c < p.ch; ++c) {
     const unsigned char v = ok ? d.image[src * p.ch + c] : (unsigned char)0;
     if (c == 0) lit = ok && (v != 0 || d.keep_dark);
-    p.X[((long long)b * p.ch + c) * plane + o] = p.lut[v];
+    sink(((long long)b * p.ch + c) * plane + o, v);
   }
   const f16 wv = lit ? p.lut[d.weight[src]] : zero;
   for (int c = 0; c < p.C; ++c) {
@@ -99,10 +101,16 @@ __global__ __launch_bounds__(256) void augment_batch_kernel(AugParams p) {
   }
 }
 
-// ---- elastic, colour jitter, blur and noise (tests/augment_ref.py) ---------------------------------------------------------------
-constexpr int AUG_ELASTIC = 1, AUG_JITTER = 2, AUG_BLUR = 4, AUG_NOISE = 8;      // the bits of `use`
-constexpr int AUG_MAX_TAPS = 129;                // cap of the elastic Gaussian's K = int(8 sigma + 1) made odd: sigma up to 16
+// one lane per output pixel (four pixels per lane with 8-byte stores measured slower: 38 vs 25 us per batch of 8 -- the rows are
+// only 512 pixels wide and the rotated gather loses its coalescing)
+__global__ __launch_bounds__(256) void augment_batch_kernel(AugParams p) {
+  const int ox = blockIdx.x * 256 + threadIdx.x, oy = blockIdx.y, b = blockIdx.z;
+  if (ox >= p.OW) return;
+  const AugDesc d = p.descs[b];
+  aug_gather_pixel(d, p, b, oy, ox, true, (long long)oy * p.OW + ox, [&](long long at, unsigned char v) { p.X[at] = p.lut[v]; });
+}
 
+// ---- elastic, colour jitter, blur and noise (tests/augment_ref.py) ---------------------------------------------------------------
 struct AugExtraDesc {            // one sample's further transforms (mirrored by interactive_unet/loader.py: AugExtraDesc)
   int flags;                     // AUG_ELASTIC | AUG_JITTER where the sample has them
   int kind;                      // 0 neither, 1 blur, 2 noise
@@ -133,116 +141,75 @@ struct AugExtraParams {
 struct AugWorkspace { long long rows, map, G, hist, T, total; };     // byte offsets of the workspace's parts
 inline AugWorkspace aug_workspace(int B, int ch, int OH, int OW) {
   const long long plane = (long long)OH * OW;
-  auto up = [](long long v) { return (v + 255) & ~255LL; };
   AugWorkspace s;
   s.rows = 0;
-  s.map = up(8 * B * plane);
-  s.G = s.map + up(4 * B * plane);
-  s.hist = s.G + up(B * ch * plane);
+  s.map = aug_align256(8 * B * plane);
+  s.G = s.map + aug_align256(4 * B * plane);
+  s.hist = s.G + aug_align256(B * ch * plane);
   s.T = s.hist + 1024LL * B;
   s.total = s.T + 1024LL * B;
   return s;
 }
 
-// Philox4x32-10 at counter (c0, c1, c2, c3) under key (k0, k1): words 0 and 1 of the output.  32-bit integer arithmetic: exact.
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned& w0, unsigned& w1) {
-  const unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const unsigned h0 = __umulhi(M0, c0), l0 = M0 * c0, h1 = __umulhi(M1, c2), l1 = M1 * c2;
-    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  w0 = c0; w1 = c1;
-}
-
-__device__ __forceinline__ int aug_reflect(int p, int n) {      // -1 -> 1, n -> n - 2: no edge repeat; needs |overhang| < n
-  p = p < 0 ? -p : p;
-  return p >= n ? 2 * n - 2 - p : p;
-}
-__device__ __forceinline__ float aug_clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
-
-// Elastic, horizontal pass.  A block: 256 pixels of one row of one elastic sample; the row segment's noise plus r on each side is
-// generated once into LDS (one Philox per value, not K per pixel), the K taps are taken from there in ascending order.
+// Elastic, horizontal pass (augment_common.h: aug_row_pass).  A block: 256 pixels of one row of one elastic sample, both fields;
+// counter (x, y, c, 0).
 __global__ __launch_bounds__(256) void elastic_rows_kernel(AugExtraParams p) {
   __shared__ float noise[256 + AUG_MAX_TAPS - 1];
   const int x0 = blockIdx.x * 256, y = blockIdx.y, b = blockIdx.z;
   const AugExtraDesc& e = p.extras[b];
   if (!(e.flags & AUG_ELASTIC)) return;              // the same in every lane of the block
-  const int r = p.K / 2, span = min(256, p.OW - x0) + 2 * r;
   const unsigned k0 = e.ekey[0], k1 = e.ekey[1];
   const int ox = x0 + threadIdx.x;
   for (int c = 0; c < 2; ++c) {
-    for (int t = threadIdx.x; t < span; t += 256) {
-      unsigned w0, w1;
-      philox4x32_10((unsigned)aug_reflect(x0 - r + t, p.OW), (unsigned)y, (unsigned)c, 0u, k0, k1, w0, w1);
-      const float u = (float)(w0 >> 8) * 0x1p-24f;
-      noise[t] = 2.f * u - 1.f;
-    }
-    __syncthreads();
-    if (ox < p.OW) {
-      float acc = 0.f;
-      for (int i = 0; i < p.K; ++i) acc += p.taps[i] * noise[threadIdx.x + i];
-      p.rows[(((long long)b * 2 + c) * p.OH + y) * p.OW + ox] = acc;
-    }
+    const float acc = aug_row_pass<256>(noise, threadIdx.x, true, x0, p.OW, (unsigned)y, (unsigned)c, 0u, k0, k1, p.taps, p.K);
+    if (ox < p.OW) p.rows[(((long long)b * 2 + c) * p.OH + y) * p.OW + ox] = acc;
     __syncthreads();
   }
 }
 
-// Elastic, vertical pass and displacement.  A block: a tile of 64 columns x 32 rows of one elastic sample; the tile's rows plus r
-// above and below (reflected) go through LDS once per field, so a value is read from memory (32 + 2 r) / 32 times, not K times.
-// Lane (tx, ty) takes rows ty, ty + 4, ... of column tx; the taps run in ascending order as in the horizontal pass.  Out: the pixel
-// each output pixel is displaced to, packed ey << 16 | ex, or AUG_OUTSIDE.
-constexpr int AUG_TILE_X = 64, AUG_TILE_Y = 32;
+// Elastic, vertical pass (augment_common.h: aug_tile_pass) and displacement.  A block: a tile of 64 columns x 32 rows of one elastic
+// sample, field 0 (displaces x) kept in registers, then field 1 (displaces y).  Out: the pixel each output pixel is displaced to,
+// packed ey << 16 | ex, or AUG_OUTSIDE.
 constexpr unsigned AUG_OUTSIDE = 0xFFFFFFFFu;    // no pixel packs to this: OH, OW <= 65535
-__global__ __launch_bounds__(256) void elastic_cols_kernel(AugExtraParams p) {
-  __shared__ float tile[(AUG_TILE_Y + AUG_MAX_TAPS - 1) * AUG_TILE_X];
-  const int x0 = blockIdx.x * AUG_TILE_X, y0 = blockIdx.y * AUG_TILE_Y, b = blockIdx.z;
+__global__ __launch_bounds__(AUG_TILE_LANES) void elastic_cols_kernel(AugExtraParams p) {
+  __shared__ float tile[AUG_TILE_FLOATS];
+  const int x0 = blockIdx.x * AUG_TILE_X, y0 = blockIdx.y * AUG_TILE_A, b = blockIdx.z;
   const AugExtraDesc& e = p.extras[b];
   if (!(e.flags & AUG_ELASTIC)) return;              // the same in every lane of the block
-  const int r = p.K / 2, nrows = min(AUG_TILE_Y, p.OH - y0) + 2 * r;
-  const int tx = threadIdx.x & (AUG_TILE_X - 1), ty = threadIdx.x / AUG_TILE_X, ox = x0 + tx;
   const long long plane = (long long)p.OH * p.OW;
-  float dx[AUG_TILE_Y / 4];
-  for (int c = 0; c < 2; ++c) {                      // c = 0 displaces x, c = 1 displaces y
-    const float* src = p.rows + ((long long)b * 2 + c) * plane;
-    for (int t = threadIdx.x; t < nrows * AUG_TILE_X; t += 256) {
-      const int j = t / AUG_TILE_X, gx = x0 + (t & (AUG_TILE_X - 1));
-      tile[t] = gx < p.OW ? src[(long long)aug_reflect(y0 - r + j, p.OH) * p.OW + gx] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < AUG_TILE_Y / 4; ++q) {
-      const int ly = ty + 4 * q, oy = y0 + ly;
-      if (oy < p.OH && ox < p.OW) {
-        float acc = 0.f;
-        for (int i = 0; i < p.K; ++i) acc += p.taps[i] * tile[(ly + i) * AUG_TILE_X + tx];
-        if (c == 0) dx[q] = acc * e.a2;
-        else {
-          const float fy = rintf((float)oy + acc * e.a2), fx = rintf((float)ox + dx[q]);
-          const bool inside = fy >= 0.f && fy <= (float)(p.OH - 1) && fx >= 0.f && fx <= (float)(p.OW - 1);
-          p.map[(long long)b * plane + (long long)oy * p.OW + ox] = inside ? ((unsigned)(int)fy << 16 | (unsigned)(int)fx) : AUG_OUTSIDE;
-        }
+  float dx[AUG_TILE_A / 4];
+  for (int c = 0; c < 2; ++c)
+    aug_tile_pass(tile, p.rows + ((long long)b * 2 + c) * plane, x0, y0, p.OW, p.OH, p.OW, p.taps, p.K, [&](int q, int oy, int ox, float acc) {
+      if (c == 0) dx[q] = acc * e.a2;
+      else {
+        const float fy = rintf((float)oy + acc * e.a2), fx = rintf((float)ox + dx[q]);
+        const bool inside = fy >= 0.f && fy <= (float)(p.OH - 1) && fx >= 0.f && fx <= (float)(p.OW - 1);
+        p.map[(long long)b * plane + (long long)oy * p.OW + ox] = inside ? ((unsigned)(int)fy << 16 | (unsigned)(int)fx) : AUG_OUTSIDE;
       }
-    }
-    __syncthreads();
-  }
+    });
 }
 
-// The gather: today's body behind a prologue.  An elastic sample's lane reads the pixel it is displaced to and evaluates the chain
+// The gather: aug_gather_pixel behind a prologue.  An elastic sample's lane reads the pixel it is displaced to and evaluates the chain
 // there; a pixel displaced out of the output is outside like the rotation's padding.  The image goes out as bytes (the table is not
 // known yet); a jitter sample's bytes are counted per block in LDS and merged with integer atomics.  One lane per output pixel as
 // above, but a block walks AUG_GATHER_ROWS rows: every block adds up to 256 counts to its sample's 256 words, and with a row a
 // block those atomics on 2 048 addresses (batch of 8), not the gather, set the kernel's time.
 constexpr int AUG_GATHER_ROWS = 8;
+struct AugStoreBytes {           // the gather's sink: the byte to G and into the block's histogram
+  unsigned char* G;
+  unsigned* hist;                // the block's 256 bins in LDS, or null (a lambda testing `jitter` instead: 106 SGPRs, some spilled)
+  __device__ __forceinline__ void operator()(long long at, unsigned char v) const {
+    G[at] = v;
+    if (hist) atomicAdd(&hist[v], 1u);
+  }
+};
 __global__ __launch_bounds__(256) void augment_gather_kernel(AugExtraParams p) {
   __shared__ unsigned hist[256];
   const int ox = blockIdx.x * 256 + threadIdx.x, b = blockIdx.z;
   const AugDesc d = p.descs[b];
   const AugExtraDesc& e = p.extras[b];
   const bool elastic = p.use & e.flags & AUG_ELASTIC, jitter = p.use & e.flags & AUG_JITTER;
-  if (jitter) { hist[threadIdx.x] = 0; __syncthreads(); }
+  if (jitter) aug_hist_zero(hist, threadIdx.x);
   const int row0 = blockIdx.y * AUG_GATHER_ROWS, row1 = min(row0 + AUG_GATHER_ROWS, p.OH);
   for (int oy = row0; oy < row1 && ox < p.OW; ++oy) {
     const long long plane = (long long)p.OH * p.OW, o = (long long)oy * p.OW + ox;
@@ -253,32 +220,13 @@ __global__ __launch_bounds__(256) void augment_gather_kernel(AugExtraParams p) {
       inside = m != AUG_OUTSIDE;
       py = inside ? (int)(m >> 16) : 0; px = inside ? (int)(m & 0xFFFFu) : 0;
     }
-    bool ok;
-    const long long src = aug_source(d, p.OH, p.OW, py, px, ok);
-    ok = ok && inside;
-    const f16 zero = p.lut[0];
-    bool lit = false;
-    for (int c = 0; c < p.ch; ++c) {
-      const unsigned char v = ok ? d.image[src * p.ch + c] : (unsigned char)0;
-      if (c == 0) lit = ok && (v != 0 || d.keep_dark);
-      p.G[((long long)b * p.ch + c) * plane + o] = v;
-      if (jitter) atomicAdd(&hist[v], 1u);
-    }
-    const f16 wv = lit ? p.lut[d.weight[src]] : zero;
-    for (int c = 0; c < p.C; ++c) {
-      p.y[((long long)b * p.C + c) * plane + o] = lit ? p.lut[d.mask[src * p.C + c]] : zero;
-      p.w[((long long)b * p.C + c) * plane + o] = wv;
-    }
+    aug_gather_pixel(d, p, b, py, px, inside, o, AugStoreBytes{p.G, jitter ? hist : nullptr});
   }
-  if (jitter) {
-    __syncthreads();
-    const unsigned n = hist[threadIdx.x];
-    if (n) atomicAdd(&p.hist[(long long)b * 256 + threadIdx.x], n);
-  }
+  if (jitter) aug_hist_flush(hist, threadIdx.x, p.hist + (long long)b * 256);
 }
 
-// T[b][v] of a jitter sample: one block per sample, one lane per byte value.  The mean is the exact one of the definition: the
-// products in float64, summed by ONE lane in ascending v (a tree would round differently), divided by N, rounded to float32.
+// T[b][v] of a jitter sample: one block per sample, one lane per byte value: the exact mean (augment_common.h: aug_contrast_mean)
+// from lane 0 to every lane, then the jitter of L[v].
 __global__ __launch_bounds__(256) void jitter_table_kernel(AugExtraParams p) {
   __shared__ double term[256];
   __shared__ float mean;
@@ -288,18 +236,10 @@ __global__ __launch_bounds__(256) void jitter_table_kernel(AugExtraParams p) {
   const float br = e.brightness, co = e.contrast;
   const bool contrast_first = e.contrast_first != 0;
   const float L = p.lut32[v];
-  const float entering = contrast_first ? L : aug_clamp01(L * br);
-  term[v] = (double)p.hist[(long long)b * 256 + v] * (double)entering;
+  const float m = aug_contrast_mean(p.hist + (long long)b * 256, v, L, br, contrast_first, (long long)p.ch * p.OH * p.OW, term);
+  if (v == 0) mean = m;
   __syncthreads();
-  if (v == 0) {
-    double acc = 0.0;
-    for (int i = 0; i < 256; ++i) acc += term[i];
-    mean = (float)(acc / (double)((long long)p.ch * p.OH * p.OW));
-  }
-  __syncthreads();
-  float t = aug_clamp01(co * entering + (1.f - co) * mean);
-  if (contrast_first) t = aug_clamp01(t * br);
-  p.T[(long long)b * 256 + v] = t;
+  p.T[(long long)b * 256 + v] = aug_jitter(L, br, co, contrast_first, mean);
 }
 
 // X from the gathered bytes through the sample's table (in LDS): as it is, blurred 5 x 5 with reflecting borders, or with Gaussian
@@ -335,9 +275,7 @@ __global__ __launch_bounds__(256) void augment_finish_kernel(AugExtraParams p) {
       if (kind == 2) {
         unsigned w0, w1;
         philox4x32_10((unsigned)ox, (unsigned)oy, (unsigned)c, 1u, e.nkey[0], e.nkey[1], w0, w1);
-        const float u1 = (float)((w0 >> 8) + 1u) * 0x1p-24f, u2 = (float)(w1 >> 8) * 0x1p-24f;
-        const float z = sqrtf(-2.f * logf(u1)) * cosf(6.2831855f * u2);
-        v = aug_clamp01(v + e.sigma_n * z);
+        v = aug_clamp01(v + e.sigma_n * aug_gauss(w0, w1));
       }
     }
     p.X[((long long)b * p.ch + c) * plane + o] = (f16)v;
@@ -379,17 +317,11 @@ int iunet_augment_batch_extra(const void* descs, const void* extras, int use, in
   IUNET_REQUIRE(descs && extras && lut_f16 && lut_f32 && ws && X && y && w, "augment_batch_extra: null pointer");
   IUNET_REQUIRE(B >= 1 && B <= 65535 && ch >= 1 && ch <= 4 && C >= 1 && C <= 16 && OH >= 1 && OH <= 65535 && OW >= 1 && OW <= 65535,
                 "augment_batch_extra: B %d, channels %d, classes %d, output %d x %d", B, ch, C, OH, OW);
-  IUNET_REQUIRE(use >= 0 && use <= (AUG_ELASTIC | AUG_JITTER | AUG_BLUR | AUG_NOISE), "augment_batch_extra: use %d (bits 1 elastic, 2 jitter, 4 blur, 8 noise)", use);
   const AugWorkspace s = aug_workspace(B, ch, OH, OW);
-  IUNET_REQUIRE(ws_bytes >= s.total, "augment_batch_extra: workspace of %lld bytes, %lld needed (iunet_augment_extra_ws_bytes)", ws_bytes, s.total);
-  const int side = OH < OW ? OH : OW;
-  if (use & AUG_ELASTIC) {
-    IUNET_REQUIRE(taps_f32, "augment_batch_extra: elastic without taps");
-    IUNET_REQUIRE(K >= 1 && K <= AUG_MAX_TAPS && K % 2 == 1, "augment_batch_extra: %d elastic taps (odd, 1 .. %d)", K, AUG_MAX_TAPS);
-    IUNET_REQUIRE(side > K / 2, "augment_batch_extra: a %d x %d output cannot reflect the elastic Gaussian's radius %d (every side must exceed it)", OH, OW, K / 2);
-  }
-  if (use & AUG_BLUR)
-    IUNET_REQUIRE(side > 2, "augment_batch_extra: a %d x %d output cannot reflect the blur's radius 2 (every side must exceed it)", OH, OW);
+  char shape[64];
+  snprintf(shape, sizeof shape, "%d x %d output", OH, OW);
+  const int rc = aug_check_extra("augment_batch_extra", shape, use, taps_f32, K, OH < OW ? OH : OW, ws_bytes, s.total, "iunet_augment_extra_ws_bytes", "side");
+  if (rc != IUNET_OK) return rc;
   AugExtraParams p;
   p.descs = (const AugDesc*)descs; p.extras = (const AugExtraDesc*)extras;
   p.use = use; p.B = B; p.ch = ch; p.C = C; p.OH = OH; p.OW = OW; p.K = (use & AUG_ELASTIC) ? K : 1;
@@ -401,7 +333,7 @@ int iunet_augment_batch_extra(const void* descs, const void* extras, int use, in
   const dim3 grid((OW + 255) / 256, OH, B), block(256);
   if (use & AUG_ELASTIC) {
     hipLaunchKernelGGL(elastic_rows_kernel, grid, block, 0, st, p);
-    hipLaunchKernelGGL(elastic_cols_kernel, dim3((OW + AUG_TILE_X - 1) / AUG_TILE_X, (OH + AUG_TILE_Y - 1) / AUG_TILE_Y, B), block, 0, st, p);
+    hipLaunchKernelGGL(elastic_cols_kernel, dim3((OW + AUG_TILE_X - 1) / AUG_TILE_X, (OH + AUG_TILE_A - 1) / AUG_TILE_A, B), block, 0, st, p);
   }
   if (use & AUG_JITTER) IUNET_CHECK_HIP(hipMemsetAsync(p.hist, 0, 1024 * (size_t)B, st));
   hipLaunchKernelGGL(augment_gather_kernel, dim3(grid.x, (OH + AUG_GATHER_ROWS - 1) / AUG_GATHER_ROWS, B), block, 0, st, p);

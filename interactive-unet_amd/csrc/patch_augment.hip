@@ -16,18 +16,18 @@
 //   jitter_mean_kernel         (jitter)   the contrast mean from the histogram, in float64 in ascending byte value by ONE lane
 //   patch_finish_kernel        (any image transform)  jitter as a tile is loaded, the three 5-tap passes inside the tile (halo 2 on
 //                                         every axis), or Box-Muller noise; one fp16 store
-// No float atomics anywhere: a repeated call gives the same bits.  Lanes run along x.
+// No float atomics anywhere: a repeated call gives the same bits.  Lanes run along x.  What this pipeline has in common with the 2-D
+// batch producer's (augment.hip) -- Philox, the jitter, the contrast mean, the histogram, the elastic passes, the entry point's
+// checks -- is in augment_common.h.
+#include "augment_common.h"
 #include "patch_gather.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int PA_ELASTIC = 1, PA_JITTER = 2, PA_BLUR = 4, PA_NOISE = 8;          // the bits of `use`
-constexpr int PA_MAX_TAPS = 129;                 // cap of the elastic Gaussian's K = int(8 sigma + 1) made odd: sizes the LDS arrays
-
 struct PatchExtraDesc {          // one sample's further transforms (mirrored by interactive_unet/loader.py: PatchExtraDesc)
-  int flags;                     // PA_ELASTIC | PA_JITTER where the sample has them
+  int flags;                     // AUG_ELASTIC | AUG_JITTER where the sample has them
   int kind;                      // 0 neither, 1 blur, 2 noise
   unsigned ekey[2];              // elastic Philox key: low word, high word
   float a2;                      // float32(alpha / 2)
@@ -54,101 +54,52 @@ struct PatchExtraParams {
 struct PatchWorkspace { long long fa, fb, img, hist, mean, total; };      // byte offsets of the workspace's parts
 inline PatchWorkspace patch_workspace(int B, int ch, int SZ, int SY, int SX) {
   const long long vol = (long long)SZ * SY * SX;
-  auto up = [](long long v) { return (v + 255) & ~255LL; };
   PatchWorkspace s;
   s.fa = 0;
-  s.fb = up(12 * B * vol);
-  s.img = s.fb + up(12 * B * vol);
-  s.hist = s.img + up(4 * B * ch * vol);
+  s.fb = aug_align256(12 * B * vol);
+  s.img = s.fb + aug_align256(12 * B * vol);
+  s.hist = s.img + aug_align256(4 * B * ch * vol);
   s.mean = s.hist + 1024LL * B;
-  s.total = s.mean + up(4LL * B);
+  s.total = s.mean + aug_align256(4LL * B);
   return s;
 }
 
-// Philox4x32-10 at counter (c0, c1, c2, c3) under key (k0, k1): words 0 and 1 of the output.  32-bit integer arithmetic: exact.
-__device__ __forceinline__ void pa_philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned& w0,
-                                          unsigned& w1) {
-  const unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const unsigned h0 = __umulhi(M0, c0), l0 = M0 * c0, h1 = __umulhi(M1, c2), l1 = M1 * c2;
-    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  w0 = c0; w1 = c1;
-}
-
-__device__ __forceinline__ int pa_reflect(int p, int n) {       // -1 -> 1, n -> n - 2: no edge repeat; needs |overhang| < n
-  p = p < 0 ? -p : p;
-  return p >= n ? 2 * n - 2 - p : p;
-}
-__device__ __forceinline__ float pa_clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
-
-// Elastic, pass along x.  A block: two rows (oy) of 128 voxels of one z plane of one elastic sample; each row segment's noise plus r
-// on each side is generated once into LDS (one Philox per value, not K per voxel), the K taps are taken from there in ascending order.
+// Elastic, pass along x (augment_common.h: aug_row_pass).  A block: two rows (oy) of 128 voxels of one z plane of one elastic sample,
+// a line of LDS each, the three fields; counter (x, oy, oz, 2 c).
 constexpr int PA_XT = 128, PA_XR = 2;
 __global__ __launch_bounds__(PA_XT * PA_XR) void elastic_x_kernel(PatchExtraParams p) {
-  __shared__ float noise[PA_XR][PA_XT + PA_MAX_TAPS - 1];
+  __shared__ float noise[PA_XR][PA_XT + AUG_MAX_TAPS - 1];
   const int b = blockIdx.z / p.SZ, oz = blockIdx.z - b * p.SZ;
   const PatchExtraDesc& e = p.extras[b];
-  if (!(e.flags & PA_ELASTIC)) return;               // the same in every lane of the block
+  if (!(e.flags & AUG_ELASTIC)) return;              // the same in every lane of the block
   const int x0 = blockIdx.x * PA_XT, oy = blockIdx.y * PA_XR + threadIdx.y, ox = x0 + threadIdx.x;
-  const int r = p.K / 2, span = min(PA_XT, p.SX - x0) + 2 * r;
   const bool row = oy < p.SY;
   const unsigned k0 = e.ekey[0], k1 = e.ekey[1];
   const long long vol = (long long)p.SZ * p.SY * p.SX;
-  float* line = noise[threadIdx.y];
   for (int c = 0; c < 3; ++c) {
-    if (row)
-      for (int t = threadIdx.x; t < span; t += PA_XT) {
-        unsigned w0, w1;
-        pa_philox((unsigned)pa_reflect(x0 - r + t, p.SX), (unsigned)oy, (unsigned)oz, (unsigned)(2 * c), k0, k1, w0, w1);
-        const float u = (float)(w0 >> 8) * 0x1p-24f;
-        line[t] = 2.f * u - 1.f;
-      }
-    __syncthreads();
-    if (row && ox < p.SX) {
-      float acc = 0.f;
-      for (int i = 0; i < p.K; ++i) acc += p.taps[i] * line[threadIdx.x + i];
-      p.fa[((long long)b * 3 + c) * vol + ((long long)oz * p.SY + oy) * p.SX + ox] = acc;
-    }
+    const float acc = aug_row_pass<PA_XT>(noise[threadIdx.y], threadIdx.x, row, x0, p.SX, (unsigned)oy, (unsigned)oz, (unsigned)(2 * c), k0, k1,
+                                          p.taps, p.K);
+    if (row && ox < p.SX) p.fa[((long long)b * 3 + c) * vol + ((long long)oz * p.SY + oy) * p.SX + ox] = acc;
     __syncthreads();
   }
 }
 
-// Elastic, pass along y or z (`axis`: nA voxels, sA elements apart; the other of the two: nO voxels, sO apart).  A block: a tile of 64
-// voxels along x by 32 along the axis, at one position of the other axis, of one elastic sample; the tile plus r before and after
-// (reflected) goes through LDS once per field, so a value is read from memory (32 + 2 r) / 32 times, not K times.  Lane (tx, ty) takes
-// positions ty, ty + 4, ... of column tx; the taps run in ascending order.  `last`: the result is multiplied by a2 -- the displacement.
-constexpr int PA_TILE_X = 64, PA_TILE_A = 32;
-__global__ __launch_bounds__(256) void elastic_axis_kernel(PatchExtraParams p, const float* src, float* dst, int nA, long long sA, int nO,
-                                                           long long sO, int last) {
-  __shared__ float tile[(PA_TILE_A + PA_MAX_TAPS - 1) * PA_TILE_X];
+// Elastic, pass along y or z (augment_common.h: aug_tile_pass; `axis`: nA voxels, sA elements apart; the other of the two: nO voxels,
+// sO apart).  A block: a tile of 64 voxels along x by 32 along the axis, at one position of the other axis, of one elastic sample, the
+// three fields.  `last`: the result is multiplied by a2 -- the displacement.
+__global__ __launch_bounds__(AUG_TILE_LANES) void elastic_axis_kernel(PatchExtraParams p, const float* src, float* dst, int nA, long long sA,
+                                                                      int nO, long long sO, int last) {
+  __shared__ float tile[AUG_TILE_FLOATS];
   const int b = blockIdx.z / nO, other = blockIdx.z - b * nO;
   const PatchExtraDesc& e = p.extras[b];
-  if (!(e.flags & PA_ELASTIC)) return;               // the same in every lane of the block
-  const int x0 = blockIdx.x * PA_TILE_X, a0 = blockIdx.y * PA_TILE_A;
-  const int r = p.K / 2, rows = min(PA_TILE_A, nA - a0) + 2 * r;
-  const int tx = threadIdx.x & (PA_TILE_X - 1), ty = threadIdx.x / PA_TILE_X, ox = x0 + tx;
+  if (!(e.flags & AUG_ELASTIC)) return;              // the same in every lane of the block
+  const int x0 = blockIdx.x * AUG_TILE_X, a0 = blockIdx.y * AUG_TILE_A;
   const long long vol = (long long)p.SZ * p.SY * p.SX;
   const float a2 = e.a2;
   for (int c = 0; c < 3; ++c) {
     const long long base = ((long long)b * 3 + c) * vol + other * sO;
-    for (int t = threadIdx.x; t < rows * PA_TILE_X; t += 256) {
-      const int j = t / PA_TILE_X, gx = x0 + (t & (PA_TILE_X - 1));
-      tile[t] = gx < p.SX ? src[base + pa_reflect(a0 - r + j, nA) * sA + gx] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < PA_TILE_A / 4; ++q) {
-      const int la = ty + 4 * q, oa = a0 + la;
-      if (oa < nA && ox < p.SX) {
-        float acc = 0.f;
-        for (int i = 0; i < p.K; ++i) acc += p.taps[i] * tile[(la + i) * PA_TILE_X + tx];
-        dst[base + oa * sA + ox] = last ? acc * a2 : acc;
-      }
-    }
-    __syncthreads();
+    aug_tile_pass(tile, src + base, x0, a0, p.SX, nA, sA, p.taps, p.K,
+                  [&](int, int oa, int ox, float acc) { dst[base + oa * sA + ox] = last ? acc * a2 : acc; });
   }
 }
 
@@ -191,9 +142,9 @@ __global__ __launch_bounds__(PATCH_TX * PATCH_TY) void patch_gather_extra_kernel
   const int tid = threadIdx.y * PATCH_TX + threadIdx.x;
   const int b = blockIdx.z / p.SZ, oz = blockIdx.z - b * p.SZ, ox = blockIdx.x * PATCH_TX + threadIdx.x;
   const PatchExtraDesc& e = p.extras[b];
-  const bool elastic = p.use & e.flags & PA_ELASTIC, jitter = p.use & e.flags & PA_JITTER;
-  const bool direct = !jitter && !((e.kind == 1 && (p.use & PA_BLUR)) || (e.kind == 2 && (p.use & PA_NOISE)));
-  if (jitter) { hist[tid] = 0; __syncthreads(); }
+  const bool elastic = p.use & e.flags & AUG_ELASTIC, jitter = p.use & e.flags & AUG_JITTER;
+  const bool direct = !jitter && !((e.kind == 1 && (p.use & AUG_BLUR)) || (e.kind == 2 && (p.use & AUG_NOISE)));
+  if (jitter) aug_hist_zero(hist, tid);
   const long long vol = (long long)p.SZ * p.SY * p.SX;
   const float tz = (float)oz - 0.5f * (float)(p.SZ - 1), tx = (float)ox - 0.5f * (float)(p.SX - 1);
   for (int q = 0; q < PA_GATHER_ROWS; ++q) {
@@ -209,39 +160,19 @@ __global__ __launch_bounds__(PATCH_TX * PATCH_TY) void patch_gather_extra_kernel
     PatchStoreExtra sink{p, b, vol, o, jitter ? hist : nullptr, direct};
     patch_gather_voxel(p, b, ez, ey, ex, vol, o, sink);
   }
-  if (jitter) {
-    __syncthreads();
-    const unsigned n = hist[tid];
-    if (n) atomicAdd(&p.hist[(long long)b * 256 + tid], n);
-  }
+  if (jitter) aug_hist_flush(hist, tid, p.hist + (long long)b * 256);
 }
 
-// what enters the contrast step for byte value v: float32(v / 255), or its brightness step when brightness comes first
-__device__ __forceinline__ float pa_entering(int v, const PatchExtraDesc& e) {
-  const float L = (float)v / 255.0f;
-  return e.contrast_first ? L : pa_clamp01(L * e.brightness);
-}
-
-// The contrast mean of a jitter sample: one block per sample, one lane per byte value.  It is the exact one of the definition: the
-// products in float64 in parallel, summed by ONE lane in ascending v (a tree would round differently), divided by N, rounded to float32.
+// The contrast mean of a jitter sample (augment_common.h: aug_contrast_mean): one block per sample, one lane per byte value v,
+// L = float32(v / 255) by one float32 division.
 __global__ __launch_bounds__(256) void jitter_mean_kernel(PatchExtraParams p) {
   __shared__ double term[256];
   const int b = blockIdx.x, v = threadIdx.x;
   const PatchExtraDesc& e = p.extras[b];
-  if (!(e.flags & PA_JITTER)) return;
-  term[v] = (double)p.hist[(long long)b * 256 + v] * (double)pa_entering(v, e);
-  __syncthreads();
-  if (v == 0) {
-    double acc = 0.0;
-    for (int i = 0; i < 256; ++i) acc += term[i];
-    p.mean[b] = (float)(acc / (double)((long long)p.ch * p.SZ * p.SY * p.SX));
-  }
-}
-
-__device__ __forceinline__ float pa_jitter(float x, float br, float co, bool contrast_first, float m) {
-  if (contrast_first) return pa_clamp01(pa_clamp01(co * x + (1.f - co) * m) * br);
-  const float t = pa_clamp01(x * br);
-  return pa_clamp01(co * t + (1.f - co) * m);
+  if (!(e.flags & AUG_JITTER)) return;
+  const float m = aug_contrast_mean(p.hist + (long long)b * 256, v, (float)v / 255.0f, e.brightness, e.contrast_first != 0,
+                                    (long long)p.ch * p.SZ * p.SY * p.SX, term);
+  if (v == 0) p.mean[b] = m;
 }
 
 // X of a sample with an image transform, from the workspace image.  A block: a tile of 4 x 8 x 64 voxels (z, y, x) of one sample.
@@ -258,8 +189,8 @@ __global__ __launch_bounds__(256) void patch_finish_kernel(PatchExtraParams p, i
   __shared__ float S1[PF_ZH * PF_YH * PF_X];         // after the x pass: [PF_ZH][PF_YH][PF_X]
   const int b = blockIdx.z / ztiles, z0 = (blockIdx.z - b * ztiles) * PF_Z, y0 = blockIdx.y * PF_Y, x0 = blockIdx.x * PF_X;
   const PatchExtraDesc& e = p.extras[b];
-  const bool jitter = p.use & e.flags & PA_JITTER;
-  const int kind = (e.kind == 1 && (p.use & PA_BLUR)) ? 1 : (e.kind == 2 && (p.use & PA_NOISE)) ? 2 : 0;
+  const bool jitter = p.use & e.flags & AUG_JITTER;
+  const int kind = (e.kind == 1 && (p.use & AUG_BLUR)) ? 1 : (e.kind == 2 && (p.use & AUG_NOISE)) ? 2 : 0;
   if (!jitter && kind == 0) return;                  // the gather wrote X; the same in every lane of the block
   const int SZ = p.SZ, SY = p.SY, SX = p.SX;
   const long long vol = (long long)SZ * SY * SX;
@@ -278,8 +209,8 @@ __global__ __launch_bounds__(256) void patch_finish_kernel(PatchExtraParams p, i
         const int gx = x0 - PF_H + lx, gy = y0 - PF_H + ly, gz = z0 - PF_H + lz;
         float v = 0.f;                               // beyond the halo of the patch's last voxel: read by no output that is stored
         if (gx < SX + PF_H && gy < SY + PF_H && gz < SZ + PF_H) {
-          v = src[((long long)pa_reflect(gz, SZ) * SY + pa_reflect(gy, SY)) * SX + pa_reflect(gx, SX)];
-          if (jitter) v = pa_jitter(v, br, co, cf, m);
+          v = src[((long long)aug_reflect(gz, SZ) * SY + aug_reflect(gy, SY)) * SX + aug_reflect(gx, SX)];
+          if (jitter) v = aug_jitter(v, br, co, cf, m);
         }
         S0[t] = v;
       }
@@ -315,13 +246,11 @@ __global__ __launch_bounds__(256) void patch_finish_kernel(PatchExtraParams p, i
         if (ox >= SX || oy >= SY || oz >= SZ) continue;
         const long long o = ((long long)oz * SY + oy) * SX + ox;
         float v = src[o];
-        if (jitter) v = pa_jitter(v, br, co, cf, m);
+        if (jitter) v = aug_jitter(v, br, co, cf, m);
         if (kind == 2) {
           unsigned w0, w1;
-          pa_philox((unsigned)ox, (unsigned)oy, (unsigned)oz, (unsigned)(2 * q + 1), e.nkey[0], e.nkey[1], w0, w1);
-          const float u1 = (float)((w0 >> 8) + 1u) * 0x1p-24f, u2 = (float)(w1 >> 8) * 0x1p-24f;
-          const float z = sqrtf(-2.f * logf(u1)) * cosf(6.2831855f * u2);
-          v = pa_clamp01(v + e.sigma_n * z);
+          philox4x32_10((unsigned)ox, (unsigned)oy, (unsigned)oz, (unsigned)(2 * q + 1), e.nkey[0], e.nkey[1], w0, w1);
+          v = aug_clamp01(v + e.sigma_n * aug_gauss(w0, w1));
         }
         dst[o] = (f16)v;
       }
@@ -349,41 +278,37 @@ int iunet_patch_batch_extra(const void* descs, const void* extras, int use, int 
                             void* stream) {
   IUNET_REQUIRE(descs && extras && lut_f16 && ws && X && y && w, "patch_batch_extra: null pointer");
   PATCH_REQUIRE_RANGES("patch_batch_extra", B, ch, C, SZ, SY, SX, order);
-  IUNET_REQUIRE(use >= 0 && use <= (PA_ELASTIC | PA_JITTER | PA_BLUR | PA_NOISE), "patch_batch_extra: use %d (bits 1 elastic, 2 jitter, 4 blur, 8 noise)", use);
   const PatchWorkspace s = patch_workspace(B, ch, SZ, SY, SX);
-  IUNET_REQUIRE(ws_bytes >= s.total, "patch_batch_extra: workspace of %lld bytes, %lld needed (iunet_patch_extra_ws_bytes)", ws_bytes, s.total);
-  const int side = SZ < SY ? (SZ < SX ? SZ : SX) : (SY < SX ? SY : SX);
-  if (use & PA_ELASTIC) {
-    IUNET_REQUIRE(taps_f32, "patch_batch_extra: elastic without taps");
-    IUNET_REQUIRE(K >= 1 && K <= PA_MAX_TAPS && K % 2 == 1, "patch_batch_extra: %d elastic taps (odd, 1 .. %d)", K, PA_MAX_TAPS);
-    IUNET_REQUIRE(side > K / 2, "patch_batch_extra: a %d x %d x %d patch cannot reflect the elastic Gaussian's radius %d (every extent must exceed it)", SZ, SY, SX, K / 2);
+  char shape[64];
+  snprintf(shape, sizeof shape, "%d x %d x %d patch", SZ, SY, SX);
+  const int rc = aug_check_extra("patch_batch_extra", shape, use, taps_f32, K, SZ < SY ? (SZ < SX ? SZ : SX) : (SY < SX ? SY : SX), ws_bytes, s.total,
+                                 "iunet_patch_extra_ws_bytes", "extent");
+  if (rc != IUNET_OK) return rc;
+  if (use & AUG_ELASTIC)
     IUNET_REQUIRE((long long)B * SY <= 65535, "patch_batch_extra: B * SY = %lld exceeds the grid limit 65535 of the elastic passes", (long long)B * SY);
-  }
-  if (use & PA_BLUR)
-    IUNET_REQUIRE(side > 2, "patch_batch_extra: a %d x %d x %d patch cannot reflect the blur's radius 2 (every extent must exceed it)", SZ, SY, SX);
   PatchExtraParams p;
   p.descs = (const PatchDesc*)descs; p.extras = (const PatchExtraDesc*)extras;
-  p.use = use; p.B = B; p.ch = ch; p.C = C; p.SZ = SZ; p.SY = SY; p.SX = SX; p.order = order; p.K = (use & PA_ELASTIC) ? K : 1;
+  p.use = use; p.B = B; p.ch = ch; p.C = C; p.SZ = SZ; p.SY = SY; p.SX = SX; p.order = order; p.K = (use & AUG_ELASTIC) ? K : 1;
   p.lut = (const f16*)lut_f16; p.taps = (const float*)taps_f32;
   char* base = (char*)ws;
   p.fa = (float*)(base + s.fa); p.fb = (float*)(base + s.fb); p.img = (float*)(base + s.img); p.hist = (unsigned*)(base + s.hist);
   p.mean = (float*)(base + s.mean);
   p.X = (f16*)X; p.y = (f16*)y; p.w = (f16*)w;
   const hipStream_t st = (hipStream_t)stream;
-  const int xt = (SX + PA_TILE_X - 1) / PA_TILE_X;
-  if (use & PA_ELASTIC) {
+  const int xt = (SX + AUG_TILE_X - 1) / AUG_TILE_X;
+  if (use & AUG_ELASTIC) {
     const long long sY = SX, sZ = (long long)SY * SX;
     hipLaunchKernelGGL(elastic_x_kernel, dim3((SX + PA_XT - 1) / PA_XT, (SY + PA_XR - 1) / PA_XR, B * SZ), dim3(PA_XT, PA_XR), 0, st, p);
-    hipLaunchKernelGGL(elastic_axis_kernel, dim3(xt, (SY + PA_TILE_A - 1) / PA_TILE_A, B * SZ), dim3(256), 0, st, p, (const float*)p.fa,
+    hipLaunchKernelGGL(elastic_axis_kernel, dim3(xt, (SY + AUG_TILE_A - 1) / AUG_TILE_A, B * SZ), dim3(256), 0, st, p, (const float*)p.fa,
                        p.fb, SY, sY, SZ, sZ, 0);
-    hipLaunchKernelGGL(elastic_axis_kernel, dim3(xt, (SZ + PA_TILE_A - 1) / PA_TILE_A, B * SY), dim3(256), 0, st, p, (const float*)p.fb,
+    hipLaunchKernelGGL(elastic_axis_kernel, dim3(xt, (SZ + AUG_TILE_A - 1) / AUG_TILE_A, B * SY), dim3(256), 0, st, p, (const float*)p.fb,
                        p.fa, SZ, sZ, SY, sY, 1);
   }
-  if (use & PA_JITTER) IUNET_CHECK_HIP(hipMemsetAsync(p.hist, 0, 1024 * (size_t)B, st));
+  if (use & AUG_JITTER) IUNET_CHECK_HIP(hipMemsetAsync(p.hist, 0, 1024 * (size_t)B, st));
   hipLaunchKernelGGL(patch_gather_extra_kernel, dim3((SX + PATCH_TX - 1) / PATCH_TX, (SY + PATCH_TY * PA_GATHER_ROWS - 1) / (PATCH_TY * PA_GATHER_ROWS), B * SZ),
                      dim3(PATCH_TX, PATCH_TY), 0, st, p);
-  if (use & PA_JITTER) hipLaunchKernelGGL(jitter_mean_kernel, dim3(B), dim3(256), 0, st, p);
-  if (use & (PA_JITTER | PA_BLUR | PA_NOISE)) {
+  if (use & AUG_JITTER) hipLaunchKernelGGL(jitter_mean_kernel, dim3(B), dim3(256), 0, st, p);
+  if (use & (AUG_JITTER | AUG_BLUR | AUG_NOISE)) {
     const int ztiles = (SZ + PF_Z - 1) / PF_Z;
     hipLaunchKernelGGL(patch_finish_kernel, dim3((SX + PF_X - 1) / PF_X, (SY + PF_Y - 1) / PF_Y, B * ztiles), dim3(256), 0, st, p, ztiles);
   }

@@ -22,6 +22,7 @@ draws their parameters after each sample's `draw()` and the batch goes through i
 displacement is added to the patch coordinate before the one gather, the intensity transforms follow it -- without a copy to the host.
 """
 import ctypes
+import functools
 import glob
 import math
 import os
@@ -47,11 +48,16 @@ class AugDesc(ctypes.Structure):
 USE_ELASTIC, USE_JITTER, USE_BLUR, USE_NOISE = 1, 2, 4, 8      # iunet_augment_batch_extra's `use` bits; AugExtraDesc.flags has the first two
 
 
+def _extra_fields(blur_name, blur_len):
+    """The fields of the two producers' extended descriptors: the same around the blur coefficients."""
+    return [('flags', ctypes.c_int), ('kind', ctypes.c_int), ('ekey', ctypes.c_uint * 2), ('a2', ctypes.c_float),
+            ('brightness', ctypes.c_float), ('contrast', ctypes.c_float), ('contrast_first', ctypes.c_int),
+            (blur_name, ctypes.c_float * blur_len), ('nkey', ctypes.c_uint * 2), ('sigma_n', ctypes.c_float)]
+
+
 class AugExtraDesc(ctypes.Structure):
     """Mirror of csrc/augment.hip: AugExtraDesc (36 four-byte fields, no padding)."""
-    _fields_ = [('flags', ctypes.c_int), ('kind', ctypes.c_int), ('ekey', ctypes.c_uint * 2), ('a2', ctypes.c_float),
-                ('brightness', ctypes.c_float), ('contrast', ctypes.c_float), ('contrast_first', ctypes.c_int),
-                ('w2', ctypes.c_float * 25), ('nkey', ctypes.c_uint * 2), ('sigma_n', ctypes.c_float)]
+    _fields_ = _extra_fields('w2', 25)
 
 
 def colored_to_categorical(colored_mask):
@@ -176,8 +182,9 @@ def gaussian_taps(sigma, K=None):
     return (g / g.sum()).astype(np.float32)
 
 
-def _fill_extra(d, extra):
-    """One AugExtraDesc from a sample's dict; returns the sample's `use` bits."""
+def _fill_shared(d, extra, write_blur):
+    """One extended descriptor (AugExtraDesc, PatchExtraDesc) from a sample's dict; `write_blur(d, k)` stores the blur's
+    coefficients from its five taps k.  Returns the sample's `use` bits."""
     use = 0
     if 'elastic' in extra:
         e = extra['elastic']
@@ -193,9 +200,8 @@ def _fill_extra(d, extra):
     bn = extra.get('blur_or_noise')
     if bn is not None:
         if bn['kind'] == 'blur':
-            k = gaussian_taps(bn['sigma'], 5)
             d.kind = 1
-            d.w2[:] = (k[:, None] * k[None, :]).reshape(-1).tolist()          # float32 products
+            write_blur(d, gaussian_taps(bn['sigma'], 5))
             use |= USE_BLUR
         elif bn['kind'] == 'noise':
             d.kind = 2
@@ -205,6 +211,36 @@ def _fill_extra(d, extra):
         else:
             raise ValueError(f"blur_or_noise kind {bn['kind']!r}: 'blur' or 'noise'")
     return use
+
+
+def _aug_blur(d, k):
+    d.w2[:] = (k[:, None] * k[None, :]).reshape(-1).tolist()          # float32 products
+
+
+_fill_extra = functools.partial(_fill_shared, write_blur=_aug_blur)      # (d, extra): one AugExtraDesc from a sample's dict -> its `use` bits
+
+
+def _upload_extras(ds, descs, extra, desc_type, fill, size_fn, ws_fn, ws_args, dev):
+    """The tail both datasets' `batch` share on the extended path: the per-sample dicts `extra` into `desc_type` descriptors by
+    `fill`, the layout checked against the library's `size_fn()`, the elastic taps and the workspace (`ws_fn(*ws_args)` bytes) from
+    the caches on `ds`, and ONE upload of `descs` with the new descriptors behind them (both are multiples of 8 bytes).
+    Returns (the uploaded buffer, the pointer to its second part, the batch's `use` bits, taps, workspace)."""
+    B = len(descs)
+    extra = list(extra)
+    if len(extra) != B:
+        raise ValueError(f'extra: {len(extra)} entries for a batch of {B}')
+    extras = (desc_type * B)()
+    use = 0
+    for d, e in zip(extras, extra):
+        use |= fill(d, e or {})
+    assert size_fn() == ctypes.sizeof(desc_type), f'{desc_type.__name__} layout mismatch with libiunet'
+    if ds._taps is None or ds._taps[0] != (ds.elastic_sigma, dev):
+        ds._taps = ((ds.elastic_sigma, dev), torch.from_numpy(gaussian_taps(ds.elastic_sigma)).to(dev))
+    need = nv.answer(ws_fn(*ws_args))
+    if ds._ws is None or ds._ws.device != dev or ds._ws.numel() < need:
+        ds._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    raw = torch.frombuffer(bytearray(bytes(descs) + bytes(extras)), dtype=torch.uint8).to(dev)
+    return raw, ctypes.c_void_p(raw.data_ptr() + ctypes.sizeof(descs)), use, ds._taps[1], ds._ws
 
 
 def _rotation(angle, H, W):
@@ -307,27 +343,15 @@ class UNetDataset:
             with torch.cuda.device(dev):
                 nv.call('iunet_augment_batch', nv.ptr(raw), B, ch, C, OH, OW, nv.ptr(self._lut), nv.ptr(X), nv.ptr(y), nv.ptr(w), nv.stream())
             return X, y, w
-        extra = drawn if extra is None else list(extra)
-        if len(extra) != B:
-            raise ValueError(f'extra: {len(extra)} entries for a batch of {B}')
-        extras = (AugExtraDesc * B)()
-        use = 0
-        for d, e in zip(extras, extra):
-            use |= _fill_extra(d, e or {})
-        assert nv.lib().iunet_augment_extra_desc_bytes() == ctypes.sizeof(AugExtraDesc), 'AugExtraDesc layout mismatch with libiunet'
+        raw, extras, use, taps, ws = _upload_extras(self, descs, drawn if extra is None else extra, AugExtraDesc, _fill_extra,
+                                                    nv.lib().iunet_augment_extra_desc_bytes, nv.lib().iunet_augment_extra_ws_bytes,
+                                                    (B, ch, OH, OW), dev)
         if self._lut32 is None or self._lut32.device != dev:
             self._lut32 = torch.from_numpy((np.arange(256) / 255).astype('float32')).to(dev)
-        if self._taps is None or self._taps[0] != (self.elastic_sigma, dev):
-            self._taps = ((self.elastic_sigma, dev), torch.from_numpy(gaussian_taps(self.elastic_sigma)).to(dev))
-        taps = self._taps[1]
-        need = nv.answer(nv.lib().iunet_augment_extra_ws_bytes(B, ch, OH, OW))
-        if self._ws is None or self._ws.device != dev or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        raw = torch.frombuffer(bytearray(bytes(descs) + bytes(extras)), dtype=torch.uint8).to(dev)      # one upload: AugDesc is a multiple of 8 bytes
         with torch.cuda.device(dev):
-            nv.call('iunet_augment_batch_extra', nv.ptr(raw), ctypes.c_void_p(raw.data_ptr() + ctypes.sizeof(descs)), use, B, ch, C, OH, OW,
-                    nv.ptr(self._lut), nv.ptr(self._lut32), nv.ptr(taps), int(taps.numel()), nv.ptr(self._ws),
-                    int(self._ws.numel()), nv.ptr(X), nv.ptr(y), nv.ptr(w), nv.stream())
+            nv.call('iunet_augment_batch_extra', nv.ptr(raw), extras, use, B, ch, C, OH, OW,
+                    nv.ptr(self._lut), nv.ptr(self._lut32), nv.ptr(taps), int(taps.numel()), nv.ptr(ws),
+                    int(ws.numel()), nv.ptr(X), nv.ptr(y), nv.ptr(w), nv.stream())
         return X, y, w
 
     def __getitem__(self, idx):
@@ -364,7 +388,7 @@ def get_data_loader(set_type='train', num_classes=2, batch_size=2, reslice=False
 
 # ---- the 3-D producer: random oblique patches of annotation volumes ----------------------------------
 class PatchDesc(ctypes.Structure):
-    """Mirror of csrc/patch_batch.hip: PatchDesc."""
+    """Mirror of csrc/patch_gather.h: PatchDesc."""
     _fields_ = [('image', ctypes.c_void_p), ('mask', ctypes.c_void_p), ('weight', ctypes.c_void_p), ('wstride', ctypes.c_int),
                 ('Z', ctypes.c_int), ('Y', ctypes.c_int), ('X', ctypes.c_int), ('m', ctypes.c_float * 9), ('c', ctypes.c_float * 3),
                 ('keep_dark', ctypes.c_int)]
@@ -372,39 +396,14 @@ class PatchDesc(ctypes.Structure):
 
 class PatchExtraDesc(ctypes.Structure):
     """Mirror of csrc/patch_augment.hip: PatchExtraDesc (16 four-byte fields, no padding)."""
-    _fields_ = [('flags', ctypes.c_int), ('kind', ctypes.c_int), ('ekey', ctypes.c_uint * 2), ('a2', ctypes.c_float),
-                ('brightness', ctypes.c_float), ('contrast', ctypes.c_float), ('contrast_first', ctypes.c_int),
-                ('taps', ctypes.c_float * 5), ('nkey', ctypes.c_uint * 2), ('sigma_n', ctypes.c_float)]
+    _fields_ = _extra_fields('taps', 5)
 
 
-def _fill_patch_extra(d, extra):
-    """One PatchExtraDesc from a sample's dict (what `draw_extra` returns); returns the sample's `use` bits."""
-    use = 0
-    if 'elastic' in extra:
-        e = extra['elastic']
-        d.flags |= USE_ELASTIC
-        d.ekey[0], d.ekey[1] = int(e['key']) & 0xFFFFFFFF, (int(e['key']) >> 32) & 0xFFFFFFFF
-        d.a2 = float(e['alpha']) / 2
-        use |= USE_ELASTIC
-    if 'color_jitter' in extra:
-        cj = extra['color_jitter']
-        d.flags |= USE_JITTER
-        d.brightness, d.contrast, d.contrast_first = float(cj['brightness']), float(cj['contrast']), int(bool(cj['contrast_first']))
-        use |= USE_JITTER
-    bn = extra.get('blur_or_noise')
-    if bn is not None:
-        if bn['kind'] == 'blur':
-            d.kind = 1
-            d.taps[:] = gaussian_taps(bn['sigma'], 5).tolist()
-            use |= USE_BLUR
-        elif bn['kind'] == 'noise':
-            d.kind = 2
-            d.nkey[0], d.nkey[1] = int(bn['key']) & 0xFFFFFFFF, (int(bn['key']) >> 32) & 0xFFFFFFFF
-            d.sigma_n = float(bn['sigma'])
-            use |= USE_NOISE
-        else:
-            raise ValueError(f"blur_or_noise kind {bn['kind']!r}: 'blur' or 'noise'")
-    return use
+def _patch_blur(d, k):
+    d.taps[:] = k.tolist()
+
+
+_fill_patch_extra = functools.partial(_fill_shared, write_blur=_patch_blur)      # (d, extra): one PatchExtraDesc from a sample's dict -> its `use` bits
 
 
 def volume_annotations_from_arrays(volumes, device='cuda'):
@@ -605,24 +604,12 @@ class VolumeDataset:
                 nv.call('iunet_patch_batch', nv.ptr(raw), B, ch, C, *self.patch, self.order, nv.ptr(self._lut), nv.ptr(X), nv.ptr(y), nv.ptr(w),
                         nv.stream())
             return X, y, w
-        extra = drawn if extra is None else list(extra)
-        if len(extra) != B:
-            raise ValueError(f'extra: {len(extra)} entries for a batch of {B}')
-        extras = (PatchExtraDesc * B)()
-        use = 0
-        for d, e in zip(extras, extra):
-            use |= _fill_patch_extra(d, e or {})
-        assert nv.lib().iunet_patch_extra_desc_bytes() == ctypes.sizeof(PatchExtraDesc), 'PatchExtraDesc layout mismatch with libiunet'
-        if self._taps is None or self._taps[0] != (self.elastic_sigma, dev):
-            self._taps = ((self.elastic_sigma, dev), torch.from_numpy(gaussian_taps(self.elastic_sigma)).to(dev))
-        taps = self._taps[1]
-        need = nv.answer(nv.lib().iunet_patch_extra_ws_bytes(B, ch, *self.patch))
-        if self._ws is None or self._ws.device != dev or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        raw = torch.frombuffer(bytearray(bytes(descs) + bytes(extras)), dtype=torch.uint8).to(dev)      # one upload: PatchDesc is a multiple of 8 bytes
+        raw, extras, use, taps, ws = _upload_extras(self, descs, drawn if extra is None else extra, PatchExtraDesc, _fill_patch_extra,
+                                                    nv.lib().iunet_patch_extra_desc_bytes, nv.lib().iunet_patch_extra_ws_bytes,
+                                                    (B, ch) + self.patch, dev)
         with torch.cuda.device(dev):
-            nv.call('iunet_patch_batch_extra', nv.ptr(raw), ctypes.c_void_p(raw.data_ptr() + ctypes.sizeof(descs)), use, B, ch, C, *self.patch,
-                    self.order, nv.ptr(self._lut), nv.ptr(taps), int(taps.numel()), nv.ptr(self._ws), int(self._ws.numel()), nv.ptr(X),
+            nv.call('iunet_patch_batch_extra', nv.ptr(raw), extras, use, B, ch, C, *self.patch,
+                    self.order, nv.ptr(self._lut), nv.ptr(taps), int(taps.numel()), nv.ptr(ws), int(ws.numel()), nv.ptr(X),
                     nv.ptr(y), nv.ptr(w), nv.stream())
         return X, y, w
 

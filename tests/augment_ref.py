@@ -135,15 +135,21 @@ def clamp01(x):
     return np.minimum(np.maximum(x, F(0)), F(1))
 
 
+def histogram_mean(byte, entering):
+    """m: the exact mean of entering[v] (float32 [256]: what enters the contrast step for byte value v) over the bytes `byte`
+    (uint8), from their histogram: float64 products summed in ascending v, divided by N, rounded to float32."""
+    hist = np.bincount(byte.reshape(-1), minlength=256)
+    acc = np.float64(0.0)
+    for v in range(256):
+        acc = acc + np.float64(int(hist[v])) * np.float64(entering[v])
+    return F(acc / np.float64(byte.size))
+
+
 def jitter_table(G, b, c, contrast_first):
     """T[v] float32 for the gathered bytes G (uint8, every channel of the sample)."""
     b, c = F(b), F(c)
     entering = LUT32 if contrast_first else clamp01(LUT32 * b)
-    hist = np.bincount(G.reshape(-1), minlength=256)
-    acc = np.float64(0.0)
-    for v in range(256):
-        acc = acc + np.float64(int(hist[v])) * np.float64(entering[v])
-    m = F(acc / np.float64(G.size))
+    m = histogram_mean(G, entering)
     t = clamp01(c * entering + (F(1) - c) * m)
     return clamp01(t * b) if contrast_first else t
 
@@ -162,6 +168,15 @@ def gaussian_blur(J, sigma_b):
     return acc
 
 
+def box_muller(u1, u2):
+    """z = sqrtf(-2 logf(u1)) cosf(6.2831855f u2), logf and cosf taken correctly rounded (float64, then float32)."""
+    logf = np.log(u1.astype(np.float64)).astype(F)
+    ang = F(6.2831855) * u2
+    z = np.sqrt(F(-2) * logf) * np.cos(ang.astype(np.float64)).astype(F)
+    assert z.dtype == F
+    return z
+
+
 def gaussian_noise(J, key, sigma_n):
     """clamp(J + sigma_n z).  logf and cosf are taken correctly rounded (float64, then float32): a device's differ from that by
     float32 ulps, which scaled by sigma_n moves the fp16 rounding of X by one step at most."""
@@ -170,11 +185,7 @@ def gaussian_noise(J, key, sigma_n):
     w = philox4x32((xs, ys, cs, np.uint32(1)), key_words(key))
     u1 = ((w[0] >> np.uint32(8)) + np.uint32(1)).astype(F) * F(2.0 ** -24)
     u2 = (w[1] >> np.uint32(8)).astype(F) * F(2.0 ** -24)
-    logf = np.log(u1.astype(np.float64)).astype(F)
-    ang = F(6.2831855) * u2
-    z = np.sqrt(F(-2) * logf) * np.cos(ang.astype(np.float64)).astype(F)
-    assert z.dtype == F
-    return clamp01(J + F(sigma_n) * z)
+    return clamp01(J + F(sigma_n) * box_muller(u1, u2))
 
 
 def sample(image, mask, weight, params, extra=None, out=(512, 512), sigma=5.0, keep_dark=False):

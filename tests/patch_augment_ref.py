@@ -117,18 +117,13 @@ def gather(image, mask, weight, p, num_classes, order, keep_dark=False):
     return np.stack(xs), np.stack(bytes_), y, w
 
 
-def clamp01(x):
-    return np.minimum(np.maximum(x, F(0)), F(1))
+clamp01 = ar.clamp01
 
 
 def contrast_mean(byte, b, contrast_first):
-    """m: the exact mean of what enters the contrast step, from the histogram of the sample's bytes."""
+    """m: the exact mean of what enters the contrast step, from the histogram of the sample's bytes (augment_ref.histogram_mean)."""
     entering = LUT32 if contrast_first else clamp01(LUT32 * F(b))
-    hist = np.bincount(byte.reshape(-1), minlength=256)
-    acc = np.float64(0.0)
-    for v in range(256):
-        acc = acc + np.float64(int(hist[v])) * np.float64(entering[v])
-    return F(acc / np.float64(byte.size))
+    return ar.histogram_mean(byte, entering)
 
 
 def jitter(x, byte, b, c, contrast_first):
@@ -165,11 +160,7 @@ def gaussian_noise(J, key, sigma_n):
     """clamp(J + sigma_n z).  logf and cosf are taken correctly rounded (float64, then float32): a device's differ from that by
     float32 ulps, which scaled by sigma_n moves the fp16 rounding of X by one step at most."""
     u1, u2 = noise_uniforms(J.shape[0], J.shape[1:], key)
-    logf = np.log(u1.astype(np.float64)).astype(F)
-    ang = F(6.2831855) * u2
-    z = np.sqrt(F(-2) * logf) * np.cos(ang.astype(np.float64)).astype(F)
-    assert z.dtype == F
-    return clamp01(J + F(sigma_n) * z)
+    return clamp01(J + F(sigma_n) * ar.box_muller(u1, u2))
 
 
 def sample(image, mask, weight, m, c, patch, num_classes, order, extra=None, sigma=5.0, keep_dark=False):

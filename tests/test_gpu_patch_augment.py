@@ -3,7 +3,8 @@ definition, tests/patch_augment_ref.py, with imposed parameters: y, w and X bit 
 step and different on at most 0.2 % of the sample's voxels (section 17's gate: the device's logf / cosf against correctly rounded
 ones).  Volumes are 20 x 30 x 40, several patches reach outside them; the patch shapes are the smallest that reach every branch:
 (6, 10, 70) -- one extent barely above the Gaussian's radius, a row longer than one block --, (24, 22, 26) -- no multiple of any
-tile --, and one (44, 42, 48) at the default sigma 5, whose radius 20 needs it."""
+tile --, (4, 5, 150) -- two blocks of the x pass along a row, an odd number of rows, inside its volume along x --, and one (44, 42, 48) at the default sigma 5,
+whose radius 20 needs it."""
 import numpy as np
 import pytest
 import torch
@@ -67,6 +68,19 @@ def _params(patch):
             (0, _flat(pr.signed_permutations()[13] * 0.5), [10.0, 12.5, 20.0])]
 
 
+LONG = (4, 5, 150)
+
+
+def _long_params():
+    """Four samples for the LONG patch whose whole x extent lies inside its volume, so that every column shows the displacement:
+    patch x runs along source x at 0.25 voxels a step (150 x 0.25 = 37.5 of the 40), backwards on one; z and y at scale 1 or 0.5,
+    flipped on two; the third in the dark volume, beside its slab."""
+    return [(0, _flat(np.diag([1.0, 1.0, 0.25])), [9.5, 14.0, 19.5]),
+            (0, _flat(np.diag([-1.0, 0.5, -0.25])), [10.0, 20.5, 19.75]),
+            (1, _flat(np.diag([0.5, 1.0, 0.25])), [6.0, 20.0, 19.5]),
+            (0, _flat(np.diag([1.0, -1.0, 0.25])), [12.5, 8.0, 20.0])]
+
+
 def _compare(got, want, extra, where):
     """One sample: y, w, X bit-equal; a noise sample's X within one fp16 step, differing on at most NOISE_SHARE of its voxels."""
     (X, y, w), (rX, ry, rw) = got, want
@@ -126,10 +140,22 @@ def test_neutral_is_the_plain_producer(order):
 @pytest.mark.parametrize('ch,C,mixes', [(1, 3, (ELASTIC, JITTER, BLUR, ALL_NOISE)), (3, 2, (NOISE, ALL_BLUR, ALL_NOISE, ELASTIC))])
 def test_each_transform_alone_and_all_together(order, ch, C, mixes):
     """(6, 10, 70) at sigma 1 (K = 9: the z extent 6 is barely above the radius 4; a row of 70 crosses a 64-lane block), and
-    (24, 22, 26) at sigma 2.5 (K = 21, radius 10), in batches of four with mixed per-sample settings."""
+    (24, 22, 26) at sigma 2.5 (K = 21, radius 10), in batches of four with mixed per-sample settings; (4, 5, 150) at sigma 0.8
+    (K = 7, radius 3 below the z extent 4): a row of 150 takes a second block of the x pass's 128 lanes, the odd y extent 5 leaves
+    the second row of its last 128 x 2 block idle.  That patch lies inside its volumes along x (`_long_params`), and every elastic
+    sample's mask or weight differs from the plain producer's at ox >= 128 and in row oy = 4: what the second block and the last row
+    wrote is in the compared result."""
     for patch, sigma in (((6, 10, 70), 1.0), ((24, 22, 26), 2.5)):
         _quiet_noise(mixes, ch, patch)
         _check(ch, C, patch, order, _params(patch), list(mixes), sigma, where='mixed')
+    _quiet_noise(mixes, ch, LONG)
+    params = _long_params()
+    got, refs, ds = _check(ch, C, LONG, order, params, list(mixes), 0.8, where='mixed, long rows')
+    plain = [t.cpu().numpy() for t in ds.batch([0, 1, 2, 3], params=params)]
+    for b, e in enumerate(mixes):
+        if 'elastic' in e:
+            moved = (_bits(got[1][b]) != _bits(plain[1][b])).any(0) | (_bits(got[2][b]) != _bits(plain[2][b])).any(0)      # [SZ][SY][SX]
+            assert moved[:, :, 128:].any() and moved[:, 4, :].any() and moved[:, 4, 128:].any(), (b, int(moved.sum()))
 
 
 @pytest.mark.parametrize('order', [0, 1])
