@@ -440,6 +440,21 @@ long long iunet_slice_scatter_workspace_bytes(int sw);
 int iunet_slice_scatter(void* vol, int Z, int Y, int X, int C, const double* geom, int sw, int start, const void* data,
                         void* workspace, void* stream);
 
+/* ---- oblique slab around the slicer's plane (defined bit for bit by tests/slab_ref.py) ----------- */
+/* out[k][i][j] (uint8 [T][sw][sw]) = map_coordinates(vol, ((a * r_i + b * r_j) + n * r_k) + origin, order, mode 'constant'), r_i =
+ * start + i, r_j = start + j, r_k = start_k + k, every product and sum rounded on its own in this order: plane r_k = 0 has the
+ * coordinates of iunet_slice_gather, sampled from the whole volume (no bounding-box crop).  geom: 12 host doubles a[3], b[3], n[3],
+ * origin[3]; orders 0 and 1; T <= 65535. */
+int iunet_slab_gather(const void* vol, int Z, int Y, int X, const double* geom, int T, int sw, int start, int start_k, int order,
+                      void* out, void* stream);
+/* The way back, as a gather over the voxels p of the box [lo, lo + len) (host ints [3], inside the volume; a zero length: nothing
+ * happens) of vol, uint8 [Z][Y][X][C], C = 1 .. 16: with d = p - origin and t_v = (d_0 v_0 + d_1 v_1) + d_2 v_2 for v in (n, a, b),
+ * k = rint(t_n) - start_k, i = rint(t_a) - start, j = rint(t_b) - start (ties to even); where k_lo <= k < k_hi and border <= i, j <
+ * sw - border the voxel becomes uint8(255 * probs[k][i][j][:]) -- the bytes of iunet_normalize_quantize at weight 1 --, every other
+ * byte keeps its value.  probs: fp32 [T][sw][sw][C] on the device; 0 <= k_lo < k_hi <= T; 0 <= 2 border < sw. */
+int iunet_slab_paste(void* vol, int Z, int Y, int X, int C, const double* geom, const int* lo, const int* len, const void* probs,
+                     int T, int sw, int start, int start_k, int k_lo, int k_hi, int border, void* stream);
+
 /* ---- multiscale pyramid (utils.py:29-77 resize_volume / add_multiscales; SURVEY 8f "Zarr block I/O ... 0.5x nearest
  * multiscale pyramid on device") ----------------------------------------------------------------------------------- */
 /* scipy.ndimage.zoom(x, zoom, order=0) index arithmetic for one axis (host only, no GPU): n_out = round-half-even(n_in *

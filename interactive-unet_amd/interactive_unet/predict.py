@@ -292,6 +292,69 @@ def predict_slice(image_slice, num_channels=1, num_classes=2, return_probabiliti
     return rgb.cpu().numpy()
 
 
+# --------------------------------------------------------------------------- the working slice through the 3-D net
+def predict_slab(model, volume, slicer, slice_width=256, depth=32, axis=0, order=1):
+    """The 3-D net on the oblique slab around the slicer's plane: `depth` planes of slice_width^2 pixels gathered from the resident
+    uint8 [Z, Y, X] volume (Slicer.get_slab), one forward.  -> (slab uint8 [T, S, S], cls uint8 [T, S, S], probs fp32 [T, S, S, C]),
+    all on the device; plane T // 2 is the slicer's own plane, the others are the slices its `q` / `a` keys reach."""
+    T, S = int(depth), int(slice_width)
+    if model.dim != 3:
+        raise ValueError('predict_slab needs a 3-D network (a 2-D one predicts the slice itself: predict_slice)')
+    f = 2 ** (model.levels - 1)
+    if T < f or S < f or T % f or S % f:
+        raise ValueError(f'slab {T} x {S} x {S}: depth and slice_width must be positive multiples of {f} ({model.levels} levels)')
+    if not (torch.is_tensor(volume) and volume.is_cuda and volume.dtype == torch.uint8 and volume.dim() == 3):
+        raise ValueError('predict_slab reads a resident volume: a uint8 [Z, Y, X] tensor on the GPU')
+    eng = model.engine('eval')
+    C = eng.ncls
+    with torch.cuda.device(volume.device):
+        slab = slicer.get_slab(volume, axis=axis, slice_width=S, depth=T, order=order)
+        probs = torch.empty((T, S, S, C), dtype=torch.float32, device=volume.device)
+        cls = torch.empty((T, S, S), dtype=torch.uint8, device=volume.device)
+        vox = T * S * S
+        run = lambda: eng.infer(slab, (vox, vox, S * S, S, 1), 1, T, S, S, probs=probs, cls=cls,
+                                out_strides=(vox * C, 1, S * S * C, S * C, C))
+        if hasattr(eng, 'run_checked'):
+            eng.run_checked(run)
+        else:
+            run()
+    return slab, cls, probs
+
+
+def predict_slice_3d(volume, slicer, slice_width=256, depth=32, num_classes=2, return_probabilities=False, model=None, axis=0):
+    """predict_slice for a 3-D model: what the net thinks of the slice being annotated, with the context of the slab around it.
+    Same return contract for the slab's centre plane: palette-coloured uint8 [S, S, 3], or probabilities [1, S, S, C]."""
+    device = volume.device if torch.is_tensor(volume) and volume.is_cuda else torch.device('cuda')
+    if model is None:
+        model = _load_model(1, num_classes, device)
+    _, cls, probs = predict_slab(model, volume, slicer, slice_width=slice_width, depth=depth, axis=axis)
+    S, C, mid = int(slice_width), int(probs.shape[3]), int(depth) // 2
+    if return_probabilities:
+        return probs[mid][None].cpu().numpy()
+    if num_classes < C:                                # argmax over the first num_classes only (rare: host path, as predict_slice)
+        c = np.argmax(probs[mid].cpu().numpy()[..., :num_classes], axis=-1)
+        colored = np.zeros((S, S, 3), dtype='uint8')
+        for i in range(num_classes):
+            colored[c == i, :] = COLORS[i + 1]
+        return colored
+    pal = _palette(device, C)
+    rgb = torch.empty((S, S, 3), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        nv.call('iunet_colorize', nv.ptr(cls[mid]), S * S, nv.ptr(pal), min(num_classes, C), nv.ptr(rgb), nv.stream())
+    return rgb.cpu().numpy()
+
+
+def update_predicted_volume(predicted, probs, slicer, axis=0, margin=None, border=None):
+    """Refresh the resident predicted volume (uint8 [Z, Y, X, C], as predict_volumes writes it) around the slicer's plane from
+    predict_slab's probabilities.  Only the slab's trusted core is pasted: `margin` planes at each end and `border` pixels at each
+    side are dropped, by default a quarter of the extent each -- the outer samples were predicted next to the slab's zero padding,
+    not next to the volume (a whole-volume prediction sees reflected blocks there), so they are the least reliable ones."""
+    T, S = int(probs.shape[0]), int(probs.shape[1])
+    margin = T // 4 if margin is None else int(margin)
+    border = S // 4 if border is None else int(border)
+    return slicer.paste_slab(probs, predicted, axis=axis, planes=(margin, T - margin), border=border)
+
+
 def predict_volume_array(model, volume, input_size=256, num_classes=2, overlap=0.25, batch_size=None,
                          axes=[0, 1, 2], block_range=None, accumulator=None, finalize=True):
     """predict.py:164-256 for one in-memory uint8 volume (numpy or device tensor): block grid,

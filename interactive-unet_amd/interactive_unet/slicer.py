@@ -1,7 +1,8 @@
 """Drop-in for interactive_unet/slicer.py (row a19 of SURVEY.md section 8).  Same class, attributes and method
 signatures; `get_slice` on a uint8 volume that is a CUDA tensor runs on the device (libiunet: iunet_slice_gather,
 bit-exact with the scipy path for orders 0 and 1 -- SURVEY 8f "Slicer on device"), numpy volumes take the reference's
-scipy path;
+scipy path; `get_slab` / `paste_slab` (not in the reference) are the 3-D net's way to the working slice: the oblique slab of planes
+around the slicer's plane, and its prediction written back into a resident volume (iunet_slab_gather / iunet_slab_paste);
 geometry written as small pure helpers (orientation from a rotation vector by Rodrigues'
 formula, plane grids, nearest/linear sampling through scipy) with the reference's numeric
 conventions: 15-decimal rounding then normalisation (slicer.py:22-35), eps-shifted rotation
@@ -176,6 +177,92 @@ class Slicer(object):
         idx = np.array([np.clip(idx[i], 0, volume.shape[i] - 1) for i in range(3)])
         flat = data.ravel() if data.ndim == 2 else data.reshape(-1, data.shape[2])
         volume[idx[0], idx[1], idx[2]] = flat
+        return volume
+
+    # ---- oblique slab around the plane (the 3-D net's interactive prediction: DESIGN.md section 19, tests/slab_ref.py) ----
+    def _slab_geometry(self, axis):
+        """(a, b, n, origin) as float64: the plane vectors of `axis` and the remaining one of (u, v, w), the slab's normal."""
+        a, b = self._plane_vectors(axis)
+        return [np.asarray(t, dtype=float) for t in (a, b, (self.u, self.v, self.w)[axis], self.origin)]
+
+    def get_slab_coords(self, axis=0, slice_width=256, depth=32):
+        """float64 [3, depth, sw, sw]: sample (k, i, j) at ((a r_i + b r_j) + n r_k) + origin, every product and sum rounded on its own
+        in this order, r_k = k - floor(depth / 2): plane depth // 2 is bit for bit get_interpolation_coords(slice_width)[axis]."""
+        a, b, n, o = self._slab_geometry(axis)
+        r = np.arange(slice_width, dtype=float) + int(-np.floor(slice_width / 2))
+        rk = np.arange(depth, dtype=float) + int(-np.floor(depth / 2))
+        ax = lambda t: t[:, None, None, None]
+        plane = ax(a) * r[None, None, :, None] + ax(b) * r[None, None, None, :]
+        return (plane + ax(n) * rk[None, :, None, None]) + ax(o)
+
+    def get_slab(self, volume, axis=0, slice_width=256, depth=32, order=1):
+        """uint8 [depth, sw, sw]: `depth` parallel planes one voxel apart around the slicer's plane (plane depth // 2 is the plane of
+        get_slice; the others are the slices `shift_origin([+-1, 0, 0])` reaches), sampled from the WHOLE volume with
+        map_coordinates(mode='constant'): no bounding-box crop, so the pixels get_slice zeroes at the crop's upper faces carry the
+        real bytes.  A CUDA uint8 volume is gathered on the device (iunet_slab_gather) and the slab stays there; numpy volumes
+        take scipy on the same coordinates."""
+        if slice_width < 1 or depth < 1:
+            raise ValueError(f'slab {depth} x {slice_width} x {slice_width}: every extent must be positive')
+        if not (hasattr(volume, 'is_cuda') and volume.is_cuda):
+            return ndimage.map_coordinates(volume, self.get_slab_coords(axis, slice_width, depth), order=order)
+        import ctypes
+        import torch
+        from . import _native as nv
+        if volume.dtype != torch.uint8 or volume.dim() != 3:
+            raise NotImplementedError('device get_slab handles uint8 [Z, Y, X] volumes')
+        if order not in (0, 1):
+            raise NotImplementedError('device get_slab implements spline orders 0 and 1')
+        volume = volume.contiguous()
+        out = torch.empty((depth, slice_width, slice_width), dtype=torch.uint8, device=volume.device)
+        geom = (ctypes.c_double * 12)(*[float(t) for v in self._slab_geometry(axis) for t in v])
+        with torch.cuda.device(volume.device):
+            nv.call('iunet_slab_gather', nv.ptr(volume), int(volume.shape[0]), int(volume.shape[1]), int(volume.shape[2]), geom,
+                    int(depth), int(slice_width), int(-np.floor(slice_width / 2)), int(-np.floor(depth / 2)), int(order), nv.ptr(out),
+                    nv.stream())
+        return out
+
+    def slab_paste_box(self, volume_shape, axis, slice_width, depth, planes, border):
+        """(lo, length) of the voxels paste_slab has to visit: the bounding box of the kept region's eight corner samples, padded by
+        one voxel (a voxel's nearest sample is at most half a sample step away along n, a and b, i.e. less than sqrt(3) / 2 voxels
+        along an axis) and clipped to the volume."""
+        a, b, n, o = self._slab_geometry(axis)
+        start, start_k = int(-np.floor(slice_width / 2)), int(-np.floor(depth / 2))
+        ends = np.array([start + border, start + slice_width - border - 1], dtype=float)
+        ends_k = np.array([start_k + planes[0], start_k + planes[1] - 1], dtype=float)
+        ax = lambda t: t[:, None, None, None]
+        corners = (ax(a) * ends[None, None, :, None] + ax(b) * ends[None, None, None, :]) + ax(n) * ends_k[None, :, None, None] + ax(o)
+        shape = np.asarray(volume_shape[:3], dtype=int)
+        lo = np.clip(np.floor(corners.min(axis=(1, 2, 3))).astype(int) - 1, 0, shape)
+        hi = np.clip(np.ceil(corners.max(axis=(1, 2, 3))).astype(int) + 2, 0, shape)
+        return lo, np.maximum(hi - lo, 0)
+
+    def paste_slab(self, probs, volume, axis=0, planes=None, border=0):
+        """Write the slab's fp32 probabilities [T, sw, sw, C] (what predict.predict_slab returns) into the resident uint8 volume
+        [Z, Y, X, C] (or [Z, Y, X] for C = 1): every voxel whose nearest slab sample lies in the planes [planes[0], planes[1]) --
+        default: all T -- and at least `border` pixels from the slab's sides becomes uint8(255 * p), the bytes predict_volumes
+        writes; every other voxel keeps its value (iunet_slab_paste: a gather over the region's bounding box, no holes)."""
+        import ctypes
+        import torch
+        from . import _native as nv
+        if not (torch.is_tensor(volume) and volume.is_cuda and volume.dtype == torch.uint8 and volume.dim() in (3, 4)
+                and volume.is_contiguous()):
+            raise NotImplementedError('paste_slab handles resident contiguous uint8 [Z, Y, X] / [Z, Y, X, C] volumes')
+        C = 1 if volume.dim() == 3 else int(volume.shape[3])
+        if not (torch.is_tensor(probs) and probs.dtype == torch.float32 and probs.dim() in (3, 4) and probs.shape[1] == probs.shape[2]
+                and probs.numel() == probs.shape[0] * probs.shape[1] ** 2 * C):
+            raise ValueError(f'probs must be fp32 [T, sw, sw, {C}] for this volume, got {tuple(probs.shape)}')
+        probs = probs.to(volume.device).contiguous()
+        T, sw = int(probs.shape[0]), int(probs.shape[1])
+        k_lo, k_hi = (0, T) if planes is None else (int(planes[0]), int(planes[1]))
+        border = int(border)
+        if not (0 <= k_lo < k_hi <= T) or not (0 <= 2 * border < sw):
+            raise ValueError(f'planes [{k_lo}, {k_hi}) of {T} / border {border} of {sw} pixels keep nothing of the slab')
+        lo, length = self.slab_paste_box(volume.shape, axis, sw, T, (k_lo, k_hi), border)
+        geom = (ctypes.c_double * 12)(*[float(t) for v in self._slab_geometry(axis) for t in v])
+        with torch.cuda.device(volume.device):
+            nv.call('iunet_slab_paste', nv.ptr(volume), int(volume.shape[0]), int(volume.shape[1]), int(volume.shape[2]), C, geom,
+                    nv.int_array(lo), nv.int_array(length), nv.ptr(probs), T, sw, int(-np.floor(sw / 2)), int(-np.floor(T / 2)),
+                    k_lo, k_hi, border, nv.stream())
         return volume
 
     def shift_origin(self, shift_amount=[0, 0, 0]):
