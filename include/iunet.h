@@ -455,6 +455,24 @@ int iunet_slab_gather(const void* vol, int Z, int Y, int X, const double* geom, 
 int iunet_slab_paste(void* vol, int Z, int Y, int X, int C, const double* geom, const int* lo, const int* len, const void* probs,
                      int T, int sw, int start, int start_k, int k_lo, int k_hi, int border, void* stream);
 
+/* ---- where to annotate next: prediction uncertainty (defined bit for bit by tests/propose_ref.py) ----------- */
+/* One pass over a resident predicted volume pred, uint8 [Z][Y][X][C], C = 2 .. 16: u[z][y][x] = 255 - (b1 - b2) with b1 the largest and
+ * b2 the second largest byte of the voxel (with multiplicity: a tie at the top gives 255), 0 where b1 = 0 (never predicted), where any
+ * of the wch (1 or 2) bytes of weight, uint8 [Z][Y][X][wch] or NULL, is > 0 (annotated), and where channel 0 of image, uint8
+ * [Z][Y][X][ich], ich = 1 .. 4, or NULL, is 0 (dark).  bricks[bz][by][bx] (uint32, ceil(dim / brick) entries per axis, brick 4, 8, 16
+ * or 32) = the sum of u over the brick's voxels inside the volume.  u or bricks may be NULL, not both.  Integer arithmetic, no atomics:
+ * the same bits on every launch. */
+int iunet_uncertainty_volume(const void* pred, int Z, int Y, int X, int C, const void* weight, int wch, const void* image, int ich,
+                             int brick, void* u, void* bricks, void* stream);
+/* out[p] (int64 [P][2] on the device) = (sum of u, number of samples) over the samples of plane p that lie inside the volume: sample
+ * (i, j) at c = (a * r_i + b * r_j) + origin, r_i = start + i, r_j = start + j, every product and sum rounded on its own, inside iff 0 <= c
+ * <= dim - 1 on all three axes, reading voxel floor(c + 0.5) -- iunet_slab_gather's plane r_k = 0 at order 0.  u: uint8 [Z][Y][X]; geoms:
+ * P x 9 doubles a[3], b[3], origin[3] ON THE DEVICE; P = 1 .. 65535, sw = 1 .. 4096; ws: iunet_plane_scores_ws_bytes(P, sw) bytes of
+ * device memory (0 = P or sw out of range). */
+long long iunet_plane_scores_ws_bytes(int P, int sw);
+int iunet_plane_scores(const void* u, int Z, int Y, int X, const void* geoms, int P, int sw, int start, void* ws, long long ws_bytes,
+                       void* out, void* stream);
+
 /* ---- multiscale pyramid (utils.py:29-77 resize_volume / add_multiscales; SURVEY 8f "Zarr block I/O ... 0.5x nearest
  * multiscale pyramid on device") ----------------------------------------------------------------------------------- */
 /* scipy.ndimage.zoom(x, zoom, order=0) index arithmetic for one axis (host only, no GPU): n_out = round-half-even(n_in *
