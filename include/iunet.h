@@ -473,6 +473,27 @@ long long iunet_plane_scores_ws_bytes(int P, int sw);
 int iunet_plane_scores(const void* u, int Z, int Y, int X, const void* geoms, int P, int sw, int start, void* ws, long long ws_bytes,
                        void* out, void* stream);
 
+/* ---- symmetry ensemble of the 3-D net: mirror / transpose test-time augmentation (defined bit for bit by
+ * tests/tta_ref.py) ----------- */
+/* A symmetry of the cube is sym = 8 * pi + f, 0 <= sym < 48: pi indexes the permutations of (0, 1, 2) in lexicographic order ((0,1,2),
+ * (0,2,1), (1,0,2), (1,2,0), (2,0,1), (2,1,0)), bit a of f flips OUTPUT axis a.  out (uint8 [m0][m1][m2], m[a] = (D, H, W)[perm[a]]) =
+ * np.flip(np.transpose(in, perm), the flipped axes) of in, uint8 [D][H][W]: out[t] = in[s] with s[perm[a]] = m[a] - 1 - t[a] where bit a
+ * is set, t[a] otherwise.  in and out on the device, not overlapping; D * H * W < 2^42.
+ * Grid rule (both entry points): a launch is a one-dimensional grid of at most 2^24 - 1 workgroups of 256 threads -- one thread per voxel
+ * for pi = 0 and 2 (ceil(D * H * W / 256) workgroups), one tile per workgroup otherwise: 64 x 64 voxels of the plane (axis perm[2], W) here,
+ * TB x 64 in iunet_sym_accumulate (TB = 32 for C <= 2, 16 for C <= 4, else 8), times the extent of the third axis; beyond it the call is
+ * refused. */
+int iunet_sym_block(const void* in, int D, int H, int W, int sym, void* out, void* stream);
+/* Member `index` of `count` (1 .. 48) of the ensemble over one block: P[s][c] = q[t][c] for the same pairing (q: fp32 [m0][m1][m2][C], the
+ * forward's probabilities of the transformed block, C = 1 .. 16), then in the block's own order [D][H][W][C]
+ *   index == 0: sum = mn = mx = P (their previous contents are ignored);  else: sum += P, mn = min(mn, P), mx = max(mx, P);
+ *   index == count - 1, also: mean = sum * inv_count (ONE fp32 multiply: the caller passes float32(1) / float32(count)) and
+ *   spread[s] (fp32 [D][H][W]) = max over c of (mx - mn).
+ * sum, mn, mx: scratch the caller owns across the `count` calls of one block.  mn, mx and spread may be NULL together (the mean only);
+ * mean may be sum; mean is needed on the last call only.  No atomics, every element owned by one thread: the same bits on every launch. */
+int iunet_sym_accumulate(const void* q, int D, int H, int W, int C, int sym, int index, int count, float inv_count,
+                         void* sum, void* mn, void* mx, void* mean, void* spread, void* stream);
+
 /* ---- multiscale pyramid (utils.py:29-77 resize_volume / add_multiscales; SURVEY 8f "Zarr block I/O ... 0.5x nearest
  * multiscale pyramid on device") ----------------------------------------------------------------------------------- */
 /* scipy.ndimage.zoom(x, zoom, order=0) index arithmetic for one axis (host only, no GPU): n_out = round-half-even(n_in *

@@ -15,6 +15,7 @@ import torch
 
 from . import _native as nv
 from . import multiscale
+from . import tta as tta_mod
 
 
 # --------------------------------------------------------------------------- helpers (predict.py:270-411)
@@ -103,6 +104,8 @@ class VolumeAccumulator:
         self.window = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)).to(self.device)
         self.block_probs = torch.empty((self.S,) * 3 + (self.C,), dtype=torch.float32, device=self.device)
         self._batch = None
+        self.spread_pred = self.spread_weight = self.spread_final = None      # the ensemble's spread volume: allocated on request
+        self._ensemble = None
 
     def batch_buffers(self, nb):
         """uint8 [nb, S, S, S] blocks and fp32 [nb, S, S, S, C] probabilities for a batched 3-D forward."""
@@ -111,9 +114,27 @@ class VolumeAccumulator:
                            torch.empty((nb,) + (self.S,) * 3 + (self.C,), dtype=torch.float32, device=self.device))
         return self._batch
 
+    def spread_buffers(self):
+        """A second pair of accumulators, pred [V] / weight [V] float32, and the final uint8 [V] for the symmetry ensemble's spread map
+        (DESIGN.md section 21): allocated by the first call."""
+        if self.spread_pred is None:
+            self.spread_pred = torch.zeros(self.V, dtype=torch.float32, device=self.device)
+            self.spread_weight = torch.zeros(self.V, dtype=torch.float32, device=self.device)
+            self.spread_final = torch.empty(self.V, dtype=torch.uint8, device=self.device)
+        return self.spread_pred, self.spread_weight
+
+    def ensemble(self, spread):
+        """One block's ensemble scratch (tta.Ensemble), with min / max / spread buffers where the spread is wanted."""
+        if self._ensemble is None or (spread and self._ensemble.spread is None):
+            self._ensemble = tta_mod.Ensemble((self.S,) * 3, self.C, self.device, spread=spread)
+        return self._ensemble
+
     def reset(self):
         self.pred.zero_()
         self.weight.zero_()
+        if self.spread_pred is not None:
+            self.spread_pred.zero_()
+            self.spread_weight.zero_()
 
     def blend(self, block, local, probs=None):
         """predict.py:244-245 for one block (clipped volume coords, coords inside the block)."""
@@ -128,6 +149,21 @@ class VolumeAccumulator:
         nv.call('iunet_normalize_quantize', nv.ptr(self.pred), nv.ptr(self.weight), nv.ptr(self.final),
                 self.V[0] * self.V[1] * self.V[2], self.C, float(eps), nv.stream())
         return self.final
+
+    def blend_spread(self, block, local, spread):
+        """blend for the spread map: one channel into the second pair of accumulators."""
+        pred, weight = self.spread_buffers()
+        nv.call('iunet_blend_accumulate', nv.ptr(pred), nv.ptr(weight), nv.ptr(spread), nv.ptr(self.window),
+                self.V[0], self.V[1], self.V[2], 1, self.S, nv.int_array(block), nv.int_array(local), nv.stream())
+
+    def finalize_spread(self, eps=1e-3):
+        """finalize for the spread map: uint8 [V], the window weighting and truncation of the probabilities."""
+        self.spread_buffers()
+        if self.V[0] * self.V[1] * self.V[2] == 0:
+            return self.spread_final
+        nv.call('iunet_normalize_quantize', nv.ptr(self.spread_pred), nv.ptr(self.spread_weight), nv.ptr(self.spread_final),
+                self.V[0] * self.V[1] * self.V[2], 1, float(eps), nv.stream())
+        return self.spread_final
 
 
 def gather_block(volume_dev, padded_coords, S, out=None):
@@ -144,12 +180,30 @@ def gather_block(volume_dev, padded_coords, S, out=None):
 BLOCK_BATCH = 2      # 3-D blocks per forward: the deep levels (16^3, 32^3 per block) fill the chip better, half the launches (4: no further gain)
 
 
-def predict_blocks_3d(eng, acc, volume, blocks, padded, local, lo, hi, batch=None):
+def predict_blocks_3d(eng, acc, volume, blocks, padded, local, lo, hi, batch=None, tta=None, spread_acc=None):
     """Blocks lo..hi-1 of the flat list through the 3-D net, `batch` at a time (gather -> forward + softmax -> blend);
-    the blends happen in list order, so the accumulators are those of the one-block-at-a-time loop."""
+    the blends happen in list order, so the accumulators are those of the one-block-at-a-time loop.
+    `tta` (None, a set name or symmetry codes: tta.members): every block is predicted once per member -- gathered once, transformed per
+    member, `batch` members per forward, accumulated in member order -- and the ensemble's mean is blended; with `spread_acc` true the
+    members' spread is blended into the accumulator's second pair (VolumeAccumulator.spread_buffers)."""
     S, C = acc.S, acc.C
     B = max(1, int(batch or BLOCK_BATCH))
     blk, probs = acc.batch_buffers(B)
+    syms = tta_mod.members(tta)
+    if syms is not None:
+        ens = acc.ensemble(bool(spread_acc))
+        if spread_acc:
+            acc.spread_buffers()
+        one = torch.empty((S, S, S), dtype=torch.uint8, device=acc.device)
+        for i in range(lo, hi):
+            gather_block(volume, padded[i], S, out=one)
+            tta_mod.run(eng, one, syms, ens, acc.block_probs, batch=B, blk=blk, probs=probs)
+            acc.blend(blocks[i], local[i])
+            if spread_acc:
+                acc.blend_spread(blocks[i], local[i], ens.spread)
+        return
+    if spread_acc:
+        raise ValueError('a spread map needs an ensemble: pass tta')
     for i in range(lo, hi, B):
         nb = min(B, hi - i)
         for j in range(nb):
@@ -293,11 +347,14 @@ def predict_slice(image_slice, num_channels=1, num_classes=2, return_probabiliti
 
 
 # --------------------------------------------------------------------------- the working slice through the 3-D net
-def predict_slab(model, volume, slicer, slice_width=256, depth=32, axis=0, order=1):
+def predict_slab(model, volume, slicer, slice_width=256, depth=32, axis=0, order=1, tta=None):
     """The 3-D net on the oblique slab around the slicer's plane: `depth` planes of slice_width^2 pixels gathered from the resident
     uint8 [Z, Y, X] volume (Slicer.get_slab), one forward.  -> (slab uint8 [T, S, S], cls uint8 [T, S, S], probs fp32 [T, S, S, C]),
-    all on the device; plane T // 2 is the slicer's own plane, the others are the slices its `q` / `a` keys reach."""
+    all on the device; plane T // 2 is the slicer's own plane, the others are the slices its `q` / `a` keys reach.
+    `tta` (tta.members): one forward per member on the transformed slab; probs is the ensemble's mean and cls its argmax (the first
+    maximum: torch.argmax's documented rule).  Any member is legal: a permuted slab is still a multiple of 2^(levels - 1) on every axis."""
     T, S = int(depth), int(slice_width)
+    syms = tta_mod.members(tta)
     if model.dim != 3:
         raise ValueError('predict_slab needs a 3-D network (a 2-D one predicts the slice itself: predict_slice)')
     f = 2 ** (model.levels - 1)
@@ -312,22 +369,28 @@ def predict_slab(model, volume, slicer, slice_width=256, depth=32, axis=0, order
         probs = torch.empty((T, S, S, C), dtype=torch.float32, device=volume.device)
         cls = torch.empty((T, S, S), dtype=torch.uint8, device=volume.device)
         vox = T * S * S
-        run = lambda: eng.infer(slab, (vox, vox, S * S, S, 1), 1, T, S, S, probs=probs, cls=cls,
-                                out_strides=(vox * C, 1, S * S * C, S * C, C))
+        if syms is None:
+            run = lambda: eng.infer(slab, (vox, vox, S * S, S, 1), 1, T, S, S, probs=probs, cls=cls,
+                                    out_strides=(vox * C, 1, S * S * C, S * C, C))
+        else:
+            ens = tta_mod.Ensemble((T, S, S), C, volume.device)
+            run = lambda: tta_mod.run(eng, slab, syms, ens, probs)
         if hasattr(eng, 'run_checked'):
             eng.run_checked(run)
         else:
             run()
+        if syms is not None:
+            cls.copy_(torch.argmax(probs, dim=-1))
     return slab, cls, probs
 
 
-def predict_slice_3d(volume, slicer, slice_width=256, depth=32, num_classes=2, return_probabilities=False, model=None, axis=0):
+def predict_slice_3d(volume, slicer, slice_width=256, depth=32, num_classes=2, return_probabilities=False, model=None, axis=0, tta=None):
     """predict_slice for a 3-D model: what the net thinks of the slice being annotated, with the context of the slab around it.
     Same return contract for the slab's centre plane: palette-coloured uint8 [S, S, 3], or probabilities [1, S, S, C]."""
     device = volume.device if torch.is_tensor(volume) and volume.is_cuda else torch.device('cuda')
     if model is None:
         model = _load_model(1, num_classes, device)
-    _, cls, probs = predict_slab(model, volume, slicer, slice_width=slice_width, depth=depth, axis=axis)
+    _, cls, probs = predict_slab(model, volume, slicer, slice_width=slice_width, depth=depth, axis=axis, tta=tta)
     S, C, mid = int(slice_width), int(probs.shape[3]), int(depth) // 2
     if return_probabilities:
         return probs[mid][None].cpu().numpy()
@@ -356,11 +419,19 @@ def update_predicted_volume(predicted, probs, slicer, axis=0, margin=None, borde
 
 
 def predict_volume_array(model, volume, input_size=256, num_classes=2, overlap=0.25, batch_size=None,
-                         axes=[0, 1, 2], block_range=None, accumulator=None, finalize=True):
+                         axes=[0, 1, 2], block_range=None, accumulator=None, finalize=True, tta=None, return_spread=False):
     """predict.py:164-256 for one in-memory uint8 volume (numpy or device tensor): block grid,
     reflect-padded blocks, block prediction (2.5-D with a 2-D model, direct with a 3-D model),
     Gaussian blend, normalise + quantise.  Returns the uint8 [V, C] device tensor.
-    `block_range=(lo, hi)` restricts to a contiguous run of the flat block list (multi-GPU)."""
+    `block_range=(lo, hi)` restricts to a contiguous run of the flat block list (multi-GPU).
+    `tta` (3-D models; None, a set name or symmetry codes: tta.members): every block is the mean over the members of the symmetry
+    ensemble.  With `return_spread` the result is (pred, spread_u8): uint8 [V], the members' largest per-class
+    disagreement, blended and quantised like the probabilities (with finalize=False it stays on the accumulator: finalize_spread)."""
+    syms = tta_mod.members(tta)
+    if return_spread and syms is None:
+        raise ValueError('return_spread needs an ensemble: pass tta')
+    if syms is not None and model.dim != 3:
+        raise ValueError("tta is the 3-D net's ensemble: a 2-D model already averages its three slicing axes (axes=)")
     dev = model.device
     vol = volume if torch.is_tensor(volume) else torch.from_numpy(np.ascontiguousarray(volume))
     vol = vol.to(dev)
@@ -371,14 +442,16 @@ def predict_volume_array(model, volume, input_size=256, num_classes=2, overlap=0
     lo, hi = (0, len(pbc)) if block_range is None else block_range
     eng = model.engine('eval')
     if eng.dim == 3:
-        predict_blocks_3d(eng, acc, vol, bc, pbc, lbc, lo, hi)
+        predict_blocks_3d(eng, acc, vol, bc, pbc, lbc, lo, hi, tta=syms, spread_acc=bool(return_spread))
     else:
         blk = torch.empty((S, S, S), dtype=torch.uint8, device=dev)
         for i in range(lo, hi):
             gather_block(vol, pbc[i], S, out=blk)
             predict_block_device(model, blk, acc.block_probs, C, batch_size, axes)
             acc.blend(bc[i], lbc[i])
-    return acc.finalize() if finalize else acc
+    if not finalize:
+        return acc
+    return (acc.finalize(), acc.finalize_spread()) if return_spread else acc.finalize()
 
 
 def predict_volumes(input_size=256, num_channels=1, num_classes=2, overlap=0.25, chunk_size=128, shard_size=256,
