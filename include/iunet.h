@@ -494,6 +494,27 @@ int iunet_sym_block(const void* in, int D, int H, int W, int sym, void* out, voi
 int iunet_sym_accumulate(const void* q, int D, int H, int W, int C, int sym, int index, int count, float inv_count,
                          void* sum, void* mn, void* mx, void* mean, void* spread, void* stream);
 
+/* ---- connected components of a resident volume: label, measure, filter (defined bit for bit by
+ * tests/components_ref.py) ----------- */
+/* src: uint8 on the device; C == 1: a class map [Z][Y][X]; C = 2 .. 16: a predicted volume [Z][Y][X][C], a voxel's class = the index of
+ * its largest byte (the lowest index on a tie), a voxel whose bytes are all 0 belongs to no component.  background = -1 (every class is
+ * labelled) or 0 .. 255 (voxels of that class belong to no component).  connectivity 6, 18 or 26.  Two voxels are connected if they are
+ * neighbours, have the same class and are both foreground; components are numbered 1 .. K in increasing order of their first voxel
+ * (smallest raster index (z Y + y) X + x).  labels: int32 [Z][Y][X], 0 = no component; cls: NULL or uint8 [Z][Y][X], the class map
+ * that was labelled; count: one int32 on the device, K; ws: iunet_cc_ws_bytes(Z, Y, X) bytes of device memory (0 = refused: a dimension
+ * < 1 or Z Y X > 2^31 - 1).  Integer atomics only (minima): the same bits on every launch. */
+long long iunet_cc_ws_bytes(int Z, int Y, int X);
+int iunet_cc_label(const void* src, int Z, int Y, int X, int C, int connectivity, int background,
+                   void* labels, void* cls, void* count, void* ws, long long ws_bytes, void* stream);
+/* The table of labels 0 .. K of (labels, cls): sizes int32 [K + 1] (entry 0 = 0), classes uint8 [K + 1] (entry 0 = 0), first int32
+ * [K + 1]: the raster index of the component's first voxel (entry 0 = -1).  Integer sums and minima. */
+int iunet_cc_table(const void* labels, const void* cls, int Z, int Y, int X, int K,
+                   void* sizes, void* classes, void* first, void* stream);
+/* out[v] (uint8 [Z][Y][X]) = keep[labels[v]] ? cls[v] : fill where labels[v] > 0, cls[v] elsewhere; keep: uint8 [K + 1] on the device;
+ * fill 0 .. 255; out may be cls. */
+int iunet_cc_filter(const void* labels, const void* cls, int Z, int Y, int X, int K, const void* keep, int fill,
+                    void* out, void* stream);
+
 /* ---- multiscale pyramid (utils.py:29-77 resize_volume / add_multiscales; SURVEY 8f "Zarr block I/O ... 0.5x nearest
  * multiscale pyramid on device") ----------------------------------------------------------------------------------- */
 /* scipy.ndimage.zoom(x, zoom, order=0) index arithmetic for one axis (host only, no GPU): n_out = round-half-even(n_in *
