@@ -515,6 +515,30 @@ int iunet_cc_table(const void* labels, const void* cls, int Z, int Y, int X, int
 int iunet_cc_filter(const void* labels, const void* cls, int Z, int Y, int X, int K, const void* keep, int fill,
                     void* out, void* stream);
 
+/* ---- exact squared Euclidean distance transform of a resident volume and ball morphology by thresholds of it (DESIGN.md section 23;
+ * defined bit for bit by tests/morphology_ref.py) ----------- */
+/* src: uint8 on the device, as above: C == 1 a class map [Z][Y][X] (every voxel has the class of its byte); C = 2 .. 16 a predicted
+ * volume [Z][Y][X][C], class = the index of the largest byte (the lowest on a tie), a voxel whose bytes are all 0 has no class and 0 in
+ * the class map.  A = {v: v has a class and it is `target`} (target 0 .. 255); the seeds are S = A (invert 0) or its complement, the
+ * never-predicted voxels included (invert 1); voxels outside the volume are never seeds.
+ * d2: NULL or int32 [Z][Y][X], d2[v] = min over s in S of |v - s|^2 -- 0 on S, INF = 2^31 - 1 everywhere when S is empty; cls: NULL or
+ * uint8 [Z][Y][X], the class map; not both NULL, and d2 == NULL is the class-map pass alone (ws is not read).
+ * Limits: Z Y X <= 2^31 - 1 and (Z-1)^2 + (Y-1)^2 + (X-1)^2 <= 2^31 - 2 (every finite distance is below INF; every axis <= 46341).
+ * ws: iunet_edt_ws_bytes(Z, Y, X) bytes of device memory, 8 per voxel (0 = refused: a dimension < 1 or a limit passed).  Three separable
+ * passes, in place on d2: rows (class, membership, nearest seed left and right), then the exact lower envelope of the columns along Y and
+ * along Z (Meijster's two scans, integers).  No atomics, every element owned by one thread: the same bits on every launch. */
+long long iunet_edt_ws_bytes(int Z, int Y, int X);
+int iunet_edt_sq(const void* src, int Z, int Y, int X, int C, int target, int invert,
+                 void* d2, void* cls, void* ws, long long ws_bytes, void* stream);
+/* The same transform with the seeds read off an earlier distance map: S = {prev > r2} (above 1) or {prev <= r2} (above 0); prev int32
+ * [Z][Y][X]; 0 <= r2 <= 2^31 - 2.  d2 and prev do not overlap. */
+int iunet_edt_sq_mask(const void* prev, int Z, int Y, int X, int r2, int above,
+                      void* d2, void* ws, long long ws_bytes, void* stream);
+/* out[v] (uint8 [Z][Y][X]) = value where cond(d2[v]) and (only < 0 or cls[v] == only), cls[v] elsewhere; cond = d2 > r2 (above 1) or
+ * d2 <= r2 (above 0); only -1 .. 255, value 0 .. 255, 0 <= r2 <= 2^31 - 2; out may be cls.  One streaming pass. */
+int iunet_edt_select(const void* d2, const void* cls, int Z, int Y, int X, int r2, int above, int only, int value,
+                     void* out, void* stream);
+
 /* ---- multiscale pyramid (utils.py:29-77 resize_volume / add_multiscales; SURVEY 8f "Zarr block I/O ... 0.5x nearest
  * multiscale pyramid on device") ----------------------------------------------------------------------------------- */
 /* scipy.ndimage.zoom(x, zoom, order=0) index arithmetic for one axis (host only, no GPU): n_out = round-half-even(n_in *
