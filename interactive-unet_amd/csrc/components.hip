@@ -20,8 +20,9 @@
 //   apply_kernel    labels[v] = P[labels[v] - 1].
 //   table kernels   sizes by atomicAdd and first by atomicMin, one pair per (workgroup, label): equal labels next to each other are
 //                   summed in the wave by ballot, then in the workgroup in a table in LDS.
-//   filter_kernel   one streaming pass.
+//   the filter      one streaming pass: volume_select_kernel (volume_rules.h) with FilterPick.
 #include "common.h"
+#include "volume_rules.h"
 #include <cstdint>
 
 namespace {
@@ -75,20 +76,12 @@ __device__ __forceinline__ void lds_unite(int* L, int a, int b) {
   }
 }
 
+// the voxel's class (volume_top_byte, volume_rules.h); a voxel of no component: -1 for a class map, -1 - class for a predicted volume
 template <int CT>
 __device__ __forceinline__ int voxel_class(const CcParams& p, long long v) {
-  if (CT == 1) {
-    const int c = p.src[v];
-    return c == p.background ? -1 : c;
-  }
-  const unsigned char* q = p.src + v * p.C;          // 64-bit: Z Y X C passes 2^31
-  int best = q[0], at = 0;
-  const int n = CT == 2 ? 2 : p.C;
-  for (int c = 1; c < n; ++c) {
-    const int t = q[c];
-    if (t > best) { best = t; at = c; }
-  }
-  return (best == 0 || at == p.background) ? -1 - at : at;      // no component: -1 - class
+  const TopByte t = volume_top_byte<CT>(p.src, v, p.C);
+  if (CT == 1) return t.at == p.background ? -1 : t.at;
+  return (t.best == 0 || t.at == p.background) ? -1 - t.at : t.at;
 }
 
 // CT: 1 a class map, 2 two classes, 0 any number; LV: the structure's rank (1, 2, 3 = connectivity 6, 18, 26), so that the offsets it
@@ -412,36 +405,16 @@ __global__ __launch_bounds__(CC_THREADS) void table_classes_kernel(const unsigne
   classes[k] = (at >= 0 && at < N) ? cls[at] : 0;
 }
 
-// V voxels per thread and step: 4 where labels, cls and out are aligned for 16- and 4-byte accesses, else 1
-template <int V>
-__global__ __launch_bounds__(CC_THREADS) void filter_kernel(const int* labels, const unsigned char* cls, const unsigned char* keep, int K,
-                                                            int fill, unsigned char* out, long long N) {
-  const long long base = (long long)blockIdx.x * CC_CHUNK;
-  for (int s = 0; s < CC_STEPS / V; ++s) {               // fixed trip count
-    const long long v = base + ((long long)s * CC_THREADS + threadIdx.x) * V;
-    if (v >= N) break;
-    if (V == 4 && v + 4 <= N) {
-      const int4 l = *(const int4*)(labels + v);
-      uchar4 c = *(const uchar4*)(cls + v);
-      if (l.x > 0 && l.x <= K && !keep[l.x]) c.x = (unsigned char)fill;
-      if (l.y > 0 && l.y <= K && !keep[l.y]) c.y = (unsigned char)fill;
-      if (l.z > 0 && l.z <= K && !keep[l.z]) c.z = (unsigned char)fill;
-      if (l.w > 0 && l.w <= K && !keep[l.w]) c.w = (unsigned char)fill;
-      *(uchar4*)(out + v) = c;
-    } else {
-      for (int j = 0; j < V && v + j < N; ++j) {
-        const int l = labels[v + j];
-        const unsigned char c = cls[v + j];
-        out[v + j] = (l > 0 && l <= K && !keep[l]) ? (unsigned char)fill : c;
-      }
-    }
+// the filter's rule for volume_select_kernel: the voxels of a component that is not kept take `fill`
+struct FilterPick {
+  const unsigned char* keep;
+  int K, fill;
+  __device__ __forceinline__ unsigned char operator()(int l, unsigned char c) const {
+    return (l > 0 && l <= K && !keep[l]) ? (unsigned char)fill : c;
   }
-}
+};
 
-inline long long cc_align16(long long n) { return (n + 15) & ~15ll; }
 inline long long cc_chunks(long long N) { return (N + CC_CHUNK - 1) / CC_CHUNK; }
-
-inline bool cc_volume_ok(int Z, int Y, int X) { return Z > 0 && Y > 0 && X > 0 && (long long)Z * Y * X <= CC_MAX_VOX; }
 
 }  // namespace
 
@@ -449,16 +422,16 @@ extern "C" {
 
 // the workspace: P int32 [N] | key uint8 [N] | counts int32 [ceil(N / CC_CHUNK)], each part a multiple of 16 bytes
 long long iunet_cc_ws_bytes(int Z, int Y, int X) {
-  if (!cc_volume_ok(Z, Y, X)) return 0;
+  if (!volume_ok(Z, Y, X, CC_MAX_VOX)) return 0;
   const long long N = (long long)Z * Y * X;
-  return cc_align16(4 * N) + cc_align16(N) + cc_align16(4 * cc_chunks(N));
+  return volume_align16(4 * N) + volume_align16(N) + volume_align16(4 * cc_chunks(N));
 }
 
 int iunet_cc_label(const void* src, int Z, int Y, int X, int C, int connectivity, int background,
                    void* labels, void* cls, void* count, void* ws, long long ws_bytes, void* stream) {
   IUNET_REQUIRE(src && labels && count && ws, "cc_label: null pointer (src, labels, count, ws)");
-  IUNET_REQUIRE(Z > 0 && Y > 0 && X > 0, "cc_label: volume %d x %d x %d: a dimension below 1", Z, Y, X);
-  IUNET_REQUIRE(cc_volume_ok(Z, Y, X), "cc_label: volume %d x %d x %d: more than 2^31 - 1 voxels", Z, Y, X);
+  VOLUME_REQUIRE_DIMS("cc_label", Z, Y, X);
+  IUNET_REQUIRE(volume_ok(Z, Y, X, CC_MAX_VOX), "cc_label: volume %d x %d x %d: more than 2^31 - 1 voxels", Z, Y, X);
   IUNET_REQUIRE(C >= 1 && C <= 16, "cc_label: %d classes outside 1..16", C);
   IUNET_REQUIRE(connectivity == 6 || connectivity == 18 || connectivity == 26, "cc_label: connectivity %d (6, 18 or 26)", connectivity);
   IUNET_REQUIRE(background >= -1 && background <= 255, "cc_label: background %d outside -1..255", background);
@@ -468,12 +441,12 @@ int iunet_cc_label(const void* src, int Z, int Y, int X, int C, int connectivity
   hipStream_t st = (hipStream_t)stream;
   CcParams p;
   p.src = (const unsigned char*)src; p.P = (int*)ws; p.cls = (unsigned char*)cls;
-  p.key = (unsigned char*)ws + cc_align16(4 * N);
-  int* counts = (int*)((unsigned char*)ws + cc_align16(4 * N) + cc_align16(N));
+  p.key = (unsigned char*)ws + volume_align16(4 * N);
+  int* counts = (int*)((unsigned char*)ws + volume_align16(4 * N) + volume_align16(N));
   p.Z = Z; p.Y = Y; p.X = X; p.C = C; p.level = connectivity == 6 ? 1 : connectivity == 18 ? 2 : 3; p.background = background;
   p.nty = (Y + CC_TY - 1) / CC_TY; p.ntx = (X + CC_TX - 1) / CC_TX;
   p.ntiles = (long long)((Z + CC_TZ - 1) / CC_TZ) * p.nty * p.ntx;
-  const unsigned int tgrid = (unsigned int)(p.ntiles < CC_MAX_TILE_GRID ? p.ntiles : CC_MAX_TILE_GRID);
+  const unsigned int tgrid = volume_grid(p.ntiles, CC_MAX_TILE_GRID);
   void (*tile[3][3])(CcParams) = {{tile_kernel<0, 1>, tile_kernel<0, 2>, tile_kernel<0, 3>},
                                   {tile_kernel<1, 1>, tile_kernel<1, 2>, tile_kernel<1, 3>},
                                   {tile_kernel<2, 1>, tile_kernel<2, 2>, tile_kernel<2, 3>}};
@@ -500,8 +473,8 @@ int iunet_cc_label(const void* src, int Z, int Y, int X, int C, int connectivity
 int iunet_cc_table(const void* labels, const void* cls, int Z, int Y, int X, int K,
                    void* sizes, void* classes, void* first, void* stream) {
   IUNET_REQUIRE(labels && cls && sizes && classes && first, "cc_table: null pointer");
-  IUNET_REQUIRE(Z > 0 && Y > 0 && X > 0, "cc_table: volume %d x %d x %d: a dimension below 1", Z, Y, X);
-  IUNET_REQUIRE(cc_volume_ok(Z, Y, X), "cc_table: volume %d x %d x %d: more than 2^31 - 1 voxels", Z, Y, X);
+  VOLUME_REQUIRE_DIMS("cc_table", Z, Y, X);
+  IUNET_REQUIRE(volume_ok(Z, Y, X, CC_MAX_VOX), "cc_table: volume %d x %d x %d: more than 2^31 - 1 voxels", Z, Y, X);
   IUNET_REQUIRE(K >= 0 && K <= (long long)Z * Y * X, "cc_table: %d components outside 0..the number of voxels", K);
   IUNET_REQUIRE((((uintptr_t)labels | (uintptr_t)sizes | (uintptr_t)first) & 3) == 0, "cc_table: labels, sizes and first must be 4-byte aligned");
   const long long N = (long long)Z * Y * X;
@@ -523,18 +496,13 @@ int iunet_cc_table(const void* labels, const void* cls, int Z, int Y, int X, int
 int iunet_cc_filter(const void* labels, const void* cls, int Z, int Y, int X, int K, const void* keep, int fill,
                     void* out, void* stream) {
   IUNET_REQUIRE(labels && cls && keep && out, "cc_filter: null pointer");
-  IUNET_REQUIRE(Z > 0 && Y > 0 && X > 0, "cc_filter: volume %d x %d x %d: a dimension below 1", Z, Y, X);
-  IUNET_REQUIRE(cc_volume_ok(Z, Y, X), "cc_filter: volume %d x %d x %d: more than 2^31 - 1 voxels", Z, Y, X);
+  VOLUME_REQUIRE_DIMS("cc_filter", Z, Y, X);
+  IUNET_REQUIRE(volume_ok(Z, Y, X, CC_MAX_VOX), "cc_filter: volume %d x %d x %d: more than 2^31 - 1 voxels", Z, Y, X);
   IUNET_REQUIRE(K >= 0 && K <= (long long)Z * Y * X, "cc_filter: %d components outside 0..the number of voxels", K);
   IUNET_REQUIRE(fill >= 0 && fill <= 255, "cc_filter: fill %d outside 0..255", fill);
   IUNET_REQUIRE(((uintptr_t)labels & 3) == 0, "cc_filter: labels must be 4-byte aligned");
   const long long N = (long long)Z * Y * X;
-  const unsigned int chunks = (unsigned int)cc_chunks(N);
-  const bool wide = ((uintptr_t)labels & 15) == 0 && (((uintptr_t)cls | (uintptr_t)out) & 3) == 0;
-  if (wide) hipLaunchKernelGGL(filter_kernel<4>, dim3(chunks), dim3(CC_THREADS), 0, (hipStream_t)stream, (const int*)labels,
-                               (const unsigned char*)cls, (const unsigned char*)keep, K, fill, (unsigned char*)out, N);
-  else hipLaunchKernelGGL(filter_kernel<1>, dim3(chunks), dim3(CC_THREADS), 0, (hipStream_t)stream, (const int*)labels,
-                          (const unsigned char*)cls, (const unsigned char*)keep, K, fill, (unsigned char*)out, N);
+  volume_select_launch<CC_CHUNK, CC_THREADS>(labels, cls, FilterPick{(const unsigned char*)keep, K, fill}, out, N, (hipStream_t)stream);
   IUNET_CHECK_HIP(hipGetLastError());
   return IUNET_OK;
 }

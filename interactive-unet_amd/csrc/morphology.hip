@@ -16,7 +16,8 @@
 //                   f = INF never enter the envelope (the sums below would overflow).  The stack (site uint16, start uint16, f int32 = one 8-byte
 //                   entry per voxel, laid out [k][column] like the volume) lives in the workspace: the pass runs in place on d2 -- the
 //                   forward scan reads the whole column before the backward scan writes it, and the backward scan reads f from the stack.
-//   select_kernel   one streaming pass: out = value where the distance passes the threshold (and the class is `only`), else cls.
+//   the select      one streaming pass, volume_select_kernel (volume_rules.h) with SelectPick: out = value where the distance passes the
+//                   threshold (and the class is `only`), else cls.
 //
 // Ranges.  Every axis <= 46341 and (Z-1)^2 + (Y-1)^2 + (X-1)^2 <= 2^31 - 2, so a finite f(i) + (u - i)^2 is a true squared distance
 // inside the volume or the sum of one (< 2^31) and a square (< 2^31): below 2^32, compared as unsigned.  The numerator of
@@ -24,6 +25,7 @@
 // start t >= 0, so the crossing lies at or after t: the numerator is >= 0, and it is <= u^2 + f(u) <= 2^31 - 2.  All linear indices are
 // 64-bit: d2 passes 2^32 bytes at 2^30 voxels.
 #include "common.h"
+#include "volume_rules.h"
 #include <cstdint>
 
 namespace {
@@ -38,7 +40,7 @@ constexpr int ED_WORDS_PER_THREAD = (ED_WORDS + ED_THREADS - 1) / ED_THREADS;
 constexpr int ED_NONE = 1 << 30;                                    // no seed on this side
 constexpr long long ED_MAX_GRID = 1ll << 20;                        // more rows / column groups than this: a workgroup takes several
 constexpr int ED_AHEAD = 8;                                         // column entries loaded ahead of the forward scan
-constexpr int ED_CHUNK = 4096, ED_STEPS = ED_CHUNK / ED_THREADS;    // voxels of one workgroup of the streaming pass: <= 2^19 workgroups
+constexpr int ED_CHUNK = 4096;                                      // voxels of one workgroup of the streaming pass: <= 2^19 workgroups
 
 static_assert(ED_WORDS_PER_THREAD * ED_THREADS >= ED_WORDS && ED_MAX_AXIS <= 65535, "the scan covers the longest row; positions fit uint16");
 
@@ -59,22 +61,10 @@ __device__ __forceinline__ bool voxel_seed(const RowParams& p, long long v) {
     const int d = p.prev[v];
     return p.above ? d > p.r2 : d <= p.r2;
   }
-  int c, has = 1;
-  if (CT == 1) {
-    c = p.src[v];
-  } else {
-    const unsigned char* q = p.src + v * p.C;            // 64-bit: Z Y X C passes 2^31
-    int best = q[0];
-    c = 0;
-    const int n = CT == 2 ? 2 : p.C;
-    for (int k = 1; k < n; ++k) {                        // fixed trip count
-      const int t = q[k];
-      if (t > best) { best = t; c = k; }
-    }
-    has = best > 0;                                      // all bytes 0: never predicted, class map 0 (c == 0 here), member of no class
-  }
-  if (p.cls) p.cls[v] = (unsigned char)c;
-  return (has && c == p.target) != (p.invert != 0);
+  const TopByte t = volume_top_byte<CT>(p.src, v, p.C);  // volume_rules.h
+  if (p.cls) p.cls[v] = (unsigned char)t.at;
+  // all bytes 0: never predicted, class map 0 (t.at == 0 there), member of no class
+  return (t.best > 0 && t.at == p.target) != (p.invert != 0);
 }
 
 template <int CT>
@@ -198,38 +188,19 @@ __global__ __launch_bounds__(ED_THREADS) void column_kernel(ColParams p) {
   }
 }
 
-// V voxels per thread and step: 4 where d2, cls and out are aligned for 16- and 4-byte accesses, else 1
-template <int V>
-__global__ __launch_bounds__(ED_THREADS) void select_kernel(const int* d2, const unsigned char* cls, int r2, int above, int only, int value,
-                                                            unsigned char* out, long long N) {
-  const long long base = (long long)blockIdx.x * ED_CHUNK;
-  auto pick = [&](int d, unsigned char c) -> unsigned char {
+// the select's rule for volume_select_kernel: `value` where the distance passes the threshold (and the class is `only`), else the class
+struct SelectPick {
+  int r2, above, only, value;
+  __device__ __forceinline__ unsigned char operator()(int d, unsigned char c) const {
     const bool cond = above ? d > r2 : d <= r2;
     return (cond && (only < 0 || c == only)) ? (unsigned char)value : c;
-  };
-  for (int s = 0; s < ED_STEPS / V; ++s) {               // fixed trip count
-    const long long v = base + ((long long)s * ED_THREADS + threadIdx.x) * V;
-    if (v >= N) break;
-    if (V == 4 && v + 4 <= N) {
-      const int4 d = *(const int4*)(d2 + v);
-      uchar4 c = *(const uchar4*)(cls + v);
-      c.x = pick(d.x, c.x); c.y = pick(d.y, c.y); c.z = pick(d.z, c.z); c.w = pick(d.w, c.w);
-      *(uchar4*)(out + v) = c;
-    } else {
-      for (int j = 0; j < V && v + j < N; ++j) out[v + j] = pick(d2[v + j], cls[v + j]);
-    }
   }
-}
-
-inline long long ed_align16(long long n) { return (n + 15) & ~15ll; }
+};
 
 inline bool ed_volume_ok(int Z, int Y, int X) {
-  if (Z <= 0 || Y <= 0 || X <= 0 || Z > ED_MAX_AXIS || Y > ED_MAX_AXIS || X > ED_MAX_AXIS) return false;
-  if ((long long)Z * Y * X > ED_MAX_VOX) return false;
+  if (!volume_ok(Z, Y, X, ED_MAX_VOX) || Z > ED_MAX_AXIS || Y > ED_MAX_AXIS || X > ED_MAX_AXIS) return false;
   return (long long)(Z - 1) * (Z - 1) + (long long)(Y - 1) * (Y - 1) + (long long)(X - 1) * (X - 1) <= ED_MAX_SQ;
 }
-
-inline unsigned int ed_grid(long long groups) { return (unsigned int)(groups < ED_MAX_GRID ? groups : ED_MAX_GRID); }
 
 // passes Y and Z in place on d2; an axis of one entry is its own envelope
 int ed_columns(int* d2, int Z, int Y, int X, void* ws, hipStream_t st) {
@@ -240,12 +211,12 @@ int ed_columns(int* d2, int Z, int Y, int X, void* ws, hipStream_t st) {
   c.plane = (long long)Y * X;
   if (Y > 1) {
     c.ncols = (long long)Z * X; c.stride = X; c.n = Y; c.inner = 1;
-    hipLaunchKernelGGL(column_kernel, dim3(ed_grid((c.ncols + ED_THREADS - 1) / ED_THREADS)), dim3(ED_THREADS), 0, st, c);
+    hipLaunchKernelGGL(column_kernel, dim3(volume_grid((c.ncols + ED_THREADS - 1) / ED_THREADS, ED_MAX_GRID)), dim3(ED_THREADS), 0, st, c);
     IUNET_CHECK_HIP(hipGetLastError());
   }
   if (Z > 1) {
     c.ncols = c.plane; c.stride = c.plane; c.n = Z; c.inner = 0;
-    hipLaunchKernelGGL(column_kernel, dim3(ed_grid((c.ncols + ED_THREADS - 1) / ED_THREADS)), dim3(ED_THREADS), 0, st, c);
+    hipLaunchKernelGGL(column_kernel, dim3(volume_grid((c.ncols + ED_THREADS - 1) / ED_THREADS, ED_MAX_GRID)), dim3(ED_THREADS), 0, st, c);
     IUNET_CHECK_HIP(hipGetLastError());
   }
   return IUNET_OK;
@@ -259,13 +230,13 @@ extern "C" {
 long long iunet_edt_ws_bytes(int Z, int Y, int X) {
   if (!ed_volume_ok(Z, Y, X)) return 0;
   const long long N = (long long)Z * Y * X;
-  return ed_align16(8 * N);
+  return volume_align16(8 * N);
 }
 
 int iunet_edt_sq(const void* src, int Z, int Y, int X, int C, int target, int invert,
                  void* d2, void* cls, void* ws, long long ws_bytes, void* stream) {
   IUNET_REQUIRE(src && (d2 || cls), "edt_sq: null pointer (src; d2 and cls both)");
-  IUNET_REQUIRE(Z > 0 && Y > 0 && X > 0, "edt_sq: volume %d x %d x %d: a dimension below 1", Z, Y, X);
+  VOLUME_REQUIRE_DIMS("edt_sq", Z, Y, X);
   IUNET_REQUIRE(ed_volume_ok(Z, Y, X), "edt_sq: volume %d x %d x %d: more than 2^31 - 1 voxels or a squared diagonal above 2^31 - 2", Z, Y, X);
   IUNET_REQUIRE(C >= 1 && C <= 16, "edt_sq: %d classes outside 1..16", C);
   IUNET_REQUIRE(target >= 0 && target <= 255, "edt_sq: target %d outside 0..255", target);
@@ -282,7 +253,7 @@ int iunet_edt_sq(const void* src, int Z, int Y, int X, int C, int target, int in
   p.words = (X + 63) / 64;
   p.rows = (long long)Z * Y;
   void (*row[3])(RowParams) = {row_kernel<0>, row_kernel<1>, row_kernel<2>};
-  hipLaunchKernelGGL(row[C <= 2 ? C : 0], dim3(ed_grid(p.rows)), dim3(ED_THREADS), 0, st, p);
+  hipLaunchKernelGGL(row[C <= 2 ? C : 0], dim3(volume_grid(p.rows, ED_MAX_GRID)), dim3(ED_THREADS), 0, st, p);
   IUNET_CHECK_HIP(hipGetLastError());
   return d2 ? ed_columns((int*)d2, Z, Y, X, ws, st) : IUNET_OK;
 }
@@ -290,7 +261,7 @@ int iunet_edt_sq(const void* src, int Z, int Y, int X, int C, int target, int in
 int iunet_edt_sq_mask(const void* prev, int Z, int Y, int X, int r2, int above,
                       void* d2, void* ws, long long ws_bytes, void* stream) {
   IUNET_REQUIRE(prev && d2 && ws, "edt_sq_mask: null pointer (prev, d2, ws)");
-  IUNET_REQUIRE(Z > 0 && Y > 0 && X > 0, "edt_sq_mask: volume %d x %d x %d: a dimension below 1", Z, Y, X);
+  VOLUME_REQUIRE_DIMS("edt_sq_mask", Z, Y, X);
   IUNET_REQUIRE(ed_volume_ok(Z, Y, X), "edt_sq_mask: volume %d x %d x %d: more than 2^31 - 1 voxels or a squared diagonal above 2^31 - 2", Z, Y, X);
   IUNET_REQUIRE(r2 >= 0 && r2 <= ED_MAX_SQ, "edt_sq_mask: threshold r2 %d outside 0..2^31 - 2", r2);
   IUNET_REQUIRE(above == 0 || above == 1, "edt_sq_mask: above %d (0 or 1)", above);
@@ -305,7 +276,7 @@ int iunet_edt_sq_mask(const void* prev, int Z, int Y, int X, int r2, int above,
   p.X = X; p.C = 1; p.target = 0; p.invert = 0; p.r2 = r2; p.above = above;
   p.words = (X + 63) / 64;
   p.rows = (long long)Z * Y;
-  hipLaunchKernelGGL(row_kernel<3>, dim3(ed_grid(p.rows)), dim3(ED_THREADS), 0, st, p);
+  hipLaunchKernelGGL(row_kernel<3>, dim3(volume_grid(p.rows, ED_MAX_GRID)), dim3(ED_THREADS), 0, st, p);
   IUNET_CHECK_HIP(hipGetLastError());
   return ed_columns((int*)d2, Z, Y, X, ws, st);
 }
@@ -313,7 +284,7 @@ int iunet_edt_sq_mask(const void* prev, int Z, int Y, int X, int r2, int above,
 int iunet_edt_select(const void* d2, const void* cls, int Z, int Y, int X, int r2, int above, int only, int value,
                      void* out, void* stream) {
   IUNET_REQUIRE(d2 && cls && out, "edt_select: null pointer");
-  IUNET_REQUIRE(Z > 0 && Y > 0 && X > 0, "edt_select: volume %d x %d x %d: a dimension below 1", Z, Y, X);
+  VOLUME_REQUIRE_DIMS("edt_select", Z, Y, X);
   IUNET_REQUIRE(ed_volume_ok(Z, Y, X), "edt_select: volume %d x %d x %d: more than 2^31 - 1 voxels or a squared diagonal above 2^31 - 2", Z, Y, X);
   IUNET_REQUIRE(r2 >= 0 && r2 <= ED_MAX_SQ, "edt_select: threshold r2 %d outside 0..2^31 - 2", r2);
   IUNET_REQUIRE(above == 0 || above == 1, "edt_select: above %d (0 or 1)", above);
@@ -321,12 +292,7 @@ int iunet_edt_select(const void* d2, const void* cls, int Z, int Y, int X, int r
   IUNET_REQUIRE(value >= 0 && value <= 255, "edt_select: value %d outside 0..255", value);
   IUNET_REQUIRE(((uintptr_t)d2 & 3) == 0, "edt_select: d2 must be 4-byte aligned");
   const long long N = (long long)Z * Y * X;
-  const unsigned int chunks = (unsigned int)((N + ED_CHUNK - 1) / ED_CHUNK);
-  const bool wide = ((uintptr_t)d2 & 15) == 0 && (((uintptr_t)cls | (uintptr_t)out) & 3) == 0;
-  if (wide) hipLaunchKernelGGL(select_kernel<4>, dim3(chunks), dim3(ED_THREADS), 0, (hipStream_t)stream, (const int*)d2, (const unsigned char*)cls,
-                               r2, above, only, value, (unsigned char*)out, N);
-  else hipLaunchKernelGGL(select_kernel<1>, dim3(chunks), dim3(ED_THREADS), 0, (hipStream_t)stream, (const int*)d2, (const unsigned char*)cls,
-                          r2, above, only, value, (unsigned char*)out, N);
+  volume_select_launch<ED_CHUNK, ED_THREADS>(d2, cls, SelectPick{r2, above, only, value}, out, N, (hipStream_t)stream);
   IUNET_CHECK_HIP(hipGetLastError());
   return IUNET_OK;
 }

@@ -15,12 +15,13 @@
 // The sums meet in LDS at the end.  The pass lives on the bytes it keeps in flight: a thread issues four loads before it stores them,
 // reads four rows' bytes from LDS before it uses them, and the host sizes xs so that the grid fills the chip.
 //
-// plane_scores_kernel: sample (i, j) of plane p at c = (a r_i + b r_j) + o per axis, float64, every product and sum rounded on its own;
-// inside iff 0 <= c <= dim - 1 on all axes, then it reads voxel floor(c + 0.5) -- slab_gather_kernel (slab.hip) at r_k = 0 and order 0,
-// with its lane mapping: 64 consecutive j per wave, a wave per row, four steps of four rows per workgroup.  (sum u, count inside) is
+// plane_scores_kernel: sample (i, j) of plane p at c = (a r_i + b r_j) + o per axis (plane_point, volume_rules.h); inside iff
+// 0 <= c <= dim - 1 on all axes (coord_inside), then it reads voxel floor(c + 0.5) (coord_nearest) -- the order-0 sample of
+// slab_gather_kernel (slab.hip) at r_k = 0, with its lane mapping: 64 consecutive j per wave, a wave per row, four steps of four rows per workgroup.  (sum u, count inside) is
 // reduced in the wave, then across the four waves, and written as one int pair per workgroup; plane_scores_finish_kernel sums a
 // plane's pairs into int64.  Integer sums: any order gives the same bits.
 #include "common.h"
+#include "volume_rules.h"
 #include <cstdint>
 
 namespace {
@@ -189,7 +190,6 @@ struct ScoreParams {
 __host__ __device__ inline long long score_blocks(int sw) { return (long long)((sw + 63) / 64) * ((sw + SCORE_ROWS - 1) / SCORE_ROWS); }
 
 __global__ __launch_bounds__(256) void plane_scores_kernel(ScoreParams p) {
-#pragma clang fp contract(off)
   __shared__ int part[4][2];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = blockIdx.x * 64 + lane;
@@ -205,13 +205,11 @@ __global__ __launch_bounds__(256) void plane_scores_kernel(ScoreParams p) {
     bool inside = true;
 #pragma unroll
     for (int x = 0; x < 3; ++x) {
-      const double t1 = g[x] * ri, t2 = g[3 + x] * rj;
-      const double s = t1 + t2;
-      c[x] = s + g[6 + x];
-      inside = inside && c[x] >= 0.0 && c[x] <= (double)(p.dim[x] - 1);
+      c[x] = plane_point(g[x], g[3 + x], g[6 + x], ri, rj);
+      inside = inside && coord_inside(c[x], p.dim[x]);
     }
     if (inside) {
-      const long long z = (long long)floor(c[0] + 0.5), y = (long long)floor(c[1] + 0.5), x = (long long)floor(c[2] + 0.5);
+      const long long z = (long long)coord_nearest(c[0]), y = (long long)coord_nearest(c[1]), x = (long long)coord_nearest(c[2]);
       sum += p.u[z * sz + y * sy + x];
       cnt += 1;
     }
@@ -251,7 +249,7 @@ int iunet_uncertainty_volume(const void* pred, int Z, int Y, int X, int C, const
   IUNET_REQUIRE(!weight || wch == 1 || wch == 2, "uncertainty_volume: %d weight channels (1 or 2)", wch);
   IUNET_REQUIRE(!image || (ich >= 1 && ich <= 4), "uncertainty_volume: %d image channels outside 1..4", ich);
   IUNET_REQUIRE(brick == 4 || brick == 8 || brick == 16 || brick == 32, "uncertainty_volume: brick size %d (4, 8, 16 or 32)", brick);
-  IUNET_REQUIRE(Z > 0 && Y > 0 && X > 0 && (long long)Z * Y * X < (1ll << 42), "uncertainty_volume: volume %d x %d x %d", Z, Y, X);
+  IUNET_REQUIRE(volume_ok(Z, Y, X, VOLUME_MAX_SAMPLED), "uncertainty_volume: volume %d x %d x %d", Z, Y, X);
   UncParams p;
   p.pred = (const unsigned char*)pred; p.weight = (const unsigned char*)weight; p.image = (const unsigned char*)image;
   p.u = (unsigned char*)u; p.bricks = (unsigned int*)bricks;
@@ -297,7 +295,7 @@ long long iunet_plane_scores_ws_bytes(int P, int sw) {
 int iunet_plane_scores(const void* u, int Z, int Y, int X, const void* geoms, int P, int sw, int start, void* ws, long long ws_bytes,
                        void* out, void* stream) {
   IUNET_REQUIRE(u && geoms && ws && out, "plane_scores: null pointer");
-  IUNET_REQUIRE(Z > 0 && Y > 0 && X > 0 && (long long)Z * Y * X < (1ll << 42), "plane_scores: volume %d x %d x %d", Z, Y, X);
+  IUNET_REQUIRE(volume_ok(Z, Y, X, VOLUME_MAX_SAMPLED), "plane_scores: volume %d x %d x %d", Z, Y, X);
   IUNET_REQUIRE(P >= 1 && P <= 65535, "plane_scores: %d planes outside 1..65535", P);
   IUNET_REQUIRE(sw >= 1 && sw <= 4096, "plane_scores: slice width %d outside 1..4096", sw);
   IUNET_REQUIRE(ws_bytes >= iunet_plane_scores_ws_bytes(P, sw), "plane_scores: workspace of %lld bytes, %lld needed", ws_bytes,

@@ -2,19 +2,16 @@
 // into a resident predicted volume (defined bit for bit by tests/slab_ref.py).
 //
 // Gather.  Sample (k, i, j) of the uint8 [T][sw][sw] slab lies at c = ((a * r_i + b * r_j) + n * r_k) + o per axis, r_i = start + i,
-// r_j = start + j, r_k = start_k + k, float64, every product and sum rounded on its own in this order -- at r_k = 0 the plane of
-// Slicer.get_interpolation_coords.  It is sampled from the WHOLE volume the way slice_gather_kernel (slicer.hip) samples its crop,
-// i.e. as scipy.ndimage.map_coordinates(mode='constant', cval=0) does for spline orders 0 and 1:
-//   * a coordinate outside [0, dim - 1] along any axis gives 0 (no interpolation against the padding);
-//   * order 0: voxel floor(c + 0.5);
-//   * order 1: weights w0 = 1 - frac, w1 = 1 - w0, neighbour indices mirrored at the volume's edge (weight 0 there),
-//     t = sum over (dz, dy, dx) of ((v * wz) * wy) * wx in that order, result trunc(t + 0.5) clamped to 255.
-// Paste.  The adjoint direction as a gather over the voxels of a host-given box (no holes, no atomics): voxel p has the slab
+// r_j = start + j, r_k = start_k + k (slab_point, volume_rules.h) -- at r_k = 0 the plane of Slicer.get_interpolation_coords.  It is
+// sampled from the WHOLE volume by the rules slice_gather_kernel (slicer.hip) applies to its crop (coord_inside, coord_nearest,
+// volume_sample_linear), i.e. as scipy.ndimage.map_coordinates(mode='constant', cval=0) does for spline orders 0 and 1.
+// Paste. The adjoint direction as a gather over the voxels of a host-given box (no holes, no atomics): voxel p has the slab
 // coordinates t_v = (d_0 v_0 + d_1 v_1) + d_2 v_2, d = p - o, for v in (n, a, b); its sample is the nearest one (ties to even), and it
 // is written iff that sample lies in the kept planes and inside the border.  The fp32 probabilities are quantised on the way to the
 // bytes iunet_normalize_quantize gives at weight 1.
 // Both are HBM-bound: one lane per output element, 64 consecutive lanes on 64 consecutive j (gather) / x (paste), 4 rows per workgroup.
 #include "common.h"
+#include "volume_rules.h"
 
 namespace {
 
@@ -39,16 +36,7 @@ struct SlabPasteParams {
   int sw, start, start_k, k_lo, k_hi, border;
 };
 
-__device__ __forceinline__ int slab_mirror(int idx, int len) {       // slicer.hip: mirror_idx
-  if (len <= 1) return 0;
-  const int s2 = 2 * len - 2;
-  if (idx < 0) { idx = s2 * (-idx / s2) + idx; return idx <= 1 - len ? idx + s2 : -idx; }
-  if (idx >= len) { idx -= s2 * (idx / s2); if (idx >= len) idx = s2 - idx; }
-  return idx;
-}
-
 __global__ __launch_bounds__(256) void slab_gather_kernel(SlabGatherParams p) {
-#pragma clang fp contract(off)
   const int j = blockIdx.x * 64 + (threadIdx.x & 63), i = blockIdx.y * 4 + (threadIdx.x >> 6), k = blockIdx.z;
   if (i >= p.sw || j >= p.sw) return;
   const double ri = (double)(p.start + i), rj = (double)(p.start + j), rk = (double)(p.start_k + k);
@@ -56,47 +44,17 @@ __global__ __launch_bounds__(256) void slab_gather_kernel(SlabGatherParams p) {
   bool inside = true;
 #pragma unroll
   for (int x = 0; x < 3; ++x) {
-    const double t1 = p.g.a[x] * ri, t2 = p.g.b[x] * rj, t3 = p.g.n[x] * rk;
-    const double s = t1 + t2;
-    const double q = s + t3;
-    c[x] = q + p.g.o[x];
-    inside = inside && c[x] >= 0.0 && c[x] <= (double)(p.dim[x] - 1);
+    c[x] = slab_point(p.g.a[x], p.g.b[x], p.g.n[x], p.g.o[x], ri, rj, rk);
+    inside = inside && coord_inside(c[x], p.dim[x]);
   }
   unsigned char res = 0;
   if (inside) {
     const long long sy = p.dim[2], sz = (long long)p.dim[1] * p.dim[2];
     if (p.order == 0) {
-      const long long z = (long long)floor(c[0] + 0.5), y = (long long)floor(c[1] + 0.5), x = (long long)floor(c[2] + 0.5);
+      const long long z = (long long)coord_nearest(c[0]), y = (long long)coord_nearest(c[1]), x = (long long)coord_nearest(c[2]);
       res = p.vol[z * sz + y * sy + x];
     } else {
-      int st[3];
-      double w[3][2];
-#pragma unroll
-      for (int x = 0; x < 3; ++x) {
-        const double f = floor(c[x]);
-        st[x] = (int)f;
-        const double fr = c[x] - f;
-        w[x][0] = 1.0 - fr;
-        w[x][1] = 1.0 - w[x][0];
-      }
-      double t = 0.0;
-#pragma unroll
-      for (int dz = 0; dz < 2; ++dz)
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-          for (int dx = 0; dx < 2; ++dx) {
-            const long long iz = slab_mirror(st[0] + dz, p.dim[0]), iy = slab_mirror(st[1] + dy, p.dim[1]),
-                            ix = slab_mirror(st[2] + dx, p.dim[2]);
-            double coeff = (double)p.vol[iz * sz + iy * sy + ix];
-            coeff = coeff * w[0][dz];
-            coeff = coeff * w[1][dy];
-            coeff = coeff * w[2][dx];
-            t = t + coeff;
-          }
-      t = t > 0.0 ? t + 0.5 : 0.0;
-      t = t > 255.0 ? 255.0 : t;
-      res = (unsigned char)t;
+      res = volume_sample_linear(p.vol, p.dim, sy, sz, c);
     }
   }
   p.out[((long long)k * p.sw + i) * p.sw + j] = res;
@@ -144,7 +102,7 @@ int iunet_slab_gather(const void* vol, int Z, int Y, int X, const double* geom, 
   IUNET_REQUIRE(order == 0 || order == 1, "slab_gather: spline order must be 0 or 1 (got %d)", order);
   IUNET_REQUIRE(T >= 1 && sw >= 1, "slab_gather: bad slab %d x %d x %d", T, sw, sw);
   IUNET_REQUIRE(T <= 65535 && (sw + 3) / 4 <= 65535, "slab_gather: slab %d x %d x %d exceeds the grid (65535 planes, 262140 rows)", T, sw, sw);
-  IUNET_REQUIRE(Z > 0 && Y > 0 && X > 0 && (long long)Z * Y * X < (1ll << 42), "slab_gather: volume %d x %d x %d", Z, Y, X);
+  IUNET_REQUIRE(volume_ok(Z, Y, X, VOLUME_MAX_SAMPLED), "slab_gather: volume %d x %d x %d", Z, Y, X);
   SlabGatherParams p;
   p.vol = (const unsigned char*)vol; p.dim[0] = Z; p.dim[1] = Y; p.dim[2] = X;
   slab_geom(p.g, geom);
@@ -161,7 +119,7 @@ int iunet_slab_paste(void* vol, int Z, int Y, int X, int C, const double* geom, 
   IUNET_REQUIRE(vol && geom && lo && len && probs, "slab_paste: null pointer");
   IUNET_REQUIRE(T >= 1 && sw >= 1, "slab_paste: bad slab %d x %d x %d", T, sw, sw);
   IUNET_REQUIRE(C >= 1 && C <= 16, "slab_paste: %d classes outside 1..16", C);
-  IUNET_REQUIRE(Z > 0 && Y > 0 && X > 0 && (long long)Z * Y * X < (1ll << 42), "slab_paste: volume %d x %d x %d", Z, Y, X);
+  IUNET_REQUIRE(volume_ok(Z, Y, X, VOLUME_MAX_SAMPLED), "slab_paste: volume %d x %d x %d", Z, Y, X);
   IUNET_REQUIRE(k_lo >= 0 && k_hi <= T && k_hi > k_lo, "slab_paste: empty or outlying plane range [%d, %d) of %d planes", k_lo, k_hi, T);
   IUNET_REQUIRE(border >= 0 && 2 * (long long)border < sw, "slab_paste: border %d leaves nothing of %d pixels", border, sw);
   SlabPasteParams p;

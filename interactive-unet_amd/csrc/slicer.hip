@@ -1,14 +1,11 @@
 // Oblique-slice extraction on the device (slicer.py:94-115 coordinates, :196-228 crop + map_coordinates).
-// The plane point of output pixel (i, j) is origin + a * r_i + b * r_j (float64, every operation rounded on its
-// own exactly as numpy evaluates `a[:, None, None] * r[None, :, None] + b[:, None, None] * r[None, None, :] + o`);
-// it is sampled from the bounding-box crop [lo, lo + len) of the uint8 volume the way scipy.ndimage.map_coordinates
-// (mode='constant', cval=0) does it for spline orders 0 and 1:
-//   * a coordinate outside [0, len - 1] along any axis gives 0 (no interpolation against the padding);
-//   * order 0: voxel floor(c + 0.5);
-//   * order 1: weights w0 = 1 - frac, w1 = 1 - w0, neighbour indices mirrored at the crop edge (weight 0 there),
-//     t = sum over (dz, dy, dx) of ((v * wz) * wy) * wx in that order, result trunc(t + 0.5) clamped to 255.
+// The plane point of output pixel (i, j) is origin + a * r_i + b * r_j (plane_point, volume_rules.h: float64, every operation rounded on
+// its own exactly as numpy evaluates `a[:, None, None] * r[None, :, None] + b[:, None, None] * r[None, None, :] + o`); it is sampled from
+// the bounding-box crop [lo, lo + len) of the uint8 volume the way scipy.ndimage.map_coordinates (mode='constant', cval=0) does it for
+// spline orders 0 and 1 (coord_inside, coord_nearest, volume_sample_linear: the rules slab.hip applies to the whole volume).
 // HBM-bound gather: one thread per output pixel, 1 or 8 byte reads.
 #include "common.h"
+#include "volume_rules.h"
 
 namespace {
 
@@ -21,14 +18,6 @@ struct SliceParams {
   unsigned char* out;
 };
 
-__device__ __forceinline__ int mirror_idx(int idx, int len) {
-  if (len <= 1) return 0;
-  const int s2 = 2 * len - 2;
-  if (idx < 0) { idx = s2 * (-idx / s2) + idx; return idx <= 1 - len ? idx + s2 : -idx; }
-  if (idx >= len) { idx -= s2 * (idx / s2); if (idx >= len) idx = s2 - idx; }
-  return idx;
-}
-
 __global__ __launch_bounds__(256) void slice_gather_kernel(SliceParams p) {
 #pragma clang fp contract(off)
   const int j = blockIdx.x * 16 + (threadIdx.x & 15), i = blockIdx.y * 16 + (threadIdx.x >> 4);
@@ -38,48 +27,18 @@ __global__ __launch_bounds__(256) void slice_gather_kernel(SliceParams p) {
   bool inside = true;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const double t1 = p.a[k] * ri, t2 = p.b[k] * rj;
-    const double s = t1 + t2;
-    const double g = s + p.o[k];
-    c[k] = g - (double)p.lo[k];
-    inside = inside && c[k] >= 0.0 && c[k] <= (double)(p.len[k] - 1);
+    c[k] = plane_point(p.a[k], p.b[k], p.o[k], ri, rj) - (double)p.lo[k];      // the crop's offset: a step of its own after the sum
+    inside = inside && coord_inside(c[k], p.len[k]);
   }
   unsigned char res = 0;
   if (inside) {
     const long long sy = p.X, sz = (long long)p.Y * p.X;
     const unsigned char* base = p.vol + (long long)p.lo[0] * sz + (long long)p.lo[1] * sy + p.lo[2];
     if (p.order == 0) {
-      const int z = (int)floor(c[0] + 0.5), y = (int)floor(c[1] + 0.5), x = (int)floor(c[2] + 0.5);
+      const int z = (int)coord_nearest(c[0]), y = (int)coord_nearest(c[1]), x = (int)coord_nearest(c[2]);
       res = base[z * sz + y * sy + x];
     } else {
-      int st[3];
-      double w[3][2];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const double f = floor(c[k]);
-        st[k] = (int)f;
-        const double x = c[k] - f;
-        w[k][0] = 1.0 - x;
-        w[k][1] = 1.0 - w[k][0];
-      }
-      double t = 0.0;
-#pragma unroll
-      for (int dz = 0; dz < 2; ++dz)
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-          for (int dx = 0; dx < 2; ++dx) {
-            const int iz = mirror_idx(st[0] + dz, p.len[0]), iy = mirror_idx(st[1] + dy, p.len[1]),
-                      ix = mirror_idx(st[2] + dx, p.len[2]);
-            double coeff = (double)base[iz * sz + iy * sy + ix];
-            coeff = coeff * w[0][dz];
-            coeff = coeff * w[1][dy];
-            coeff = coeff * w[2][dx];
-            t = t + coeff;
-          }
-      t = t > 0.0 ? t + 0.5 : 0.0;
-      t = t > 255.0 ? 255.0 : t;
-      res = (unsigned char)t;
+      res = volume_sample_linear(base, p.len, sy, sz, c);
     }
   }
   p.out[(long long)i * p.sw + j] = res;
@@ -101,16 +60,12 @@ struct ScatterParams {
 };
 
 __device__ __forceinline__ long long scatter_voxel(const ScatterParams& p, int i, int j) {
-#pragma clang fp contract(off)
   const double ri = (double)(p.start + i), rj = (double)(p.start + j);
   const int dims[3] = {p.Z, p.Y, p.X};
   long long idx[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const double t1 = p.a[k] * ri, t2 = p.b[k] * rj;
-    const double s = t1 + t2;
-    const double g = s + p.o[k];
-    const long long r = (long long)rint(g);                       // np.round: half to even
+    const long long r = (long long)rint(plane_point(p.a[k], p.b[k], p.o[k], ri, rj));      // np.round: half to even
     idx[k] = r < 0 ? 0 : (r > dims[k] - 1 ? dims[k] - 1 : r);
   }
   return (idx[0] * p.Y + idx[1]) * p.X + idx[2];
@@ -171,7 +126,7 @@ int iunet_slice_scatter(void* vol, int Z, int Y, int X, int C, const double* geo
                         void* workspace, void* stream) {
   IUNET_REQUIRE(vol && geom && data && workspace, "slice_scatter: null pointer");
   IUNET_REQUIRE(sw >= 1 && sw <= 1024, "slice_scatter: slice width %d outside 1..1024", sw);
-  IUNET_REQUIRE(Z > 0 && Y > 0 && X > 0 && C > 0 && (long long)Z * Y * X < (1ll << 42), "slice_scatter: volume %d x %d x %d x %d", Z, Y, X, C);
+  IUNET_REQUIRE(volume_ok(Z, Y, X, VOLUME_MAX_SAMPLED) && C > 0, "slice_scatter: volume %d x %d x %d x %d", Z, Y, X, C);
   ScatterParams p;
   p.vol = (unsigned char*)vol; p.Z = Z; p.Y = Y; p.X = X; p.C = C;
   for (int k = 0; k < 3; ++k) { p.a[k] = geom[k]; p.b[k] = geom[3 + k]; p.o[k] = geom[6 + k]; }

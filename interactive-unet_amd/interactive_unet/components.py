@@ -13,40 +13,25 @@ uint8 tensors) go through libiunet (iunet_cc_label, iunet_cc_table, iunet_cc_fil
 import numpy as np
 import torch
 
+from . import resident
+
 TILE = (4, 16, 64)                # (tz, ty, tx) of csrc/components.hip: CC_TZ, CC_TY, CC_TX (tests/test_components_cpu.py compares them)
 CONNECTIVITIES = (6, 18, 26)
-MAX_VOXELS = 2 ** 31 - 1
 
 
 def _check(src, connectivity, background):
     """Validated (on_device, Z, Y, X, C, background as -1 .. 255).  Raises ValueError before any GPU work."""
-    dev = torch.is_tensor(src)
-    if not (dev or isinstance(src, np.ndarray)):
-        raise ValueError('src must be a CUDA uint8 tensor or a numpy uint8 array')
-    if dev and not src.is_cuda:
-        raise ValueError('a resident volume must be a CUDA tensor (a host volume goes in as a numpy array)')
-    if src.dtype != (torch.uint8 if dev else np.uint8):
-        raise ValueError(f'src must be uint8, got {src.dtype}')
-    if not (src.is_contiguous() if dev else src.flags['C_CONTIGUOUS']):
-        raise ValueError('src must be contiguous')
-    if src.ndim not in (3, 4) or min(src.shape) < 1 or (src.ndim == 4 and not 2 <= src.shape[3] <= 16):
-        raise ValueError(f'src must be a class map [Z, Y, X] or a predicted volume [Z, Y, X, C] with 2 <= C <= 16, got {tuple(src.shape)}')
-    Z, Y, X = (int(n) for n in src.shape[:3])
-    if Z * Y * X > MAX_VOXELS:
-        raise ValueError(f'volume {Z} x {Y} x {X}: more than 2^31 - 1 voxels')
+    dev, Z, Y, X, C = resident.check_volume(src)
     if connectivity not in CONNECTIVITIES:
         raise ValueError(f'connectivity {connectivity}: one of {CONNECTIVITIES}')
     background = -1 if background is None else background
-    if not isinstance(background, (int, np.integer)) or isinstance(background, bool) or not -1 <= background <= 255:
+    if not resident.is_int(background) or not -1 <= background <= 255:
         raise ValueError(f'background {background!r}: None / -1 (every class is labelled) or 0 .. 255')
-    return dev, Z, Y, X, (1 if src.ndim == 3 else int(src.shape[3])), int(background)
+    return dev, Z, Y, X, C, int(background)
 
 
 def _fill(fill, background):
-    fill = (0 if background in (None, -1) else background) if fill is None else fill
-    if not isinstance(fill, (int, np.integer)) or isinstance(fill, bool) or not 0 <= fill <= 255:
-        raise ValueError(f'fill {fill!r} outside 0 .. 255')
-    return int(fill)
+    return resident.check_byte((0 if background in (None, -1) else background) if fill is None else fill, 'fill')
 
 
 def _pair(labels, cls):
@@ -63,15 +48,13 @@ def _pair(labels, cls):
     if not ((labels.is_contiguous() and cls.is_contiguous()) if dev else (labels.flags['C_CONTIGUOUS'] and cls.flags['C_CONTIGUOUS'])):
         raise ValueError('labels and cls must be contiguous')
     Z, Y, X = (int(n) for n in labels.shape)
-    if Z * Y * X > MAX_VOXELS:
+    if Z * Y * X > resident.MAX_VOXELS:
         raise ValueError(f'volume {Z} x {Y} x {X}: more than 2^31 - 1 voxels')
     return dev, Z, Y, X
 
 
 def _count(count):
-    if isinstance(count, bool) or not isinstance(count, (int, np.integer)) or count < 0:
-        raise ValueError(f'count {count!r}: the number of components, an int >= 0')
-    return int(count)
+    return resident.check_count(count, 'count', 'the number of components, an int >= 0')
 
 
 def label(src, connectivity=6, background=0):
@@ -93,11 +76,8 @@ def label(src, connectivity=6, background=0):
                     ws_bytes, nv.stream())
         return labels, int(count.item()), cls
     from scipy import ndimage
-    if C == 1:
-        cls, fg = src.copy(), src != bg
-    else:
-        cls = src.argmax(axis=-1).astype(np.uint8)                                       # the first of equal bytes
-        fg = (src.max(axis=-1) > 0) & (cls != bg)
+    cls, has = resident.host_maps(src)
+    fg = has & (cls != bg)
     structure = ndimage.generate_binary_structure(3, CONNECTIVITIES.index(connectivity) + 1)
     # per class: scipy's labels and the raster index of each one's first voxel; then all components in order of first voxel
     firsts, flat = [], np.zeros(Z * Y * X, dtype=np.int64)
@@ -197,11 +177,10 @@ def remove_small(src, min_size, connectivity=6, background=0, fill=None):
     """The class map uint8 [Z, Y, X] of src with every component of fewer than min_size voxels set to `fill` (default: the background,
     0 where every class is labelled)."""
     fill = _fill(fill, background)
-    if isinstance(min_size, bool) or not isinstance(min_size, (int, np.integer)) or min_size < 0:
-        raise ValueError(f'min_size {min_size!r}: an int >= 0')
+    min_size = resident.check_count(min_size, 'min_size')
     labels, count, cls = label(src, connectivity, background)
     sizes, _, _ = table(labels, cls, count)
-    return filter_components(labels, cls, count, sizes >= int(min_size), fill)
+    return filter_components(labels, cls, count, sizes >= min_size, fill)
 
 
 def keep_largest(src, n=1, per_class=True, connectivity=6, background=0, fill=None):
@@ -209,8 +188,7 @@ def keep_largest(src, n=1, per_class=True, connectivity=6, background=0, fill=No
     others set to `fill` (default: the background, 0 where every class is labelled).  Of components of equal size the one with the
     smaller label (the earlier first voxel) is kept."""
     fill = _fill(fill, background)
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
-        raise ValueError(f'n {n!r}: an int >= 0')
+    n = resident.check_count(n, 'n')
     labels, count, cls = label(src, connectivity, background)
     sizes, classes, _ = table(labels, cls, count)
-    return filter_components(labels, cls, count, largest_flags(sizes, classes, int(n), bool(per_class)), fill)
+    return filter_components(labels, cls, count, largest_flags(sizes, classes, n, bool(per_class)), fill)

@@ -17,38 +17,10 @@ import math
 import numpy as np
 import torch
 
-from . import components
+from . import components, resident
 
 INF = 2 ** 31 - 1
-MAX_VOXELS = 2 ** 31 - 1
 MAX_SQ = 2 ** 31 - 2              # the largest finite squared distance: the squared diagonal of the volume may not pass it
-
-
-def _check(src):
-    """Validated (on_device, Z, Y, X, C).  Raises ValueError before any GPU work."""
-    dev = torch.is_tensor(src)
-    if not (dev or isinstance(src, np.ndarray)):
-        raise ValueError('src must be a CUDA uint8 tensor or a numpy uint8 array')
-    if dev and not src.is_cuda:
-        raise ValueError('a resident volume must be a CUDA tensor (a host volume goes in as a numpy array)')
-    if src.dtype != (torch.uint8 if dev else np.uint8):
-        raise ValueError(f'src must be uint8, got {src.dtype}')
-    if not (src.is_contiguous() if dev else src.flags['C_CONTIGUOUS']):
-        raise ValueError('src must be contiguous')
-    if src.ndim not in (3, 4) or min(src.shape) < 1 or (src.ndim == 4 and not 2 <= src.shape[3] <= 16):
-        raise ValueError(f'src must be a class map [Z, Y, X] or a predicted volume [Z, Y, X, C] with 2 <= C <= 16, got {tuple(src.shape)}')
-    Z, Y, X = (int(n) for n in src.shape[:3])
-    if Z * Y * X > MAX_VOXELS:
-        raise ValueError(f'volume {Z} x {Y} x {X}: more than 2^31 - 1 voxels')
-    if (Z - 1) ** 2 + (Y - 1) ** 2 + (X - 1) ** 2 > MAX_SQ:
-        raise ValueError(f'volume {Z} x {Y} x {X}: its squared diagonal passes 2^31 - 2')
-    return dev, Z, Y, X, (1 if src.ndim == 3 else int(src.shape[3]))
-
-
-def _byte(value, name):
-    if not isinstance(value, (int, np.integer)) or isinstance(value, bool) or not 0 <= value <= 255:
-        raise ValueError(f'{name} {value!r} outside 0 .. 255')
-    return int(value)
 
 
 def _radius_sq(radius):
@@ -58,13 +30,6 @@ def _radius_sq(radius):
     if r2 > MAX_SQ:
         raise ValueError(f'radius {radius!r}: its square passes 2^31 - 2')
     return r2
-
-
-def _host_maps(src):
-    """(cls, has) of a numpy src."""
-    if src.ndim == 3:
-        return src.copy(), np.ones(src.shape, dtype=bool)
-    return src.argmax(axis=-1).astype(np.uint8), src.max(axis=-1) > 0                   # the first of equal bytes
 
 
 def _host_d2(seeds):
@@ -113,43 +78,43 @@ def _never_to_zero(out, src, C, target, fill):
 def distance_sq(src, target=1, invert=False):
     """int32 [Z, Y, X]: the squared Euclidean distance of every voxel to the nearest voxel of class `target` (invert: to the nearest voxel
     that is not of that class, the never-predicted ones included); 0 on those voxels, INF = 2^31 - 1 everywhere when there is none."""
-    dev, Z, Y, X, C = _check(src)
-    target = _byte(target, 'target')
+    dev, Z, Y, X, C = resident.check_volume(src, MAX_SQ)
+    target = resident.check_byte(target, 'target')
     if dev:
         return _edt(src, Z, Y, X, C, target, bool(invert), want_cls=False)[0]
-    cls, has = _host_maps(src)
+    cls, has = resident.host_maps(src)
     a = has & (cls == target)
     return _host_d2(~a if invert else a)
 
 
 def class_map(src):
     """uint8 [Z, Y, X]: the class of every voxel, 0 for a voxel never predicted."""
-    dev, Z, Y, X, C = _check(src)
+    dev, Z, Y, X, C = resident.check_volume(src, MAX_SQ)
     if dev:
         return _edt(src, Z, Y, X, C, 0, False, want_d2=False)[1]
-    return _host_maps(src)[0]
+    return resident.host_maps(src)[0]
 
 
 def dilate(src, target, radius):
     """The class map with every voxel within `radius` of class `target` set to it."""
-    dev, Z, Y, X, C = _check(src)
-    target, r2 = _byte(target, 'target'), _radius_sq(radius)
+    dev, Z, Y, X, C = resident.check_volume(src, MAX_SQ)
+    target, r2 = resident.check_byte(target, 'target'), _radius_sq(radius)
     if dev:
         d2, cls, _, _ = _edt(src, Z, Y, X, C, target, False)
         return _select(d2, cls, Z, Y, X, r2, False, -1, target)
-    cls, has = _host_maps(src)
+    cls, has = resident.host_maps(src)
     cls[_host_d2(has & (cls == target)) <= r2] = target
     return cls
 
 
 def erode(src, target, radius, fill=0):
     """The class map with the voxels of class `target` within `radius` of a voxel outside it set to `fill`."""
-    dev, Z, Y, X, C = _check(src)
-    target, fill, r2 = _byte(target, 'target'), _byte(fill, 'fill'), _radius_sq(radius)
+    dev, Z, Y, X, C = resident.check_volume(src, MAX_SQ)
+    target, fill, r2 = resident.check_byte(target, 'target'), resident.check_byte(fill, 'fill'), _radius_sq(radius)
     if dev:
         d2, cls, _, _ = _edt(src, Z, Y, X, C, target, True)
         return _never_to_zero(_select(d2, cls, Z, Y, X, r2, False, target, fill), src, C, target, fill)
-    cls, has = _host_maps(src)
+    cls, has = resident.host_maps(src)
     a = has & (cls == target)
     cls[a & (_host_d2(~a) <= r2)] = fill
     return cls
@@ -157,13 +122,13 @@ def erode(src, target, radius, fill=0):
 
 def opening(src, target, radius, fill=0):
     """Erosion then dilation of class `target` by the ball: what the ball cannot enter -- thin bridges, a ragged rim -- is set to `fill`."""
-    dev, Z, Y, X, C = _check(src)
-    target, fill, r2 = _byte(target, 'target'), _byte(fill, 'fill'), _radius_sq(radius)
+    dev, Z, Y, X, C = resident.check_volume(src, MAX_SQ)
+    target, fill, r2 = resident.check_byte(target, 'target'), resident.check_byte(fill, 'fill'), _radius_sq(radius)
     if dev:
         inner, cls, ws, ws_bytes = _edt(src, Z, Y, X, C, target, True)          # the distance to the outside of A: > r2 on the eroded set
         d2 = _edt_mask(inner, Z, Y, X, r2, True, ws, ws_bytes)                  # the distance to the eroded set
         return _never_to_zero(_select(d2, cls, Z, Y, X, r2, True, target, fill), src, C, target, fill)
-    cls, has = _host_maps(src)
+    cls, has = resident.host_maps(src)
     a = has & (cls == target)
     cls[a & (_host_d2(_host_d2(~a) > r2) > r2)] = fill
     return cls
@@ -171,13 +136,13 @@ def opening(src, target, radius, fill=0):
 
 def closing(src, target, radius):
     """Dilation then erosion of class `target` by the ball: gaps and pin-holes the ball cannot enter take the target."""
-    dev, Z, Y, X, C = _check(src)
-    target, r2 = _byte(target, 'target'), _radius_sq(radius)
+    dev, Z, Y, X, C = resident.check_volume(src, MAX_SQ)
+    target, r2 = resident.check_byte(target, 'target'), _radius_sq(radius)
     if dev:
         outer, cls, ws, ws_bytes = _edt(src, Z, Y, X, C, target, False)         # the distance to A: <= r2 on the dilated set
         d2 = _edt_mask(outer, Z, Y, X, r2, True, ws, ws_bytes)                  # the distance to the outside of the dilated set
         return _select(d2, cls, Z, Y, X, r2, True, -1, target)
-    cls, has = _host_maps(src)
+    cls, has = resident.host_maps(src)
     cls[_host_d2(_host_d2(has & (cls == target)) > r2) > r2] = target
     return cls
 
@@ -185,8 +150,8 @@ def closing(src, target, radius):
 def fill_holes(src, target, connectivity=6):
     """The class map with the holes of class `target` -- the components of its complement, under the 6-, 18- or 26-neighbourhood, that
     touch none of the six faces of the volume -- set to it.  No kernel of its own: the complement is labelled by components.label."""
-    dev, Z, Y, X, C = _check(src)
-    target = _byte(target, 'target')
+    dev, Z, Y, X, C = resident.check_volume(src, MAX_SQ)
+    target = resident.check_byte(target, 'target')
     if connectivity not in components.CONNECTIVITIES:
         raise ValueError(f'connectivity {connectivity}: one of {components.CONNECTIVITIES}')
     if dev:
@@ -200,7 +165,7 @@ def fill_holes(src, target, connectivity=6):
             keep[face.reshape(-1).long()] = 1
         return components.filter_components(labels, cls, K, keep, fill=target)
     from scipy import ndimage
-    cls, has = _host_maps(src)
+    cls, has = resident.host_maps(src)
     a = has & (cls == target)
     cls[ndimage.binary_fill_holes(a, structure=ndimage.generate_binary_structure(3, components.CONNECTIVITIES.index(connectivity) + 1)) & ~a] = target
     return cls

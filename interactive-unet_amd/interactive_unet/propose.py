@@ -12,6 +12,7 @@ numpy arrays take the vectorised numpy path below, which computes the same integ
 import numpy as np
 import torch
 
+from . import resident
 from .slicer import Slicer
 
 BRICKS = (4, 8, 16, 32)
@@ -29,10 +30,7 @@ def _volumes(pred, weight, image):
     for name, v in (('pred', pred), ('weight', weight), ('image', image)):
         if v is None:
             continue
-        if v.dtype != (torch.uint8 if dev else np.uint8):
-            raise ValueError(f'{name} must be uint8, got {v.dtype}')
-        if not (v.is_contiguous() if dev else v.flags['C_CONTIGUOUS']):
-            raise ValueError(f'{name} must be contiguous')
+        resident.check_bytes(name, v, dev)
     if pred.ndim != 4 or not 2 <= pred.shape[3] <= 16 or min(pred.shape) < 1:
         raise ValueError(f'pred must be [Z, Y, X, C] with 2 <= C <= 16, got {tuple(pred.shape)}')
     zyx = tuple(pred.shape[:3])

@@ -11,24 +11,11 @@ import torch
 from scipy import ndimage
 
 from tests import components_ref as cr
+from tests.volume_inputs import random_pred
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONN = (6, 18, 26)
 SHAPES = ((37, 41, 150), (33, 2, 65), (1, 1, 300))
-
-
-def _random_pred(shape, C, seed):
-    """Random bytes, about a tenth of the voxels all-zero and a tenth with a tie at the top (the recipe of tests/test_gpu_propose.py)."""
-    rng = np.random.default_rng(seed)
-    pred = rng.integers(0, 256, tuple(shape) + (C,), dtype=np.uint8)
-    pick = rng.random(shape)
-    pred[pick < 0.1] = 0
-    tie = (pick >= 0.1) & (pick < 0.2)
-    top = pred.max(axis=-1)
-    ch = rng.integers(0, C, shape)
-    for c in range(C):
-        pred[..., c] = np.where(tie & ((ch == c) | (ch == (c + 1) % C)), top, pred[..., c])
-    return pred
 
 
 @pytest.mark.parametrize('shape', SHAPES)
@@ -87,7 +74,7 @@ def _volumes():
     yield 'all background', np.zeros((3, 4, 5), np.uint8)
     yield 'one voxel', np.ones((1, 1, 1), np.uint8)
     for C in (2, 3, 16):
-        yield f'pred {C}', _random_pred((9, 10, 13), C, C)
+        yield f'pred {C}', random_pred((9, 10, 13), C, C)
 
 
 @pytest.mark.parametrize('conn', CONN)

@@ -12,6 +12,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests import components_ref as cr
+from tests.volume_inputs import offset_copy, random_pred
 
 CONN = (6, 18, 26)
 
@@ -28,20 +29,6 @@ def _shapes():
 
 
 SHAPE_NAMES = ('ragged', 'three tiles', 'row', 'flat', 'one tile', 'one voxel')
-
-
-def _random_pred(shape, C, seed):
-    """Random bytes, about a tenth of the voxels all-zero and a tenth with a tie at the top (the recipe of tests/test_gpu_propose.py)."""
-    rng = np.random.default_rng(seed)
-    pred = rng.integers(0, 256, tuple(shape) + (C,), dtype=np.uint8)
-    pick = rng.random(shape)
-    pred[pick < 0.1] = 0
-    tie = (pick >= 0.1) & (pick < 0.2)
-    top = pred.max(axis=-1)
-    ch = rng.integers(0, C, shape)
-    for c in range(C):
-        pred[..., c] = np.where(tie & ((ch == c) | (ch == (c + 1) % C)), top, pred[..., c])
-    return pred
 
 
 def _serpentine(shape):
@@ -93,7 +80,7 @@ def _volume(kind, name):
     elif kind == 'straddle':
         v = _straddle(shape)[0]
     else:
-        v = _random_pred(shape, int(kind), 30 + seed)
+        v = random_pred(shape, int(kind), 30 + seed)
     v.setflags(write=False)
     return v
 
@@ -134,10 +121,10 @@ def _table(labels, cls, K):
     return sizes, classes, first
 
 
-def _filter(labels, cls, K, keep, fill, alias=False):
+def _filter(labels, cls, K, keep, fill, alias=False, out=None):
     from interactive_unet import _native as nv
     Z, Y, X = labels.shape
-    out = cls if alias else torch.full((Z, Y, X), 55, dtype=torch.uint8, device='cuda')
+    out = out if out is not None else cls if alias else torch.full((Z, Y, X), 55, dtype=torch.uint8, device='cuda')
     nv.call('iunet_cc_filter', nv.ptr(labels), nv.ptr(cls), Z, Y, X, K, nv.ptr(keep), fill, nv.ptr(out), nv.stream())
     return out
 
@@ -254,6 +241,26 @@ def test_filter(name):
             assert np.array_equal(_filter(ld, odd, K, kd, fill).cpu().numpy(), want), (kind, bg, fill)
             alias = cd.clone()
             assert _filter(ld, alias, K, kd, fill, alias=True) is alias and np.array_equal(alias.cpu().numpy(), want), (kind, bg, fill)
+
+
+@pytest.mark.parametrize('shape', ((1, 1, 3), (1, 5, 821)))
+def test_filter_at_the_streaming_pass_edges(shape):
+    """The pass cc_filter shares with edt_select (volume_select_kernel): fewer voxels than one vector (3); one workgroup's 4096 and a tail
+    that is no multiple of 4 (4105); labels 4 bytes and cls / out 1 byte off the 16-byte grid (one voxel per thread); out aliasing cls."""
+    N = int(np.prod(shape))
+    v = np.array([[[1, 0, 2]]], np.uint8) if N == 3 else np.random.default_rng(N).integers(0, 4, shape).astype(np.uint8)
+    labels, K, cls = cr.label(v, 18, 0)
+    keep = np.array([0, 0, 1], np.uint8) if N == 3 else (np.random.default_rng(K).random(K + 1) < 0.5).astype(np.uint8)   # 3: filled; none; kept
+    ld, cd, kd = torch.tensor(labels).cuda(), torch.tensor(cls).cuda(), torch.tensor(keep).cuda()
+    assert (N == 3 or (N == 4096 + 9 and N % 4)) and ld.data_ptr() % 16 == 0 and cd.data_ptr() % 4 == 0
+    for fill in (0, 9):
+        want = cr.filter_components(labels, cls, keep, fill)
+        assert (want != cls).any()
+        assert np.array_equal(_filter(ld, cd, K, kd, fill).cpu().numpy(), want), fill
+        out = offset_copy(torch.full(shape, 55, dtype=torch.uint8, device='cuda'), 1)
+        assert np.array_equal(_filter(offset_copy(ld, 4), offset_copy(cd, 1), K, kd, fill, out=out).cpu().numpy(), want), fill
+        for alias in (cd.clone(), offset_copy(cd, 1)):
+            assert _filter(ld, alias, K, kd, fill, alias=True) is alias and np.array_equal(alias.cpu().numpy(), want), fill
 
 
 def test_remove_small_and_keep_largest_on_resident_volumes():

@@ -12,7 +12,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests import morphology_ref as mr
-from tests.test_morphology_cpu import blobs, holes_volume, lattice_axis, random_pred, sparse_input
+from tests.test_morphology_cpu import blobs, holes_volume, lattice_axis, sparse_input
+from tests.volume_inputs import offset_copy, random_pred
 
 # ragged; a row; flat; one voxel; one axis longer than any workgroup, in turn along the row and along either column
 SHAPES = {'ragged': (37, 41, 150), 'row': (1, 1, 300), 'flat': (33, 2, 65), 'one voxel': (1, 1, 1), 'long x': (3, 5, 2100),
@@ -80,10 +81,10 @@ def _mask(prevd, r2, above):
     return d2
 
 
-def _select(d2d, clsd, r2, above, only, value, alias=False):
+def _select(d2d, clsd, r2, above, only, value, alias=False, out=None):
     from interactive_unet import _native as nv
     Z, Y, X = d2d.shape
-    out = clsd if alias else torch.full((Z, Y, X), 55, dtype=torch.uint8, device='cuda')
+    out = out if out is not None else clsd if alias else torch.full((Z, Y, X), 55, dtype=torch.uint8, device='cuda')
     nv.call('iunet_edt_select', nv.ptr(d2d), nv.ptr(clsd), Z, Y, X, r2, int(above), only, value, nv.ptr(out), nv.stream())
     return out
 
@@ -192,6 +193,24 @@ def test_select(name):
                 assert np.array_equal(_select(d2d, odd, r2, above, only, value).cpu().numpy(), want), where
                 alias = clsd.clone()
                 assert _select(d2d, alias, r2, above, only, value, alias=True) is alias and np.array_equal(alias.cpu().numpy(), want), where
+
+
+@pytest.mark.parametrize('shape', ((1, 1, 3), (1, 5, 821)))
+def test_select_at_the_streaming_pass_edges(shape):
+    """The cases of test_filter_at_the_streaming_pass_edges (tests/test_gpu_components.py) for the other caller of volume_select_kernel."""
+    N = int(np.prod(shape))
+    v = np.array([[[1, 0, 2]]], np.uint8) if N == 3 else np.random.default_rng(N).integers(0, 4, shape).astype(np.uint8)
+    d2 = mr.distance_sq(v, 1, False)
+    d2d, clsd = torch.tensor(d2).cuda(), torch.tensor(v).cuda()
+    assert (N == 3 or (N == 4096 + 9 and N % 4)) and d2d.data_ptr() % 16 == 0 and clsd.data_ptr() % 4 == 0
+    for r2, above, only, value in ((0, False, -1, 7), (1, False, 0, 7), (1, True, 2, 0), (2, True, -1, 4)):
+        want, where = mr.select(d2, v, r2, above, only, value), (r2, above, only, value)
+        assert (want != v).any()
+        assert np.array_equal(_select(d2d, clsd, r2, above, only, value).cpu().numpy(), want), where
+        out = offset_copy(torch.full(shape, 55, dtype=torch.uint8, device='cuda'), 1)
+        assert np.array_equal(_select(offset_copy(d2d, 4), offset_copy(clsd, 1), r2, above, only, value, out=out).cpu().numpy(), want), where
+        for alias in (clsd.clone(), offset_copy(clsd, 1)):
+            assert _select(d2d, alias, r2, above, only, value, alias=True) is alias and np.array_equal(alias.cpu().numpy(), want), where
 
 
 def test_repeated_launches_and_a_second_stream_give_the_same_bytes():

@@ -11,25 +11,12 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests import propose_ref as pr
+from tests.volume_inputs import offset_copy, random_pred, random_slicer
 
 E = np.eye(3)
 VOLUMES = ((9, 10, 13), (17, 31, 70), (5, 7, 67), (6, 9, 40))   # ragged on every axis; rows longer than a wave; one brick row of long rows;
                                                                # rows of whole 16-byte slots at 2 and 16 classes (the staging's aligned path)
 CLASSES = (2, 3, 5, 16)                                  # 3 and 5: a row's byte count is no multiple of any load width
-
-
-def _random_pred(shape, C, seed):
-    """Random bytes, about a tenth of the voxels all-zero and a tenth with a tie at the top."""
-    rng = np.random.default_rng(seed)
-    pred = rng.integers(0, 256, tuple(shape) + (C,), dtype=np.uint8)
-    pick = rng.random(shape)
-    pred[pick < 0.1] = 0
-    tie = (pick >= 0.1) & (pick < 0.2)
-    top = pred.max(axis=-1)
-    ch = rng.integers(0, C, shape)
-    for c in range(C):
-        pred[..., c] = np.where(tie & ((ch == c) | (ch == (c + 1) % C)), top, pred[..., c])
-    return pred
 
 
 def _sparse(shape, ch, seed, zero_share):
@@ -53,7 +40,7 @@ def _uncertainty(pd, wd, imd, g, want_u=True, want_bricks=True):
 @pytest.mark.parametrize('C', CLASSES)
 @pytest.mark.parametrize('shape', VOLUMES)
 def test_uncertainty_volume_is_the_definition(shape, C):
-    pred = _random_pred(shape, C, C + shape[2])
+    pred = random_pred(shape, C, C + shape[2])
     pd = torch.tensor(pred).cuda()
     never, tie = (pred.max(-1) == 0).mean(), (pr.uncertainty(pred) == 255).mean()
     assert 0.03 < never < 0.2 and 0.03 < tie < 0.25, (never, tie)
@@ -82,7 +69,7 @@ def test_uncertainty_volume_is_the_definition(shape, C):
 def test_uncertainty_volume_on_wide_runs(shape, xs):
     """Volumes of 2048 brick runs at brick 4: the launch keeps runs of 128 and 256 voxels (it halves them, down to 64, only while the grid
     has fewer workgroups than that); the last run holds a single voxel, or 16 (rows of whole 16-byte slots: the staging's aligned path).  The larger bricks take runs of 64 on the same volumes."""
-    pred, weight, image = _random_pred(shape, 2, 1), _sparse(shape, 1, 2, 0.7), _sparse(shape, 1, 3, 0.2)
+    pred, weight, image = random_pred(shape, 2, 1), _sparse(shape, 1, 2, 0.7), _sparse(shape, 1, 3, 0.2)
     assert (shape[0] // 4) * (shape[1] // 4) * -(-shape[2] // xs) == 2048
     pd, wd, imd = (torch.tensor(t).cuda() for t in (pred, weight, image))
     for w, wdev, im, imdev in ((None, None, None, None), (weight, wd, image, imd)):
@@ -96,15 +83,9 @@ def test_uncertainty_volume_on_wide_runs(shape, xs):
 def test_uncertainty_volume_on_an_unaligned_volume():
     """Volumes that start at an odd byte: the 16-byte grid of the loads is the address's, not the row's."""
     shape, C = (9, 10, 13), 3
-    pred, weight, image = _random_pred(shape, C, 2), _sparse(shape, 2, 3, 0.7), _sparse(shape, 1, 4, 0.2)
+    pred, weight, image = random_pred(shape, C, 2), _sparse(shape, 2, 3, 0.7), _sparse(shape, 1, 4, 0.2)
     want = pr.uncertainty(pred, weight, image)
-
-    def shifted(a, by):
-        buf = torch.zeros(a.size + 16, dtype=torch.uint8, device='cuda')
-        view = buf[by:by + a.size].view(a.shape)
-        view.copy_(torch.tensor(a))
-        assert view.data_ptr() % 16 == by
-        return view
+    shifted = lambda a, by: offset_copy(torch.tensor(a).cuda(), by)
     for by in (1, 7, 15):
         u, bricks = _uncertainty(shifted(pred, by), shifted(weight, (by + 3) % 16), shifted(image, (by + 6) % 16), 4)
         assert np.array_equal(u.cpu().numpy(), want), by
@@ -116,20 +97,11 @@ SCORE_VOLUMES = ((20, 24, 28), (17, 31, 22))
 WIDTHS = (13, 16, 70)
 
 
-def _random_slicer(shape, seed):
-    from interactive_unet.slicer import Slicer
-    np.random.seed(seed)
-    s = Slicer(list(shape))
-    s.randomize()
-    s.origin = np.array(shape) / 2 + np.random.uniform(-1, 1, 3)
-    return s
-
-
 def _geometries(shape):
     """name -> (a, b, origin)."""
     c = np.array([s // 2 for s in shape], dtype=float)
     g = {f'axes {p}': (E[p[0]], E[p[1]], c) for p in ((1, 2), (2, 1), (0, 2), (0, 1), (2, 0), (1, 0))}
-    s = _random_slicer(shape, 3)
+    s = random_slicer(shape, 3)
     o = np.asarray(s.origin, dtype=float)
     for axis, (a, b) in enumerate(((s.v, s.w), (s.u, s.w), (s.u, s.v))):
         g[f'random {axis}'] = (np.asarray(a, float), np.asarray(b, float), o)
@@ -187,6 +159,21 @@ def test_plane_scores_are_the_definition(shape):
     many[:, 2] += rng.uniform(-2, 2, (300, 3))
     for sw in (16, 70):
         assert np.array_equal(_scores(ud, many, sw), pr.score_planes(u, many, sw)), sw
+
+
+def test_plane_scores_count_the_slab_gathers_samples():
+    """plane_scores applies the plane point, the inside test and the order-0 sample of csrc/volume_rules.h as slab_gather does: on a
+    volume without zero bytes its (score, inside) is the sum and the number of non-zero bytes of that plane."""
+    from tests import test_gpu_slab as ts
+    shape, sw = ts.SAMPLER_SHAPE, ts.SAMPLER_WIDTH
+    u = ts._volume(shape, 3)
+    assert u.all() and pr.default_start(sw) == ts.sr.default_start(sw)
+    ud = torch.tensor(u).cuda()
+    for name in ts.SAMPLER_GEOMETRIES:
+        a, b, n, o = ts._geometries(shape)[name]
+        plane = ts._gather(ud, (a, b, n, o), 1, sw, 0)[0]
+        got = _scores(ud, np.stack([a, b, o])[None], sw)
+        assert got.tolist() == [[int(plane.sum(dtype=torch.int64)), int((plane != 0).sum())]] and 0 < got[0, 1] < sw * sw, name
 
 
 # ---- the host layer end to end ---------------------------------------------------------------------------------------------

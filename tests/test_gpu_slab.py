@@ -12,6 +12,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests import slab_ref as sr
+from tests.volume_inputs import random_slicer
 
 E = np.eye(3)
 VOLUMES = ((20, 24, 28), (17, 31, 22))
@@ -26,6 +27,16 @@ def _geom12(geom):
     return (ctypes.c_double * 12)(*[float(t) for v in geom for t in v])
 
 
+def _slice_plane(vd, geom, sw, order):
+    """iunet_slice_gather's plane of (a, b, origin) with the whole volume as its crop box."""
+    from interactive_unet import _native as nv
+    a, b, _, o = geom
+    plane = torch.full((sw, sw), 55, dtype=torch.uint8, device='cuda')
+    nv.call('iunet_slice_gather', nv.ptr(vd), vd.shape[0], vd.shape[1], vd.shape[2], (ctypes.c_double * 9)(*a, *b, *o), nv.int_array((0, 0, 0)),
+            nv.int_array(vd.shape), sw, sr.default_start(sw), order, nv.ptr(plane), nv.stream())
+    return plane
+
+
 def _gather(vd, geom, T, sw, order):
     from interactive_unet import _native as nv
     out = torch.empty((T, sw, sw), dtype=torch.uint8, device='cuda')
@@ -34,20 +45,11 @@ def _gather(vd, geom, T, sw, order):
     return out
 
 
-def _random_slicer(shape, seed):
-    from interactive_unet.slicer import Slicer
-    np.random.seed(seed)
-    s = Slicer(list(shape))
-    s.randomize()
-    s.origin = np.array(shape) / 2 + np.random.uniform(-1, 1, 3)
-    return s
-
-
 def _geometries(shape):
     """name -> (a, b, n, origin)."""
     c = np.array([s // 2 for s in shape], dtype=float)
     g = {f'axes {p}': (E[p[0]], E[p[1]], E[p[2]], c) for p in ((1, 2, 0), (2, 1, 0), (0, 2, 1), (0, 1, 2), (2, 0, 1), (1, 0, 2))}
-    s = _random_slicer(shape, 3)
+    s = random_slicer(shape, 3)
     for axis in range(3):
         g[f'random {axis}'] = sr.slicer_geometry(s, axis)
     a, b, n, o = g['random 0']
@@ -61,7 +63,6 @@ def _geometries(shape):
 
 @pytest.mark.parametrize('shape', VOLUMES)
 def test_gather_is_the_restatement(shape):
-    from interactive_unet import _native as nv
     vol = _volume(shape, 1)
     vd = torch.tensor(vol).cuda()
     for name, geom in _geometries(shape).items():
@@ -81,18 +82,34 @@ def test_gather_is_the_restatement(shape):
                 if name.startswith('axes') and order == 1:
                     assert np.array_equal(want, sr.gather(vol, geom, T, sw, 0))
                 # the centre plane is iunet_slice_gather's with the whole volume as its crop box
-                a, b, _, o = geom
-                plane = torch.empty((sw, sw), dtype=torch.uint8, device='cuda')
-                nv.call('iunet_slice_gather', nv.ptr(vd), shape[0], shape[1], shape[2], (ctypes.c_double * 9)(*a, *b, *o),
-                        nv.int_array((0, 0, 0)), nv.int_array(shape), sw, sr.default_start(sw), order, nv.ptr(plane), nv.stream())
-                assert torch.equal(got[T // 2], plane), (name, T, sw, order)
+                assert torch.equal(got[T // 2], _slice_plane(vd, geom, sw, order)), (name, T, sw, order)
+
+
+SAMPLER_SHAPE, SAMPLER_WIDTH = (9, 17, 70), 70           # two ragged 64-lane groups per row of samples
+SAMPLER_GEOMETRIES = ('random 0', 'half-integer', 'edge', 'mostly outside')
+
+
+def test_the_sampler_is_one_rule_for_slab_and_slice():
+    """The plane point, the inside test and the order-0 / order-1 samplers are written once (csrc/volume_rules.h): slab_gather (64 lanes
+    along j, 4 rows per workgroup, the whole volume) and slice_gather (16 x 16 tiles, a crop that is the whole volume) give the same bytes."""
+    shape, sw = SAMPLER_SHAPE, SAMPLER_WIDTH
+    vol = _volume(shape, 3)
+    assert vol.all() and sr.default_start(1) == 0
+    vd = torch.tensor(vol).cuda()
+    for name in SAMPLER_GEOMETRIES:
+        geom = _geometries(shape)[name]
+        for order in (0, 1):
+            slab = _gather(vd, geom, 1, sw, order)[0]
+            assert torch.equal(slab, _slice_plane(vd, geom, sw, order)), (name, order)
+            assert np.array_equal(slab.cpu().numpy(), sr.gather(vol, geom, 1, sw, order)[0]), (name, order)
+            assert 0 < int((slab != 0).sum()) < sw * sw, (name, order)        # the plane is wider than the volume: samples on both sides of its faces
 
 
 def test_get_slab_on_a_resident_volume():
     shape = VOLUMES[0]
     vol = _volume(shape, 2)
     vd = torch.tensor(vol).cuda()
-    s = _random_slicer(shape, 5)
+    s = random_slicer(shape, 5)
     for axis in range(3):
         for order in (0, 1):
             got = s.get_slab(vd, axis=axis, slice_width=16, depth=8, order=order)
@@ -197,7 +214,7 @@ def test_predict_slab_is_the_engines_forward_on_the_slab(model, T, S):
     from interactive_unet.slicer import Slicer
     vol = _volume(VSHAPE, 4)
     vd = torch.tensor(vol).cuda()
-    s = _random_slicer(VSHAPE, 6)
+    s = random_slicer(VSHAPE, 6)
     for axis, order in ((0, 1), (2, 0)):
         slab, cls, probs = predict.predict_slab(model, vd, s, slice_width=S, depth=T, axis=axis, order=order)
         assert slab.shape == (T, S, S) and slab.dtype == torch.uint8 and cls.shape == (T, S, S) and cls.dtype == torch.uint8
@@ -226,7 +243,7 @@ def test_predict_slice_3d_from_a_checkpoint(model, tmp_path, monkeypatch):
     model.save_checkpoint(os.path.join('model', 'model.ckpt'))
     T, S = 8, 32
     vd = torch.tensor(_volume(VSHAPE, 4)).cuda()
-    s = _random_slicer(VSHAPE, 7)
+    s = random_slicer(VSHAPE, 7)
     _, cls, probs = predict.predict_slab(model, vd, s, slice_width=S, depth=T)
     rgb = predict.predict_slice_3d(vd, s, slice_width=S, depth=T)
     assert isinstance(rgb, np.ndarray) and rgb.shape == (S, S, 3) and rgb.dtype == np.uint8
@@ -243,7 +260,7 @@ def test_update_predicted_volume_pastes_the_core(model):
     from interactive_unet import predict
     T, S, C = 8, 32, 2
     vd = torch.tensor(_volume(VSHAPE, 4)).cuda()
-    s = _random_slicer(VSHAPE, 8)
+    s = random_slicer(VSHAPE, 8)
     _, _, probs = predict.predict_slab(model, vd, s, slice_width=S, depth=T, axis=1)
     dest = _pattern(VSHAPE, C)
     geom = sr.slicer_geometry(s, 1)

@@ -10,6 +10,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests import tta_ref as tr
+from tests.volume_inputs import random_slicer
 
 TRANSPOSING = tuple(8 * pi + f for pi in (1, 3, 4, 5) for f in range(8))
 # ragged tiles / a degenerate axis and a row longer than a tile (the issue's three); rows of whole 16-byte chunks (the wide row copy)
@@ -267,21 +268,12 @@ def test_score_planes_reads_the_spread_volume(flips):
     assert np.array_equal(got.cpu().numpy(), want) and want[:, 0].min() > 0
 
 
-def _random_slicer(shape, seed):
-    from interactive_unet.slicer import Slicer
-    np.random.seed(seed)
-    s = Slicer(list(shape))
-    s.randomize()
-    s.origin = np.array(shape) / 2 + np.random.uniform(-1, 1, 3)
-    return s
-
-
 @pytest.mark.parametrize('spec', ('planar', (0, 8 * 3 + 2, 8 * 4 + 5, 8 * 5)))
 def test_predict_slab_ensemble(model, volume, spec):
     """'planar' keeps the slab's shape; pi = 3, 4, 5 turn the (16, 32, 32) slab into (32, 32, 16) / (32, 16, 32)."""
     from interactive_unet import predict, tta
     vd = torch.tensor(volume).cuda()
-    s = _random_slicer(VSHAPE, 6)
+    s = random_slicer(VSHAPE, 6)
     T, S = 16, 32
     slab, cls, probs = predict.predict_slab(model, vd, s, slice_width=S, depth=T, tta=spec)
     assert torch.equal(slab, s.get_slab(vd, axis=0, slice_width=S, depth=T, order=1))

@@ -28,6 +28,7 @@ from tests import propose_ref as pr
 from tests import slab_ref as sr
 from tests import volume_scale_ref as vs
 from tests.test_gpu_components import _filter, _label, _table
+from tests.volume_inputs import random_pred
 
 
 def _free():
@@ -135,7 +136,7 @@ def test_components_of_a_thin_volume_of_more_tiles_than_the_grid(bg, conn):
 def test_components_of_a_predicted_volume_past_2_32_bytes(bg):
     """A.3: uint8 [700, 1201, 1301, 4] -- the class of voxel v is read at byte 4 v, up to 4.37e9."""
     Z, Y, X, C = vs.A3_SHAPE
-    block = vs.random_pred((vs.A3_BZ, Y, X), C, 44)
+    block = random_pred((vs.A3_BZ, Y, X), C, 44)
     t, K = _tiled(block, vs.copies(vs.A3_SHAPE, vs.A3_BZ), 18, bg, 0, 35, 2)
     assert np.array_equal(t.cls_B.cpu().numpy(), cr.class_map(block, bg)[0]) and K > 0
 

@@ -13,6 +13,7 @@ import torch
 from scipy import ndimage
 
 from tests import morphology_ref as mr
+from tests.volume_inputs import random_pred
 
 CONN = (6, 18, 26)
 RADII = (0, 1, 1.5, 2, 3)
@@ -71,20 +72,6 @@ def lattice_axis(n, step):
 
 def sparse_input():
     return np.random.default_rng(40).random((37, 41, 150)) < 0.0005
-
-
-def random_pred(shape, C, seed):
-    """Random bytes, about a tenth of the voxels all-zero and a tenth with a tie at the top (the recipe of tests/test_gpu_components.py)."""
-    rng = np.random.default_rng(seed)
-    pred = rng.integers(0, 256, tuple(shape) + (C,), dtype=np.uint8)
-    pick = rng.random(shape)
-    pred[pick < 0.1] = 0
-    tie = (pick >= 0.1) & (pick < 0.2)
-    top = pred.max(axis=-1)
-    ch = rng.integers(0, C, shape)
-    for c in range(C):
-        pred[..., c] = np.where(tie & ((ch == c) | (ch == (c + 1) % C)), top, pred[..., c])
-    return pred
 
 
 def _brute(seeds):

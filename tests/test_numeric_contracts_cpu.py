@@ -85,17 +85,25 @@ def test_reference_layouts():
 
 
 ONE_DEFINITION = ['float bn_fold_scale(', 'float bn_fold_mul(', 'float bn_fold_bias(', 'float round_e4m3(', 'unsigned char encode_e4m3(',
-                  'float e4m3_scale(', 'float split_row_scale(', 'float block_max_256(', 'void head_store(', 'struct HeadOut {']
+                  'float e4m3_scale(', 'float split_row_scale(', 'float block_max_256(', 'void head_store(', 'struct HeadOut {',
+                  # the resident-volume rules (volume_rules.h): plane point, inside test, samplers, class, streaming select, host helpers
+                  'double plane_point(', 'double slab_point(', 'bool coord_inside(', 'double coord_nearest(', 'int volume_mirror(',
+                  'unsigned char volume_sample_linear(', 'TopByte volume_top_byte(', 'void volume_select_kernel(', 'void volume_select_launch(',
+                  'long long volume_align16(', 'bool volume_ok(', 'unsigned int volume_grid(', 'define VOLUME_REQUIRE_DIMS(']
+HOMES = ('common.h', 'head_out.h', 'volume_rules.h')
 
 
 def test_each_shared_contract_is_defined_once():
     text = {p: open(p).read() for p in glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(CSRC, '*.hip'))}
     for needle in ONE_DEFINITION:
         hits = [(os.path.basename(p), t.count(needle)) for p, t in text.items() if needle in t]
-        assert len(hits) == 1 and hits[0][1] == 1 and hits[0][0] in ('common.h', 'head_out.h'), (needle, hits)
-    # what the single definitions replaced stays gone: hand-written folds, the second e4m3 codec, the head's fields copied into a struct
+        assert len(hits) == 1 and hits[0][1] == 1 and hits[0][0] in HOMES, (needle, hits)
+    # what the single definitions replaced stays gone: hand-written folds, the second e4m3 codec, the head's fields copied into a struct,
+    # the resident-volume kernels' own mirrors, alignment helpers and streaming passes
     for p, t in text.items():
-        if os.path.basename(p) in ('common.h', 'head_out.h'):
+        assert not re.search(r'\b(slab_mirror|mirror_idx|cc_align16|ed_align16|filter_kernel|select_kernel)\b', t), \
+            f'{os.path.basename(p)}: a retired copy of a resident-volume rule is back'
+        if os.path.basename(p) in HOMES:
             continue
         assert not re.search(r'/\s*sqrtf\(\s*(\w+\.)?var\b', t), f'{os.path.basename(p)}: a BatchNorm scale written out by hand'
         assert not re.search(r'\b(f8_round_e4m3|f8_encode_e4m3|mul_rn)\b', t), f'{os.path.basename(p)}: a retired copy is back'

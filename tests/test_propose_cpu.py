@@ -10,23 +10,10 @@ import torch
 
 from tests import propose_ref as pr
 from tests import slab_ref as sr
+from tests.volume_inputs import random_pred
 
 E = np.eye(3)
 VOXELS = (((255, 0), 0), ((128, 127), 254), ((100, 100), 255), ((0, 0), 0), ((10, 200, 200), 255), ((7, 0, 0), 248))
-
-
-def _random_pred(shape, C, seed):
-    """Random bytes, about a tenth of the voxels all-zero and a tenth with a tie at the top."""
-    rng = np.random.default_rng(seed)
-    pred = rng.integers(0, 256, tuple(shape) + (C,), dtype=np.uint8)
-    pick = rng.random(shape)
-    pred[pick < 0.1] = 0
-    tie = (pick >= 0.1) & (pick < 0.2)
-    top = pred.max(axis=-1)
-    ch = rng.integers(0, C, shape)
-    for c in range(C):
-        pred[..., c] = np.where(tie & ((ch == c) | (ch == (c + 1) % C)), top, pred[..., c])
-    return pred
 
 
 def _sparse(shape, ch, seed, zero_share=0.7):
@@ -53,7 +40,7 @@ def test_hand_made_voxels(q, want):
 
 
 def test_random_tie_and_zero_shares():
-    pred = _random_pred((9, 10, 13), 3, 0)
+    pred = random_pred((9, 10, 13), 3, 0)
     u = pr.uncertainty(pred)
     never, tie = (pred.max(-1) == 0), (u == 255)
     assert 0.03 < never.mean() < 0.2 and 0.03 < tie.mean() < 0.2 and not u[never].any()
@@ -63,7 +50,7 @@ def test_random_tie_and_zero_shares():
 
 def test_brick_sums_on_a_ragged_volume():
     shape, g = (9, 10, 13), 4
-    u = pr.uncertainty(_random_pred(shape, 2, 1))
+    u = pr.uncertainty(random_pred(shape, 2, 1))
     want = np.zeros((3, 3, 4), dtype=np.int64)
     for z in range(shape[0]):
         for y in range(shape[1]):
@@ -114,7 +101,7 @@ def test_plane_wholly_outside_scores_nothing():
 def test_numpy_uncertainty_is_the_definition(C):
     from interactive_unet import propose
     shape = (9, 10, 13)
-    pred = _random_pred(shape, C, C)
+    pred = random_pred(shape, C, C)
     for weight in (None, _sparse(shape, 0, 1), _sparse(shape, 1, 2), _sparse(shape, 2, 3)):
         for image in (None, _sparse(shape, 0, 4, 0.2), _sparse(shape, 3, 5, 0.2)):
             want = pr.uncertainty(pred, weight, image)
@@ -223,7 +210,7 @@ def test_propose_slices_on_the_planted_blob():
 def test_propose_slices_on_random_bytes_with_weight_and_image():
     from interactive_unet import propose
     shape = (17, 31, 22)
-    pred, weight, image = _random_pred(shape, 3, 8), _sparse(shape, 2, 9, 0.9), _sparse(shape, 0, 10, 0.2)
+    pred, weight, image = random_pred(shape, 3, 8), _sparse(shape, 2, 9, 0.9), _sparse(shape, 0, 10, 0.2)
     kw = dict(weight=weight, image=image, slice_width=13, brick=4, candidates=5, orientations=3)
     found = propose.propose_slices(shape, pred, generator=_gen(3), **kw)
     assert len(found) == 15 and _restated(shape, pred, found, _gen(3), **kw)

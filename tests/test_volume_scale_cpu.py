@@ -14,6 +14,7 @@ from tests import patch_ref
 from tests import propose_ref as pr
 from tests import slab_ref as sr
 from tests import volume_scale_ref as vs
+from tests.volume_inputs import random_pred
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'interactive-unet_amd', 'csrc')
 
@@ -90,7 +91,7 @@ def _blocks():
     shape = (5, 19, 70)
     return {'binary': ((rng.random(shape) < 0.5).astype(np.uint8), 2),
             'three classes': (rng.integers(0, 3, shape).astype(np.uint8), 3),
-            'pred': (vs.random_pred(shape, 3, 6), 0)}
+            'pred': (random_pred(shape, 3, 6), 0)}
 
 
 @pytest.mark.parametrize('conn', (6, 18, 26))

@@ -120,20 +120,6 @@ class Tiled(object):
         return sizes, classes, torch.cat([head(-1, torch.int32), first.to(torch.int32)])
 
 
-def random_pred(shape, C, seed):
-    """Random bytes, about a tenth of the voxels all-zero and a tenth with a tie at the top (the recipe of tests/test_gpu_components.py)."""
-    rng = np.random.default_rng(seed)
-    pred = rng.integers(0, 256, tuple(shape) + (C,), dtype=np.uint8)
-    pick = rng.random(shape)
-    pred[pick < 0.1] = 0
-    tie = (pick >= 0.1) & (pick < 0.2)
-    top = pred.max(axis=-1)
-    ch = rng.integers(0, C, shape)
-    for c in range(C):
-        pred[..., c] = np.where(tie & ((ch == c) | (ch == (c + 1) % C)), top, pred[..., c])
-    return pred
-
-
 # ---- dyadic geometries ----------------------------------------------------------------------------------------------------
 # Direction vectors and origins whose components are multiples of 2^-8 (|direction| <= 2, origin < 4096): with integer sample offsets
 # below 2^12 every product has at most 10 + 12 significant bits and every sum is a multiple of 2^-8 below 2^14 -- 22 bits --, so every
