@@ -24,6 +24,7 @@
 #include "gather_gemm.h"
 #include "head_out.h"
 #include "loss_terms.h"
+#include "resample.h"
 
 namespace {
 
@@ -300,32 +301,23 @@ __global__ __launch_bounds__(256) void dl_dropout_kernel(const T* __restrict__ y
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int c = pl * 8 + j;
-    float z = mode == 0 ? to_f32<T>(from_f32<T>(fmaxf(fmaf(scale[c], to_f32<T>(a[j]), shift[c]), 0.f))) : to_f32<T>(a[j]);
+    float z = mode == 0 ? norm_z<T, true>(scale[c], to_f32<T>(a[j]), shift[c]) : to_f32<T>(a[j]);
     if (mask != nullptr) z = mask[((long long)n * C + c) * vox + v] ? z * inv_keep : 0.f;
     o[j] = from_f32<T>(z);
   }
   *(V8T<T>*)(out + n * o_ss + off) = o;
 }
 
-// ---- logit upsampling, align_corners=True: fine index o on an axis of E_f = s E_c voxels reads coarse i0 = floor(src), i1 = min(i0 + 1,
-// E_c - 1) with weights (1 - f, f), src = o (E_c - 1) / (E_f - 1), f = src - i0
-__device__ __forceinline__ void dl_lerp(int o, int Ec, int Ef, int& i0, int& i1, float& f) {
-  const float sc = Ef > 1 ? (float)(Ec - 1) / (float)(Ef - 1) : 0.f;
-  const float src = sc * (float)o;
-  i0 = min((int)src, Ec - 1);
-  i1 = min(i0 + 1, Ec - 1);
-  f = src - (float)i0;
-}
-
+// ---- logit upsampling, align_corners=True: resample_axis_corners of resample.h
 // the fine logits of voxel (d, h, w) of sample n from coarse fp32 [N][NCLS][Dc][Hc][Wc]
 template <int NCLS, int ND>
 __device__ __forceinline__ void dl_up_logits(const float* lc, int n, int d, int h, int w, int Dc, int Hc, int Wc, int Df, int Hf, int Wf,
                                              float (&l)[NCLS]) {
-  int d0 = 0, d1 = 0, h0, h1, w0, w1;
-  float fd = 0.f, fh, fw;
-  if constexpr (ND == 3) dl_lerp(d, Dc, Df, d0, d1, fd);
-  dl_lerp(h, Hc, Hf, h0, h1, fh);
-  dl_lerp(w, Wc, Wf, w0, w1, fw);
+  ResampleAx ad = {0, 0, 0.f};
+  if constexpr (ND == 3) ad = resample_axis_corners(d, Df, Dc);
+  const ResampleAx ah = resample_axis_corners(h, Hf, Hc), aw = resample_axis_corners(w, Wf, Wc);
+  const int d0 = ad.i0, d1 = ad.i1, h0 = ah.i0, h1 = ah.i1, w0 = aw.i0, w1 = aw.i1;
+  const float fd = ad.l1, fh = ah.l1, fw = aw.l1;
   const long long vc = (long long)Dc * Hc * Wc;
 #pragma unroll
   for (int c = 0; c < NCLS; ++c) {
@@ -429,12 +421,7 @@ __global__ __launch_bounds__(256) void dl_up_adjoint_kernel(const float* __restr
   }
   float s = 0.f;
   for (int o = lo; o <= hi; ++o) {
-    int i0, i1;
-    float f;
-    dl_lerp(o, Ec, Ef, i0, i1, f);
-    float wgt = 0.f;
-    if (i0 == c) wgt += 1.f - f;
-    if (i1 == c) wgt += f;
+    const float wgt = resample_adj_w<resample_axis_corners>(o, c, Ef, Ec);
     if (wgt != 0.f) s = fmaf(wgt, in[(ou * Ef + o) * inner + in_i], s);
   }
   out[i] = s;

@@ -24,6 +24,7 @@
 // stored): the row launch walks j twice, first for delta (written for the column launch), then for dKc.
 // Every sum is fp32 in a fixed order (MFMA chains, xor trees, serial loops): no float atomics, a repeated launch is bit-equal.
 #include "common.h"
+#include "resample.h"
 
 namespace {
 
@@ -529,38 +530,7 @@ __global__ __launch_bounds__(256) void ma_gate_bwd_kernel(MaGateBwd p) {
 }
 
 // ---- gated nearest upsampling
-template <typename T> struct MaLay { static constexpr int G = 8; };
-template <> struct MaLay<float> { static constexpr int G = 1; };
-
-template <typename T>
-__device__ __forceinline__ void ma_ld(const T* s, int g, long long v, long long vox, float (&out)[MaLay<T>::G]) {
-  if constexpr (std::is_same<T, float>::value) {
-    out[0] = s[(long long)g * vox + v];
-  } else {
-    const V8T<T> b = *(const V8T<T>*)(s + ((long long)g * vox + v) * 8);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) out[j] = to_f32<T>(b[j]);
-  }
-}
-template <typename T>
-__device__ __forceinline__ void ma_st(T* s, int g, long long v, long long vox, const float (&val)[MaLay<T>::G]) {
-  if constexpr (std::is_same<T, float>::value) {
-    s[(long long)g * vox + v] = val[0];
-  } else {
-    V8T<T> o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = from_f32<T>(val[j]);
-    *(V8T<T>*)(s + ((long long)g * vox + v) * 8) = o;
-  }
-}
-// relu(scale x + shift) as iunet_bn_relu_fwd stores it
-template <typename T>
-__device__ __forceinline__ float ma_act(float v, const float* sc, const float* sh, int c) {
-  v = fmaxf(fmaf(sc[c], v, sh[c]), 0.f);
-  if constexpr (!std::is_same<T, float>::value) v = rounded<T>(v);
-  return v;
-}
-
+// (channel groups: ChanGroup / group_load / group_store of resample.h; the prologue is norm_z<T, true>: iunet_bn_relu_fwd's bits)
 struct MaUp {
   const void* h; long long h_ss;                  // on the coarse grid D H W
   const float* sc; const float* sh;               // prologue of h (or null)
@@ -574,7 +544,7 @@ struct MaUp {
 // one thread = one channel group of one fine voxel
 template <typename T, int ND, bool ACT>
 __global__ __launch_bounds__(256) void ma_up_gate_kernel(MaUp p) {
-  constexpr int G = MaLay<T>::G;
+  constexpr int G = ChanGroup<T>::G;
   const int Df = ND == 3 ? 2 * p.D : 1, Hf = 2 * p.H, Wf = 2 * p.W;
   const long long vF = (long long)Df * Hf * Wf, vC = (long long)p.D * p.H * p.W;
   const int groups = p.C / G;
@@ -585,13 +555,13 @@ __global__ __launch_bounds__(256) void ma_up_gate_kernel(MaUp p) {
   const int w = (int)(r % Wf), hh = (int)((r / Wf) % Hf), d = (int)(r / ((long long)Wf * Hf));
   const long long src = ((long long)(ND == 3 ? d >> 1 : 0) * p.H + (hh >> 1)) * p.W + (w >> 1);
   float v[G];
-  ma_ld<T>((const T*)p.h + (long long)n * p.h_ss, g, src, vC, v);
+  group_load<T>((const T*)p.h + (long long)n * p.h_ss, g, src, vC, v);
 #pragma unroll
   for (int j = 0; j < G; ++j) {
-    if constexpr (ACT) v[j] = ma_act<T>(v[j], p.sc, p.sh, g * G + j);
+    if constexpr (ACT) v[j] = norm_z<T, true>(p.sc[g * G + j], v[j], p.sh[g * G + j]);
     v[j] *= p.g[(long long)n * p.C + g * G + j];
   }
-  ma_st<T>((T*)p.out + (long long)n * p.out_ss, g, r, vF, v);
+  group_store<T>((T*)p.out + (long long)n * p.out_ss, g, r, vF, v);
 }
 
 // the sum of du over the 2^ND children of a coarse voxel, in (d, h, w) order
@@ -607,7 +577,7 @@ __device__ __forceinline__ void ma_child_sum(const T* du, int g, int d, int hh, 
 #pragma unroll
       for (int kw = 0; kw < 2; ++kw) {
         float t[8];
-        ma_ld<T>(du, g, ((long long)(ND == 3 ? 2 * d + kd : 0) * Hf + 2 * hh + kh) * Wf + 2 * w + kw, vF, t);
+        group_load<T>(du, g, ((long long)(ND == 3 ? 2 * d + kd : 0) * Hf + 2 * hh + kh) * Wf + 2 * w + kw, vF, t);
 #pragma unroll
         for (int j = 0; j < 8; ++j) s[j] += t[j];
       }
@@ -637,11 +607,11 @@ __global__ __launch_bounds__(256) void ma_up_gate_dg_kernel(MaUp p, float* out) 
   for (long long cv = lo + threadIdx.x; cv < hi; cv += 256) {
     const int w = (int)(cv % p.W), hh = (int)((cv / p.W) % p.H), d = (int)(cv / ((long long)p.W * p.H));
     float hv[8], s[8];
-    ma_ld<T>(h, g, cv, vC, hv);
+    group_load<T>(h, g, cv, vC, hv);
     ma_child_sum<T, ND>(du, g, d, hh, w, p.H, p.W, vF, s);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      if constexpr (ACT) hv[j] = ma_act<T>(hv[j], p.sc, p.sh, g * 8 + j);
+      if constexpr (ACT) hv[j] = norm_z<T, true>(p.sc[g * 8 + j], hv[j], p.sh[g * 8 + j]);
       acc[j] = fmaf(hv[j], s[j], acc[j]);
     }
   }
@@ -683,7 +653,7 @@ __global__ __launch_bounds__(256) void ma_up_gate_bwd_kernel(MaUp p) {
     const long long nc = (long long)n * p.C + g * 8 + j;
     s[j] = fmaf(p.g[nc], s[j], p.dmean != nullptr ? p.dmean[nc] * inv : 0.f);
   }
-  ma_st<T>((T*)p.out + (long long)n * p.out_ss, g, cv, vC, s);
+  group_store<T>((T*)p.out + (long long)n * p.out_ss, g, cv, vC, s);
 }
 
 // dx[n][c][v] += dmean[n][c] / vox (the skip's share of its gate's gradient)
@@ -694,11 +664,11 @@ __global__ __launch_bounds__(256) void ma_add_mean_kernel(T* dx, long long dx_ss
   const long long v = i % vox;
   const int g = (int)((i / vox) % (C / 8)), n = (int)(i / (vox * (C / 8)));
   float a[8];
-  ma_ld<T>(dx + (long long)n * dx_ss, g, v, vox, a);
+  group_load<T>(dx + (long long)n * dx_ss, g, v, vox, a);
   const float inv = 1.f / (float)vox;
 #pragma unroll
   for (int j = 0; j < 8; ++j) a[j] = fmaf(dmean[(long long)n * C + g * 8 + j], inv, a[j]);
-  ma_st<T>(dx + (long long)n * dx_ss, g, v, vox, a);
+  group_store<T>(dx + (long long)n * dx_ss, g, v, vox, a);
 }
 
 int ma_check_attn(const char* what, int Cb, int T, int N) {

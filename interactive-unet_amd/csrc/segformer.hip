@@ -10,19 +10,19 @@
 // r = sum over (n, t) of dZ):
 //   G_l = dZ R_l(X^l)^T (gather_gemm.h's staged weight gradient under the SfResample policy), dW_l = W_f,l^T G_l,
 //   dW_f,l = G_l W_l^T + r b_l^T, db_l = W_f,l^T r (sf_param_grad_kernel),
-//   dX^l = R_l^T(M_l^T dZ) (M^T dZ by iunet_dl_conv_fwd at rate 0 with the transposed operator, R^T by sf_adjoint_kernel).
+//   dX^l = R_l^T(M_l^T dZ) (M^T dZ by iunet_dl_conv_fwd at rate 0 with the transposed operator, R^T by iunet_sf_adjoint).
 //
-// Resampling.  PyTorch's linear interpolation with align_corners=False and an output size: per axis src = max(0, (t + 0.5) in / out - 0.5),
-// i0 = floor(src), i1 = i0 + (i0 < in - 1), weights (1 - lambda, lambda), lambda = src - i0.  The sources are the encoder's NHWC8c tensors
-// (16-bit) or planar fp32 tensors, each with its own grid: the kernels take any source grid, so the ratios -2 .. +3 of the network and
-// odd grids are one code path.  The taps are summed in fp32 in a fixed order and rounded once to the MFMA input type.  An optional
-// per-source relu(scale x + shift) prologue applies a BatchNorm + ReLU to each tap with iunet_bn_relu_fwd's bits before weighting it.
+// Resampling: resample_axis_f32 and the tap walk of resample.h.  The sources are the encoder's NHWC8c tensors (16-bit) or planar fp32
+// tensors, each with its own grid: the kernels take any source grid, so the ratios -2 .. +3 of the network and odd grids are one code
+// path.  The taps are rounded once to the MFMA input type.  An optional per-source relu(scale x + shift) prologue applies a BatchNorm +
+// ReLU to each tap with iunet_bn_relu_fwd's bits before weighting it.
 //
 // All reductions are fixed-order (per-workgroup rows / slabs, then ordered sums): no float atomics, two identical calls are bit-identical.
 #include <type_traits>
 
 #include "common.h"
 #include "gather_gemm.h"
+#include "resample.h"
 
 namespace {
 
@@ -44,69 +44,28 @@ struct SfSrcs {
   SfSrc s[SF_MAXS];
 };
 
-struct SfAx {
-  int i0, i1;
-  float l1;
-};
-
-// PyTorch's upsample_linear source index (align_corners=False, output size given)
-__device__ __forceinline__ SfAx sf_axis(int t, int nout, int nin) {
-  const float scale = (float)nin / (float)nout;
-  float src = scale * ((float)t + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  SfAx a;
-  a.i0 = min((int)src, nin - 1);
-  a.i1 = a.i0 + (a.i0 < nin - 1 ? 1 : 0);
-  a.l1 = src - (float)a.i0;
-  return a;
-}
-
-template <typename T>
-__device__ __forceinline__ float sf_pro(float v, const SfSrc& s, int c) {
-  v = fmaxf(fmaf(s.sc[c], v, s.sh[c]), 0.f);
-  if constexpr (!std::is_same<T, float>::value) v = to_f32<T>(from_f32<T>(v));
-  return v;
-}
-
 // The 8 channels c0 .. c0 + 7 of source s resampled at the T voxel whose per-axis taps are ad / ah / aw (fp32 sum, fixed tap order)
 template <typename T, int ND, bool ACT>
-__device__ __forceinline__ void sf_sample(const SfSrc& s, int n, int c0, const SfAx& ad, const SfAx& ah, const SfAx& aw, float out[8]) {
+__device__ __forceinline__ void sf_sample(const SfSrc& s, int n, int c0, const ResampleAx& ad, const ResampleAx& ah, const ResampleAx& aw,
+                                          float out[8]) {
+  constexpr int G = ChanGroup<T>::G;
 #pragma unroll
   for (int j = 0; j < 8; ++j) out[j] = 0.f;
   const long long vs = (long long)s.D * s.H * s.W;
+  const T* xs = (const T*)s.x + (long long)n * s.x_ss + (long long)c0 * vs;          // channel c0's plane / group in both layouts
+  resample_taps<ND>(ad, ah, aw, s.H, s.W, [&](long long vox, float wgt) {
 #pragma unroll
-  for (int td = 0; td < (ND == 3 ? 2 : 1); ++td) {
-    const int id = ND == 3 ? (td ? ad.i1 : ad.i0) : 0;
-    const float wd = ND == 3 ? (td ? ad.l1 : 1.f - ad.l1) : 1.f;
+    for (int g = 0; g < 8 / G; ++g) {              // one 16-byte group, or eight planes
+      float v[G];
+      group_load<T>(xs, g, vox, vs, v);
 #pragma unroll
-    for (int th = 0; th < 2; ++th) {
-      const int ih = th ? ah.i1 : ah.i0;
-      const float wh = wd * (th ? ah.l1 : 1.f - ah.l1);
-#pragma unroll
-      for (int tw = 0; tw < 2; ++tw) {
-        const int iw = tw ? aw.i1 : aw.i0;
-        const float wgt = wh * (tw ? aw.l1 : 1.f - aw.l1);
-        const long long vox = ((long long)id * s.H + ih) * s.W + iw;
-        if constexpr (std::is_same<T, float>::value) {
-          const float* xs = (const float*)s.x + (long long)n * s.x_ss + (long long)c0 * vs + vox;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            float v = xs[(long long)j * vs];
-            if constexpr (ACT) v = sf_pro<T>(v, s, c0 + j);
-            out[j] = fmaf(wgt, v, out[j]);
-          }
-        } else {
-          const V8T<T> b = *(const V8T<T>*)((const T*)s.x + (long long)n * s.x_ss + ((long long)(c0 >> 3) * vs + vox) * 8);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            float v = to_f32<T>(b[j]);
-            if constexpr (ACT) v = sf_pro<T>(v, s, c0 + j);
-            out[j] = fmaf(wgt, v, out[j]);
-          }
-        }
+      for (int j = 0; j < G; ++j) {
+        const int c = g * G + j;
+        if constexpr (ACT) v[j] = norm_z<T, true>(s.sc[c0 + c], v[j], s.sh[c0 + c]);
+        out[c] = fmaf(wgt, v[j], out[c]);
       }
     }
-  }
+  });
 }
 
 struct SfGemm {
@@ -148,10 +107,10 @@ __global__ __launch_bounds__(256) void sf_gemm_kernel(SfGemm p) {
     for (int t = 0; t < 4; ++t) acc[i][t] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int si = 0; si < p.src.n; ++si) {
     const SfSrc& s = p.src.s[si];
-    SfAx ad, ah, aw;
-    ad = ND == 3 ? sf_axis(gd, p.D, s.D) : SfAx{0, 0, 0.f};
-    ah = sf_axis(gh, p.H, s.H);
-    aw = sf_axis(gw, p.W, s.W);
+    ResampleAx ad, ah, aw;
+    ad = ND == 3 ? resample_axis_f32(gd, p.D, s.D) : ResampleAx{0, 0, 0.f};
+    ah = resample_axis_f32(gh, p.H, s.H);
+    aw = resample_axis_f32(gw, p.W, s.W);
     for (int c0 = 0; c0 < s.C; c0 += 32) {
       float v[8];
       if (gok) {
@@ -280,8 +239,8 @@ struct SfResample {
   template <typename T, bool ACT>
   __device__ __forceinline__ V8T<T> column(const Lane& l, int n, long long r, int D, int H, int W) const {
     const int w = (int)(r % W), h = (int)((r / W) % H), d = (int)(r / ((long long)W * H));
-    const SfAx ad = ND == 3 ? sf_axis(d, D, l.s->D) : SfAx{0, 0, 0.f};
-    const SfAx ah = sf_axis(h, H, l.s->H), aw = sf_axis(w, W, l.s->W);
+    const ResampleAx ad = ND == 3 ? resample_axis_f32(d, D, l.s->D) : ResampleAx{0, 0, 0.f};
+    const ResampleAx ah = resample_axis_f32(h, H, l.s->H), aw = resample_axis_f32(w, W, l.s->W);
     float v[8];
     sf_sample<T, ND, ACT>(*l.s, n, l.c0, ad, ah, aw, v);
     V8T<T> vb;
@@ -297,63 +256,6 @@ __global__ __launch_bounds__(256) void sf_wgrad_reduce_kernel(const float* __res
   float s = 0.f;
   for (int sp = 0; sp < splits; ++sp) s += slab[(long long)sp * total + i];
   G[i] = s;
-}
-
-// ---- adjoint of the resize, as a gather: dx[n][c][p] = sum over T voxels t of w(t, p) u[n][c][t], w the product of the per-axis weights
-// (an axis where i0 == i1 at the border gives that sample both its weights).  One thread per (voxel p, 8 channels); fp32 sum, one rounding.
-__device__ __forceinline__ void sf_adj_range(int p, int nin, int nout, int& lo, int& hi) {
-  // the T indices whose taps can reach p: src(t) in [p - 1, p + 1), widened by one index on each side (the clamp at 0 included)
-  const float inv = (float)nout / (float)nin;
-  lo = (int)floorf(((float)p - 0.5f) * inv - 0.5f) - 1;
-  hi = (int)ceilf(((float)p + 1.5f) * inv - 0.5f) + 1;
-  if (p <= 1) lo = 0;
-  lo = max(lo, 0);
-  hi = min(hi, nout - 1);
-}
-
-__device__ __forceinline__ float sf_adj_w(int t, int p, int nout, int nin) {
-  const SfAx a = sf_axis(t, nout, nin);
-  return (a.i0 == p ? 1.f - a.l1 : 0.f) + (a.i1 == p ? a.l1 : 0.f);
-}
-
-template <typename T, int ND>
-__global__ __launch_bounds__(256) void sf_adjoint_kernel(const T* __restrict__ u, long long u_ss, int Dt, int Ht, int Wt, T* __restrict__ dx,
-                                                         long long dx_ss, int Ds, int Hs, int Ws, int C, int N) {
-  const long long vs = (long long)Ds * Hs * Ws, vT = (long long)Dt * Ht * Wt;
-  const long long total = (long long)N * (C / 8) * vs;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const long long r = i % vs;
-  const int pl = (int)((i / vs) % (C / 8)), n = (int)(i / (vs * (C / 8)));
-  const int pw = (int)(r % Ws), ph = (int)((r / Ws) % Hs), pd = (int)(r / ((long long)Ws * Hs));
-  int dlo = 0, dhi = 0, hlo, hhi, wlo, whi;
-  if (ND == 3) sf_adj_range(pd, Ds, Dt, dlo, dhi);
-  sf_adj_range(ph, Hs, Ht, hlo, hhi);
-  sf_adj_range(pw, Ws, Wt, wlo, whi);
-  float acc[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-  const T* us = u + (long long)n * u_ss + (long long)pl * vT * 8;
-  for (int td = dlo; td <= dhi; ++td) {
-    const float wd = ND == 3 ? sf_adj_w(td, pd, Dt, Ds) : 1.f;
-    if (wd == 0.f) continue;
-    for (int th = hlo; th <= hhi; ++th) {
-      const float wh = sf_adj_w(th, ph, Ht, Hs);
-      if (wh == 0.f) continue;
-      for (int tw = wlo; tw <= whi; ++tw) {
-        const float ww = sf_adj_w(tw, pw, Wt, Ws);
-        if (ww == 0.f) continue;
-        const float wgt = wd * wh * ww;
-        const V8T<T> v = *(const V8T<T>*)(us + (((long long)td * Ht + th) * Wt + tw) * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = fmaf(wgt, to_f32<T>(v[j]), acc[j]);
-      }
-    }
-  }
-  V8T<T> o;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = from_f32<T>(acc[j]);
-  *(V8T<T>*)(dx + (long long)n * dx_ss + ((long long)pl * vs + r) * 8) = o;
 }
 
 // ---- the small fp32 operator kernels (C^2 sum ch MACs; one thread per output, sums in ascending index order)
@@ -599,11 +501,12 @@ int iunet_sf_adjoint(int dtype, int nd, const void* u, long long u_ss, int Dt, i
   IUNET_REQUIRE(u && dx, "sf_adjoint: null pointer");
   const long long total = (long long)N * (C / 8) * Ds * Hs * Ws;
   const dim3 grid((unsigned)((total + 255) / 256));
-#define SFA(TT, NDV) hipLaunchKernelGGL((sf_adjoint_kernel<TT, NDV>), grid, dim3(256), 0, (hipStream_t)stream, (const TT*)u, u_ss, Dt, Ht, Wt, \
-                                        (TT*)dx, dx_ss, Ds, Hs, Ws, C, N)
-  if (dtype == 0) { if (nd == 3) SFA(f16, 3); else SFA(f16, 2); }
-  else { if (nd == 3) SFA(bf16, 3); else SFA(bf16, 2); }
-#undef SFA
+  // resample.h's gather in its thread-per-voxel form only: the wide form sums in another order
+  iunet_dispatch(dtype, nd, false, [&](auto t, auto ndc, auto) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((resample_adjoint_kernel<T, ndc.value, resample_axis_f32>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)u, u_ss, Dt,
+                       Ht, Wt, (T*)dx, dx_ss, Ds, Hs, Ws, C, N, 0);
+  });
   IUNET_CHECK_HIP(hipGetLastError());
   return IUNET_OK;
 }

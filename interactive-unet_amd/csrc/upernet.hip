@@ -1,71 +1,18 @@
 // UPerNet decoder (unet.param_shapes(..., architecture='UPerNet')): the part of the graph that moves data between grids.  Every conv of
 // the decoder runs on deeplab.hip's gathered GEMMs; this file adds
 //   pn_resize_kernel        dst slot = [base +] R(act(src)): linear resampling (align_corners=False) from any grid to any grid
-//   pn_adjoint_kernel       dx = [dx +] R^T(u), as a gather over the source grid (pn_adjoint_wide_kernel: a workgroup per source voxel)
+//   iunet_pn_resize_adjoint dx = [dx +] R^T(u): resample.h's gather over the source grid (its wide form: a workgroup per source voxel)
 //   pn_pool_kernel          the four adaptive average pools (1, 2, 3, 6 bins per axis) of X^B in one launch
 //   pn_pool_bwd_kernel      dX^B = the identity slot's gradient + sum_s pool_s^T(dA_s), one gather per voxel
 //   pn_bias_relu_bwd_*      backward of relu(y + bias) of the norm-free 1-bin branch
 // Tensors are NHWC8c (dtype 0 f16 / 1 bf16) or planar fp32 [N][C][vox] (dtype 2) with sample strides in elements, so a channel slot of a
 // wider tensor is a pointer offset (c vox elements in both layouts) and the wider tensor's sample stride.
 //
-// Source index.  PyTorch's align_corners=False rule src = max(0, (nin / nout) (t + 1/2) - 1/2), i0 = floor(src), i1 = min(i0 + 1, nin - 1),
-// l1 = src - i0 (SfResample in segformer.hip states the same rule in fp32).  Here the rule is evaluated on the integers
-// num = nin (2 t + 1) - nout, den = 2 nout: i0 = num / den, l1 = (num mod den) / den with ONE rounding, so the weights carry no
-// cancellation error of an fp32 src (which grows with the index) and the forward and its adjoint use bit-identical weights.
-// Every sum is fp32 in a fixed order with one rounding to the stored type: no float atomics, a repeated launch is bit-equal.
+// Source index: resample_axis_exact of resample.h (align_corners=False on the integers, one rounding; the forward and its adjoint share it).
 #include "common.h"
+#include "resample.h"
 
 namespace {
-
-struct PnAx {
-  int i0, i1;
-  float l1;
-};
-
-__device__ __forceinline__ PnAx pn_axis(int t, int nout, int nin) {
-  const long long den = 2ll * nout;
-  long long num = (long long)nin * (2 * t + 1) - nout;
-  num = num < 0 ? 0 : num;
-  PnAx a;
-  a.i0 = min((int)(num / den), nin - 1);
-  const long long rem = num - a.i0 * den;
-  a.l1 = (float)rem / (float)den;
-  a.i1 = (rem != 0 && a.i0 < nin - 1) ? a.i0 + 1 : a.i0;      // (a zero weight reads its own voxel again: the identity is a copy)
-  return a;
-}
-
-template <typename T> struct PnLay { static constexpr int G = 8; };       // channels per thread: one 16-byte group
-template <> struct PnLay<float> { static constexpr int G = 1; };          // planar fp32: one channel
-
-// the G channels of group g at voxel v of a tensor with vox voxels per plane (s: the sample's base)
-template <typename T>
-__device__ __forceinline__ void pn_load(const T* s, int g, long long v, long long vox, float (&out)[PnLay<T>::G]) {
-  if constexpr (std::is_same<T, float>::value) {
-    out[0] = s[(long long)g * vox + v];
-  } else {
-    const V8T<T> b = *(const V8T<T>*)(s + ((long long)g * vox + v) * 8);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) out[j] = to_f32<T>(b[j]);
-  }
-}
-template <typename T>
-__device__ __forceinline__ void pn_store(T* s, int g, long long v, long long vox, const float (&val)[PnLay<T>::G]) {
-  if constexpr (std::is_same<T, float>::value) {
-    s[(long long)g * vox + v] = val[0];
-  } else {
-    V8T<T> o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = from_f32<T>(val[j]);
-    *(V8T<T>*)(s + ((long long)g * vox + v) * 8) = o;
-  }
-}
-// relu(scale x + shift) as iunet_bn_relu_fwd stores it (rounded to T; fp32: the fp32 value)
-template <typename T>
-__device__ __forceinline__ float pn_act(float v, const float* sc, const float* sh, int c) {
-  v = fmaxf(fmaf(sc[c], v, sh[c]), 0.f);
-  if constexpr (!std::is_same<T, float>::value) v = to_f32<T>(from_f32<T>(v));
-  return v;
-}
 
 struct PnResize {
   const void* src; long long src_ss; int Ds, Hs, Ws;
@@ -80,7 +27,7 @@ struct PnResize {
 // contiguous across the wave; the source rows a wave reads are contiguous runs too.
 template <typename T, int ND, bool ACT>
 __global__ __launch_bounds__(256) void pn_resize_kernel(PnResize p) {
-  constexpr int G = PnLay<T>::G;
+  constexpr int G = ChanGroup<T>::G;
   const long long vT = (long long)p.Dt * p.Ht * p.Wt, vS = (long long)p.Ds * p.Hs * p.Ws;
   const int groups = p.C / G;
   const long long total = (long long)p.N * groups * vT;
@@ -89,165 +36,35 @@ __global__ __launch_bounds__(256) void pn_resize_kernel(PnResize p) {
   const long long r = i % vT;
   const int g = (int)((i / vT) % groups), n = (int)(i / (vT * groups));
   const int tw = (int)(r % p.Wt), th = (int)((r / p.Wt) % p.Ht), td = (int)(r / ((long long)p.Wt * p.Ht));
-  PnAx ad = {0, 0, 0.f};
-  if (ND == 3) ad = pn_axis(td, p.Dt, p.Ds);
-  const PnAx ah = pn_axis(th, p.Ht, p.Hs), aw = pn_axis(tw, p.Wt, p.Ws);
+  ResampleAx ad = {0, 0, 0.f};
+  if (ND == 3) ad = resample_axis_exact(td, p.Dt, p.Ds);
+  const ResampleAx ah = resample_axis_exact(th, p.Ht, p.Hs), aw = resample_axis_exact(tw, p.Wt, p.Ws);
   const T* s = (const T*)p.src + (long long)n * p.src_ss;
   float acc[G];
 #pragma unroll
   for (int j = 0; j < G; ++j) acc[j] = 0.f;
-#pragma unroll
-  for (int kd = 0; kd < (ND == 3 ? 2 : 1); ++kd) {
-    const int id = ND == 3 ? (kd ? ad.i1 : ad.i0) : 0;
-    const float wd = ND == 3 ? (kd ? ad.l1 : 1.f - ad.l1) : 1.f;
-#pragma unroll
-    for (int kh = 0; kh < 2; ++kh) {
-      const int ih = kh ? ah.i1 : ah.i0;
-      const float wh = wd * (kh ? ah.l1 : 1.f - ah.l1);
-#pragma unroll
-      for (int kw = 0; kw < 2; ++kw) {
-        const int iw = kw ? aw.i1 : aw.i0;
-        const float wgt = wh * (kw ? aw.l1 : 1.f - aw.l1);
-        float v[G];
-        pn_load<T>(s, g, ((long long)id * p.Hs + ih) * p.Ws + iw, vS, v);
-#pragma unroll
-        for (int j = 0; j < G; ++j) {
-          if constexpr (ACT) v[j] = pn_act<T>(v[j], p.sc, p.sh, g * G + j);
-          acc[j] = fmaf(wgt, v[j], acc[j]);
-        }
-      }
-    }
-  }
-  if (p.base != nullptr) {
-    float b[G];
-    pn_load<T>((const T*)p.base + (long long)n * p.base_ss, g, r, vT, b);
+  resample_taps<ND>(ad, ah, aw, p.Hs, p.Ws, [&](long long vox, float wgt) {
+    float v[G];
+    group_load<T>(s, g, vox, vS, v);
 #pragma unroll
     for (int j = 0; j < G; ++j) {
-      if (p.bsc != nullptr) b[j] = pn_act<T>(b[j], p.bsc, p.bsh, g * G + j);
+      if constexpr (ACT) v[j] = norm_z<T, true>(p.sc[g * G + j], v[j], p.sh[g * G + j]);
+      acc[j] = fmaf(wgt, v[j], acc[j]);
+    }
+  });
+  if (p.base != nullptr) {
+    float b[G];
+    group_load<T>((const T*)p.base + (long long)n * p.base_ss, g, r, vT, b);
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+      if (p.bsc != nullptr) b[j] = norm_z<T, true>(p.bsc[g * G + j], b[j], p.bsh[g * G + j]);
       acc[j] += b[j];
     }
   }
-  pn_store<T>((T*)p.dst + (long long)n * p.dst_ss, g, r, vT, acc);
+  group_store<T>((T*)p.dst + (long long)n * p.dst_ss, g, r, vT, acc);
 }
 
-// ---- the adjoint as a gather: dx[n][c][q] = [dx +] sum over target voxels t of w(t, q) u[n][c][t], w the product of the per-axis weights
-// (a border sample whose two taps land on one voxel gives it both).  One thread per (source voxel q, 8 channels).
-__device__ __forceinline__ void pn_adj_range(int q, int nin, int nout, int& lo, int& hi) {
-  // the target indices whose taps can reach q: src(t) in (q - 1, q + 1), widened by one index on each side (the clamp at 0 included)
-  const float inv = (float)nout / (float)nin;
-  lo = (int)floorf(((float)q - 0.5f) * inv - 0.5f) - 1;
-  hi = (int)ceilf(((float)q + 1.5f) * inv - 0.5f) + 1;
-  if (q <= 1) lo = 0;
-  lo = max(lo, 0);
-  hi = min(hi, nout - 1);
-}
-
-__device__ __forceinline__ float pn_adj_w(int t, int q, int nout, int nin) {
-  const PnAx a = pn_axis(t, nout, nin);
-  if (a.i0 == a.i1) return a.i0 == q ? (1.f - a.l1) + a.l1 : 0.f;
-  return (a.i0 == q ? 1.f - a.l1 : 0.f) + (a.i1 == q ? a.l1 : 0.f);
-}
-
-template <typename T, int ND>
-__global__ __launch_bounds__(256) void pn_adjoint_kernel(const T* __restrict__ u, long long u_ss, int Dt, int Ht, int Wt, T* dx, long long dx_ss,
-                                                         int Ds, int Hs, int Ws, int C, int N, int accumulate) {
-  const long long vs = (long long)Ds * Hs * Ws, vT = (long long)Dt * Ht * Wt;
-  const long long total = (long long)N * (C / 8) * vs;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const long long r = i % vs;
-  const int pl = (int)((i / vs) % (C / 8)), n = (int)(i / (vs * (C / 8)));
-  const int qw = (int)(r % Ws), qh = (int)((r / Ws) % Hs), qd = (int)(r / ((long long)Ws * Hs));
-  int dlo = 0, dhi = 0, hlo, hhi, wlo, whi;
-  if (ND == 3) pn_adj_range(qd, Ds, Dt, dlo, dhi);
-  pn_adj_range(qh, Hs, Ht, hlo, hhi);
-  pn_adj_range(qw, Ws, Wt, wlo, whi);
-  float acc[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-  const T* us = u + (long long)n * u_ss + (long long)pl * vT * 8;
-  for (int td = dlo; td <= dhi; ++td) {
-    const float wd = ND == 3 ? pn_adj_w(td, qd, Dt, Ds) : 1.f;
-    if (wd == 0.f) continue;
-    for (int th = hlo; th <= hhi; ++th) {
-      const float wh = pn_adj_w(th, qh, Ht, Hs);
-      if (wh == 0.f) continue;
-      for (int tw = wlo; tw <= whi; ++tw) {
-        const float ww = pn_adj_w(tw, qw, Wt, Ws);
-        if (ww == 0.f) continue;
-        const float wgt = wd * wh * ww;
-        const V8T<T> v = *(const V8T<T>*)(us + (((long long)td * Ht + th) * Wt + tw) * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = fmaf(wgt, to_f32<T>(v[j]), acc[j]);
-      }
-    }
-  }
-  T* o = dx + (long long)n * dx_ss + ((long long)pl * vs + r) * 8;
-  if (accumulate) {
-    const V8T<T> old = *(const V8T<T>*)o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] += to_f32<T>(old[j]);
-  }
-  V8T<T> res;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) res[j] = from_f32<T>(acc[j]);
-  *(V8T<T>*)o = res;
-}
-
-// The same adjoint where few source voxels each gather from many target voxels (the pyramid branches: a 1 .. 6-bin grid under G_B): one
-// workgroup per (source voxel, 8 channels), its 256 threads walk the candidate range, then a fixed-order reduction (xor tree in the wave,
-// the four waves in order).  iunet_pn_resize_adjoint picks the kernel from the grids alone.
-template <typename T, int ND>
-__global__ __launch_bounds__(256) void pn_adjoint_wide_kernel(const T* __restrict__ u, long long u_ss, int Dt, int Ht, int Wt, T* dx, long long dx_ss,
-                                                              int Ds, int Hs, int Ws, int C, int N, int accumulate) {
-  const long long vs = (long long)Ds * Hs * Ws, vT = (long long)Dt * Ht * Wt;
-  const long long i = blockIdx.x;
-  const long long r = i % vs;
-  const int pl = (int)((i / vs) % (C / 8)), n = (int)(i / (vs * (C / 8)));
-  const int qw = (int)(r % Ws), qh = (int)((r / Ws) % Hs), qd = (int)(r / ((long long)Ws * Hs));
-  int dlo = 0, dhi = 0, hlo, hhi, wlo, whi;
-  if (ND == 3) pn_adj_range(qd, Ds, Dt, dlo, dhi);
-  pn_adj_range(qh, Hs, Ht, hlo, hhi);
-  pn_adj_range(qw, Ws, Wt, wlo, whi);
-  const int ew = whi - wlo + 1, eh = hhi - hlo + 1, cnt = (dhi - dlo + 1) * eh * ew;
-  float acc[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-  const T* us = u + (long long)n * u_ss + (long long)pl * vT * 8;
-  for (int e = threadIdx.x; e < cnt; e += 256) {
-    const int tw = wlo + e % ew, th = hlo + (e / ew) % eh, td = dlo + e / (ew * eh);
-    const float wgt = (ND == 3 ? pn_adj_w(td, qd, Dt, Ds) : 1.f) * pn_adj_w(th, qh, Ht, Hs) * pn_adj_w(tw, qw, Wt, Ws);
-    if (wgt == 0.f) continue;
-    const V8T<T> v = *(const V8T<T>*)(us + (((long long)td * Ht + th) * Wt + tw) * 8);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = fmaf(wgt, to_f32<T>(v[j]), acc[j]);
-  }
-  __shared__ float red[4][8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float s = wave_sum(acc[j]);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][j] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  T* o = dx + (long long)n * dx_ss + ((long long)pl * vs + r) * 8;
-  V8T<T> old;
-  if (accumulate) old = *(const V8T<T>*)o;
-  V8T<T> res;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    float s = ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j];
-    if (accumulate) s += to_f32<T>(old[j]);
-    res[j] = from_f32<T>(s);
-  }
-  *(V8T<T>*)o = res;
-}
-
-// candidate target indices per source index on one axis (pn_adj_range's extent, clamped to the axis)
-inline long long pn_adj_extent(int nin, int nout) {
-  const long long e = (2ll * nout + nin - 1) / nin + 3;
-  return e < nout ? e : nout;
-}
+// ---- the adjoint R^T: resample_adjoint_kernel / resample_adjoint_wide_kernel of resample.h under resample_axis_exact
 constexpr long long PN_WIDE_FROM = 512;        // candidates per source voxel from which the workgroup-per-voxel kernel runs
 
 // ---- adaptive average pooling, PyTorch's windows: bin i of s over n voxels = [floor(i n / s), ceil((i + 1) n / s))
@@ -266,7 +83,7 @@ struct PnPool {
 // mean is sum / count
 template <typename T, int ND>
 __global__ __launch_bounds__(64) void pn_pool_kernel(PnPool p) {
-  constexpr int G = PnLay<T>::G;
+  constexpr int G = ChanGroup<T>::G;
   constexpr int NB = ND == 3 ? 1 + 8 + 27 + 216 : 1 + 4 + 9 + 36;
   const int groups = p.C / G;
   const long long item = blockIdx.x;
@@ -291,13 +108,13 @@ __global__ __launch_bounds__(64) void pn_pool_kernel(PnPool p) {
   for (int e = threadIdx.x; e < cnt; e += 64) {
     const int ew = e % nw, eh = (e / nw) % nh, ed = e / (nw * nh);
     float v[G];
-    pn_load<T>(xs, g, ((long long)(d0 + ed) * p.H + (h0 + eh)) * p.W + (w0 + ew), vox, v);
+    group_load<T>(xs, g, ((long long)(d0 + ed) * p.H + (h0 + eh)) * p.W + (w0 + ew), vox, v);
 #pragma unroll
     for (int j = 0; j < G; ++j) acc[j] += v[j];
   }
 #pragma unroll
   for (int j = 0; j < G; ++j) acc[j] = wave_sum(acc[j]) / (float)cnt;
-  if (threadIdx.x == 0) pn_store<T>((T*)p.out[k] + (long long)n * p.out_ss[k], g, b, ND == 3 ? s * s * s : s * s, acc);
+  if (threadIdx.x == 0) group_store<T>((T*)p.out[k] + (long long)n * p.out_ss[k], g, b, ND == 3 ? s * s * s : s * s, acc);
 }
 
 struct PnPoolBwd {
@@ -326,7 +143,7 @@ __global__ __launch_bounds__(256) void pn_pool_bwd_kernel(PnPoolBwd p) {
   float acc[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-  if (p.du != nullptr) pn_load<T>((const T*)p.du + (long long)n * p.du_ss, pl, r, vox, acc);
+  if (p.du != nullptr) group_load<T>((const T*)p.du + (long long)n * p.du_ss, pl, r, vox, acc);
   for (int k = 0; k < PN_NS; ++k) {
     const int s = pn_size(k);
     int dlo = 0, dhi = 0, hlo, hhi, wlo, whi;
@@ -342,14 +159,14 @@ __global__ __launch_bounds__(256) void pn_pool_bwd_kernel(PnPoolBwd p) {
         for (int bw = wlo; bw <= whi; ++bw) {
           const float inv = 1.f / (float)(ch * (pn_bin_hi(bw, p.W, s) - pn_bin_lo(bw, p.W, s)));
           float v[8];
-          pn_load<T>(a, pl, ((long long)bd * s + bh) * s + bw, nb, v);
+          group_load<T>(a, pl, ((long long)bd * s + bh) * s + bw, nb, v);
 #pragma unroll
           for (int j = 0; j < 8; ++j) acc[j] = fmaf(inv, v[j], acc[j]);
         }
       }
     }
   }
-  pn_store<T>((T*)p.dx + (long long)n * p.dx_ss, pl, r, vox, acc);
+  group_store<T>((T*)p.dx + (long long)n * p.dx_ss, pl, r, vox, acc);
 }
 
 // ---- backward of q = relu(y + bias) (the 1-bin branch has no norm): dy = dz where the stored q is positive; dbias[c] = sum dy in (n, voxel) order
@@ -363,11 +180,11 @@ __global__ __launch_bounds__(256) void pn_bias_relu_bwd_kernel(const T* __restri
   const long long r = i % vox;
   const int pl = (int)((i / vox) % (C / 8)), n = (int)(i / (vox * (C / 8)));
   float g[8], v[8];
-  pn_load<T>(dz + (long long)n * dz_ss, pl, r, vox, g);
-  pn_load<T>(y + (long long)n * y_ss, pl, r, vox, v);
+  group_load<T>(dz + (long long)n * dz_ss, pl, r, vox, g);
+  group_load<T>(y + (long long)n * y_ss, pl, r, vox, v);
 #pragma unroll
   for (int j = 0; j < 8; ++j) g[j] = norm_masked(norm_z<T, true>(1.f, v[j], bias[pl * 8 + j]), g[j]);
-  pn_store<T>(dy + (long long)n * dy_ss, pl, r, vox, g);
+  group_store<T>(dy + (long long)n * dy_ss, pl, r, vox, g);
 }
 
 template <typename T>
@@ -435,11 +252,11 @@ int iunet_pn_resize_adjoint(int dtype, int nd, const void* u, long long u_ss, in
   iunet_dispatch(dtype, nd, wide, [&](auto t, auto ndc, auto w) {
     using T = decltype(t);
     if constexpr (w.value)
-      hipLaunchKernelGGL((pn_adjoint_wide_kernel<T, ndc.value>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)u, u_ss, Dt, Ht, Wt, (T*)dx,
-                         dx_ss, Ds, Hs, Ws, C, N, accumulate);
+      hipLaunchKernelGGL((resample_adjoint_wide_kernel<T, ndc.value, resample_axis_exact>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)u,
+                         u_ss, Dt, Ht, Wt, (T*)dx, dx_ss, Ds, Hs, Ws, C, N, accumulate);
     else
-      hipLaunchKernelGGL((pn_adjoint_kernel<T, ndc.value>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)u, u_ss, Dt, Ht, Wt, (T*)dx, dx_ss,
-                         Ds, Hs, Ws, C, N, accumulate);
+      hipLaunchKernelGGL((resample_adjoint_kernel<T, ndc.value, resample_axis_exact>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)u, u_ss,
+                         Dt, Ht, Wt, (T*)dx, dx_ss, Ds, Hs, Ws, C, N, accumulate);
   });
   IUNET_CHECK_HIP(hipGetLastError());
   return IUNET_OK;

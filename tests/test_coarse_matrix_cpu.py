@@ -49,7 +49,7 @@ def test_loss_table_branches():
         assert {c[7] for c in cases} == set(M.metrics_ref.KINDS)
         for r in rows:
             assert {(c[5], c[6]) for c in cases if c[:5] == r} == set(M.CROSS)                                  # every row meets the whole crossing
-    # the scale factors 1 and 64, dl_up_check's bounds, fit in 2-D alone (64^3 voxels are no quick test); dl_lerp is the same code per axis
+    # the scale factors 1 and 64, dl_up_check's bounds, fit in 2-D alone (64^3 voxels are no quick test); resample_axis_corners is the same code per axis
     assert {1, 64} <= {r[2] for r in M.LOSS_TABLE if r[0] == 2}
     assert all(c[7] == 'dice_ce' for c in M.LOSS_CASES if c[:3] in M.TWO_ROW) and all(rows_of(*k) == 2 for k in M.TWO_ROW)
     assert len(M.LOSS_CASES) == 4 * len(M.LOSS_TABLE)
@@ -98,7 +98,7 @@ def test_dyadic_pair_has_exact_fp32_weights():
 
 
 def test_source_coordinate_error_is_small():
-    """dl_lerp in numpy float32: f stays in [0, 1] and the weights are within src_delta (at most 1e-6 here) of the exact ones, for every pair."""
+    """resample_axis_corners in numpy float32: f stays in [0, 1] and the weights are within src_delta (at most 1e-6 here) of the exact ones, for every pair."""
     for Ec, s in axis_pairs():
         i0, f = M.lerp_weights_f32(Ec, Ec * s)
         assert f.min() >= 0 and f.max() <= 1 and 0 <= i0.min() and i0.max() <= Ec - 1

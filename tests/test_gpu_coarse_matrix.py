@@ -111,7 +111,7 @@ def adjoint2d(b, Hc, Wc):
 
 
 def src_delta(Ec, Ef):
-    """The largest difference between dl_lerp's fp32 source coordinate sc * o, sc = fp32((Ec - 1) / (Ef - 1)), and the exact one."""
+    """The largest difference between resample_axis_corners's fp32 source coordinate sc * o, sc = fp32((Ec - 1) / (Ef - 1)), and the exact one."""
     if Ef <= 1 or Ec <= 1:
         return 0.0
     sc = np.float32(Ec - 1) / np.float32(Ef - 1)
@@ -121,7 +121,7 @@ def src_delta(Ec, Ef):
 
 
 def lerp_weights_f32(Ec, Ef):
-    """dl_lerp in numpy float32: (i0, f) per fine index."""
+    """resample_axis_corners in numpy float32: (i0, f) per fine index."""
     sc = np.float32(Ec - 1) / np.float32(Ef - 1) if Ef > 1 else np.float32(0)
     src = (sc * np.arange(Ef).astype(np.float32)).astype(np.float32)
     i0 = np.minimum(src.astype(np.int32), Ec - 1)
@@ -162,7 +162,7 @@ def adjoint_tolerance(g, Hc, Wc):
 
 
 def interp_matrix_f32(Ec, Ef):
-    """The matrix of the weights dl_lerp computes in fp32 (lerp_weights_f32), as float64 values."""
+    """The matrix of the weights resample_axis_corners computes in fp32 (lerp_weights_f32), as float64 values."""
     i0, f = lerp_weights_f32(Ec, Ef)
     A = np.zeros((Ef, Ec))
     for o in range(Ef):

@@ -215,6 +215,61 @@ def test_adjoint(T, case):
     assert abs(a.sum().item() - b.sum().item()) <= 2 * U[T] * (a.abs().sum().item() + b.abs().sum().item())
 
 
+# ---------------------------------------------------------------------------------------------- (b') the two users of csrc/resample.h
+# Segformer evaluates the source index in fp32 (resample_axis_f32), UPerNet on the integers (resample_axis_exact).  Between grids whose
+# ratio is a power of two both are exact: the same i0 and l1, and where the remainder is 0 they differ only in an i1 whose weight is 0.
+# The tap walk, the adjoint's gather order and its zero-weight skips are shared code, so the two architectures' entry points must return
+# the same BYTES there.  (target grid, source grids): ratios 1/2, 1, 2 and 4.
+DYADIC = [(2, (6, 10), ssp) for ssp in ((3, 5), (6, 10), (12, 20), (24, 40))] + [(3, (2, 4, 6), ssp) for ssp in ((1, 2, 3), (2, 4, 6), (4, 8, 12))]
+DYADIC_IDS = [f'{c[2]}to{c[1]}'.replace(' ', '') for c in DYADIC]
+
+
+def _adj_extent(nin, nout):
+    """pn_adj_extent of csrc/resample.h: the candidate target indices per source index on one axis."""
+    return min((2 * nout + nin - 1) // nin + 3, nout)
+
+
+@pytest.mark.parametrize('T', DTYPES[:2], ids=['fp16', 'bf16'])
+@pytest.mark.parametrize('case', range(len(DYADIC)), ids=DYADIC_IDS)
+def test_dyadic_adjoint_is_segformers_bit_for_bit(T, case):
+    from interactive_unet import _native as nv
+    nd, tsp, ssp = DYADIC[case]
+    N, C = 2, 16
+    cand = int(np.prod([_adj_extent(s, t) for s, t in zip(ssp, tsp)]))
+    assert cand < 512, 'iunet_pn_resize_adjoint must take its thread-per-voxel form, the only one iunet_sf_adjoint has'
+    u = _rnd(T)(torch.randn((N, C) + tsp, generator=torch.Generator().manual_seed(50 + case), dtype=torch.float64))
+    us = Slot(N, C, tsp, T, payload=u)
+    pn, sf = Slot(N, C, ssp, T), Slot(N, C, ssp, T)
+    nv.call('iunet_pn_resize_adjoint', CODE[T], nd, us.ptr(), us.ss, *_dims(tsp), pn.ptr(), pn.ss, *_dims(ssp), C, N, 0, nv.stream())
+    nv.call('iunet_sf_adjoint', CODE[T], nd, us.ptr(), us.ss, *_dims(tsp), sf.ptr(), sf.ss, *_dims(ssp), C, N, nv.stream())
+    torch.cuda.synchronize()
+    assert bool(pn.read()[0].abs().sum() > 0) and torch.equal(pn.buf.view(torch.int16), sf.buf.view(torch.int16))
+
+
+@pytest.mark.parametrize('T', DTYPES, ids=['fp16', 'bf16', 'fp32'])
+@pytest.mark.parametrize('case', range(len(DYADIC)), ids=DYADIC_IDS)
+def test_dyadic_resize_is_segformers_gather_bit_for_bit(T, case):
+    """iunet_sf_gemm of one source against the identity operator with a zero bias stores its gathered tile: the matrix product with the
+    identity is exact, and the second rounding to T changes nothing (the fp32 kernel stores the tile unrounded)."""
+    from interactive_unet import _native as nv
+    nd, tsp, ssp = DYADIC[case]
+    N, C = 2, 32
+    g = torch.Generator().manual_seed(70 + case)
+    x = _rnd(T)(torch.randn((N, C) + ssp, generator=g, dtype=torch.float64))
+    act = [(0.5 + torch.rand(C, generator=g)).cuda(), (0.3 * torch.randn(C, generator=g)).cuda()]
+    xs = Slot(N, C, ssp, T, payload=x)
+    eye, zero = torch.eye(C, dtype=T, device='cuda'), torch.zeros(C, device='cuda')
+    tabs = (nv.ptr_array([xs.ptr().value]), nv.ll_array([xs.ss]), nv.int_array([C]), nv.int_array(list(_dims(ssp))))
+    for prologue in (None, act):
+        pn, sf = Slot(N, C, tsp, T), Slot(N, C, tsp, T)
+        _resize_call(nv, T, nd, xs.ptr(), xs.ss, ssp, prologue, None, pn.ptr(), pn.ss, tsp, C, N)
+        sc, sh = (None, None) if prologue is None else (nv.ptr_array([act[0]]), nv.ptr_array([act[1]]))
+        nv.call('iunet_sf_gemm', CODE[T], nd, 1, *tabs, sc, sh, _P(eye), _P(zero), sf.ptr(), sf.ss, None, 0, N, *_dims(tsp), C, nv.stream())
+        torch.cuda.synchronize()
+        bits = torch.int32 if T == torch.float32 else torch.int16
+        assert bool(pn.read()[0].abs().sum() > 0) and torch.equal(pn.buf.view(bits), sf.buf.view(bits)), f'prologue {prologue is not None}'
+
+
 # ---------------------------------------------------------------------------------------------- (c) adaptive average pooling
 POOL = [(2, (6, 10)), (2, (5, 3)), (2, (2, 3)), (2, (1, 1)), (3, (2, 4, 3))]
 

@@ -89,8 +89,14 @@ ONE_DEFINITION = ['float bn_fold_scale(', 'float bn_fold_mul(', 'float bn_fold_b
                   # the resident-volume rules (volume_rules.h): plane point, inside test, samplers, class, streaming select, host helpers
                   'double plane_point(', 'double slab_point(', 'bool coord_inside(', 'double coord_nearest(', 'int volume_mirror(',
                   'unsigned char volume_sample_linear(', 'TopByte volume_top_byte(', 'void volume_select_kernel(', 'void volume_select_launch(',
-                  'long long volume_align16(', 'bool volume_ok(', 'unsigned int volume_grid(', 'define VOLUME_REQUIRE_DIMS(']
-HOMES = ('common.h', 'head_out.h', 'volume_rules.h')
+                  'long long volume_align16(', 'bool volume_ok(', 'unsigned int volume_grid(', 'define VOLUME_REQUIRE_DIMS(',
+                  # the decoders' grid-moving rules (resample.h): channel groups, the tap record and its three index rules, the tap walk, the adjoint
+                  'struct ChanGroup {', 'void group_load(', 'void group_store(', 'struct ResampleAx {', 'ResampleAx resample_axis_f32(',
+                  'ResampleAx resample_axis_exact(', 'ResampleAx resample_axis_corners(', 'void resample_taps(', 'void resample_adj_range(',
+                  'long long pn_adj_extent(', 'float resample_adj_w(', 'void resample_adjoint_kernel(', 'void resample_adjoint_wide_kernel(']
+HOMES = ('common.h', 'head_out.h', 'volume_rules.h', 'resample.h')
+RETIRED_RESAMPLE = (r'\b(sf_axis|pn_axis|dl_lerp|SfAx|PnAx|pn_load|pn_store|pn_act|PnLay|ma_ld|ma_st|ma_act|MaLay|sf_pro|sf_adj_range|pn_adj_range|'
+                    r'sf_adj_w|pn_adj_w|sf_adjoint_kernel|pn_adjoint_kernel)\b')
 
 
 def test_each_shared_contract_is_defined_once():
@@ -103,6 +109,7 @@ def test_each_shared_contract_is_defined_once():
     for p, t in text.items():
         assert not re.search(r'\b(slab_mirror|mirror_idx|cc_align16|ed_align16|filter_kernel|select_kernel)\b', t), \
             f'{os.path.basename(p)}: a retired copy of a resident-volume rule is back'
+        assert not re.search(RETIRED_RESAMPLE, t), f'{os.path.basename(p)}: a retired copy of a resampling or channel-group rule is back'
         if os.path.basename(p) in HOMES:
             continue
         assert not re.search(r'/\s*sqrtf\(\s*(\w+\.)?var\b', t), f'{os.path.basename(p)}: a BatchNorm scale written out by hand'

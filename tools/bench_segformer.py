@@ -3,7 +3,8 @@
 2-D net) in each model's default prediction form (Segformer fp32, U-Net split precision) and in fp16.  Both training steps are sequenced
 from Python (the U-Net's C handle off), so the comparison is of the launches, not of the sequencing.  It also prints the shape bounds of
 the new kernels (bytes at 6.3 TB/s, dense FLOPs at 2.5 PFLOP/s for 16-bit): `python tools/bench_segformer.py bounds` needs no GPU.
-    python tools/bench_segformer.py [block | bounds]"""
+`python tools/bench_segformer.py adjoint` times iunet_sf_adjoint alone, per level, at the grids of its bound.
+    python tools/bench_segformer.py [block | bounds | adjoint]"""
 import math, os, sys, warnings
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'interactive-unet_amd'))
@@ -34,6 +35,38 @@ def print_bounds():
         print(f'bounds at {dim}-D {N} x {sp}, C = 256, L = 4 (16-bit):')
         for k, (b, f) in bounds(dim, N, sp).items():
             print(f'  {k:45s} {b / 1e6:10.1f} MB {b / HBM * 1e6:8.1f} us   {f / 1e9:8.1f} GFLOP {f / MFMA16 * 1e6:8.1f} us')
+
+
+def time_adjoint(levels=4, base=32, n=20, warm=3):
+    """iunet_sf_adjoint alone, per level, at the grids of the 'sf_adjoint (all levels)' bound: u [N][ch_l] on T, dx on level l's grid."""
+    import ctypes
+    import torch
+    from interactive_unet import _native as nv
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    for dim, N, sp, T in ((2, 8, (512, 512), torch.float16), (3, 2, (128, 128, 128), torch.bfloat16)):
+        tg = [x >> 2 for x in sp]
+        Dt, Ht, Wt = tg if dim == 3 else [1] + tg
+        ts = []
+        for l in range(levels):
+            C, sg = base * 2 ** l, [x >> l for x in sp]
+            Ds, Hs, Ws = sg if dim == 3 else [1] + sg
+            u = torch.randn(N * C * Dt * Ht * Wt, device='cuda').to(T)
+            dx = torch.empty(N * C * Ds * Hs * Ws, dtype=T, device='cuda')
+            fn = lambda: nv.call('iunet_sf_adjoint', nv.DTYPE_CODE[T], dim, P(u), C * Dt * Ht * Wt, Dt, Ht, Wt, P(dx), C * Ds * Hs * Ws, Ds, Hs, Ws,
+                                 C, N, nv.stream())
+            for _ in range(warm):
+                fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(n):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) / n * 1e3)
+        b = bounds(dim, N, sp, levels=levels, base=base)['sf_adjoint (all levels)'][0]
+        print(f'sf_adjoint {dim}-D {N} x {sp} {str(T)[6:]}: levels ' + ' + '.join(f'{t:.1f}' for t in ts) +
+              f' = {sum(ts):.1f} us   (bound {b / HBM * 1e6:.1f} us)')
 
 
 def main():
@@ -92,5 +125,7 @@ def main():
 if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'bounds':
         print_bounds()
+    elif len(sys.argv) > 1 and sys.argv[1] == 'adjoint':
+        time_adjoint()
     else:
         main()
