@@ -539,6 +539,33 @@ int iunet_edt_sq_mask(const void* prev, int Z, int Y, int X, int r2, int above,
 int iunet_edt_select(const void* d2, const void* cls, int Z, int Y, int X, int r2, int above, int only, int value,
                      void* out, void* stream);
 
+/* ---- nearest-seed feature transform and instance labels of a resident volume (defined bit for bit by
+ * tests/instances_ref.py) ----------- */
+/* iunet_edt_sq carrying one more value.  src, C, target, invert, the seeds S, d2 (required here), cls (NULL or uint8) and the limits as
+ * above.  idx: int32 [Z][Y][X], the raster index (z Y + y) X + x of the seed nearest to the voxel -- of the seeds at the minimum distance
+ * the one with the smallest raster index; the voxel's own index on S; -1 everywhere when S is empty.  d2 has iunet_edt_sq's bits.
+ * ws: iunet_edt_feature_ws_bytes(Z, Y, X) bytes of device memory, 12 per voxel (0 = refused, by iunet_edt_ws_bytes' rule): the columns'
+ * stacks and a second idx map -- each column pass reads the map the pass before wrote and writes the other, so no entry is read after
+ * it has been overwritten.  d2 and idx do not overlap.  No atomics, one owner per element: the same bits on every launch. */
+long long iunet_edt_feature_ws_bytes(int Z, int Y, int X);
+int iunet_edt_feature(const void* src, int Z, int Y, int X, int C, int target, int invert,
+                      void* d2, void* idx, void* cls, void* ws, long long ws_bytes, void* stream);
+/* The same with the seeds read off an int32 map: S = {prev > r2} (above 1) or {prev <= r2} (above 0), iunet_edt_sq_mask's rule; r2 = 0,
+ * above 1: the labelled voxels of a label map.  No two of prev, d2 and idx overlap. */
+int iunet_edt_feature_mask(const void* prev, int Z, int Y, int X, int r2, int above,
+                           void* d2, void* idx, void* ws, long long ws_bytes, void* stream);
+/* Labels from the nearest seed.  idx, d2, seed_labels, out: int32 [Z][Y][X]; group: NULL or int32 [Z][Y][X]; 0 <= r2 <= 2^31 - 2;
+ * offset >= 0.  A voxel v is reached if 0 <= idx[v] < Z Y X and d2[v] <= r2 (an idx outside the volume counts as no seed).
+ * group == NULL: out[v] = seed_labels[idx[v]] where v is reached, 0 elsewhere.
+ * group != NULL: out[v] = 0 where group[v] == 0; seed_labels[idx[v]] where v is reached and group[idx[v]] == group[v]; offset + group[v]
+ * otherwise (the sum must fit int32).  out may be d2; it may overlap none of idx, seed_labels and group (they are read through idx).
+ * One streaming pass. */
+int iunet_edt_assign(const void* idx, const void* d2, const void* seed_labels, const void* group, int offset,
+                     int Z, int Y, int X, int r2, void* out, void* stream);
+/* labels[v] = map[labels[v]] in place; labels int32 [Z][Y][X], map int32 [K + 1] on the device, K >= 0.  A label outside
+ * 0 .. K is left as it is.  One streaming pass. */
+int iunet_label_remap(void* labels, int Z, int Y, int X, int K, const void* map, void* stream);
+
 /* ---- multiscale pyramid (utils.py:29-77 resize_volume / add_multiscales; SURVEY 8f "Zarr block I/O ... 0.5x nearest
  * multiscale pyramid on device") ----------------------------------------------------------------------------------- */
 /* scipy.ndimage.zoom(x, zoom, order=0) index arithmetic for one axis (host only, no GPU): n_out = round-half-even(n_in *

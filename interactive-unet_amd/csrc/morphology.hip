@@ -16,6 +16,11 @@
 //                   f = INF never enter the envelope (the sums below would overflow).  The stack (site uint16, start uint16, f int32 = one 8-byte
 //                   entry per voxel, laid out [k][column] like the volume) lives in the workspace: the pass runs in place on d2 -- the
 //                   forward scan reads the whole column before the backward scan writes it, and the backward scan reads f from the stack.
+//   <.., true>      the feature transform: the same passes carrying one more value, idx, the raster index of the nearest
+//                   seed.  The row pass records which of its two candidates won (the left on a tie).  A column pass writes, beside d2[u],
+//                   idx_out[u] = idx_in[site] of the parabola that governs u, read once per parabola as the backward scan reaches it; idx_in
+//                   is the map the pass before wrote and idx_out another one (the caller's and a spare in the workspace, alternating),
+//                   so no entry is read after this pass has overwritten it.  The <.., false> instantiations are the kernels as they were.
 //   the select      one streaming pass, volume_select_kernel (volume_rules.h) with SelectPick: out = value where the distance passes the
 //                   threshold (and the class is `only`), else cls.
 //
@@ -52,6 +57,7 @@ struct RowParams {
   int X, C, target, invert, r2, above;
   int words;                   // ceil(X / 64)
   long long rows;
+  int* idx;                    // F: the raster index of the row's nearest seed (the left one of two equally near), -1 in a row without one
 };
 
 // CT: 1 a class map, 2 two classes, 0 any number of classes, 3 a distance map
@@ -67,7 +73,8 @@ __device__ __forceinline__ bool voxel_seed(const RowParams& p, long long v) {
   return (t.best > 0 && t.at == p.target) != (p.invert != 0);
 }
 
-template <int CT>
+// F: the feature transform -- the pass also records which seed is the nearest
+template <int CT, bool F>
 __global__ __launch_bounds__(ED_THREADS) void row_kernel(RowParams p) {
   __shared__ unsigned long long bits[ED_WORDS];
   __shared__ int L[ED_WORDS], R[ED_WORDS];
@@ -111,7 +118,7 @@ __global__ __launch_bounds__(ED_THREADS) void row_kernel(RowParams p) {
     for (int k = 0; k < chunks; ++k) {                   // fixed trip count
       const int x = k * ED_THREADS + threadIdx.x;
       if (x >= p.X) break;
-      int out = ED_INF;
+      int out = ED_INF, at = -1;
       if (!none) {
         const int w = x >> 6, b = x & 63;
         const unsigned long long m = bits[w];
@@ -121,8 +128,10 @@ __global__ __launch_bounds__(ED_THREADS) void row_kernel(RowParams p) {
         const int gl = left < 0 ? ED_NONE : x - left, gr = right == ED_NONE ? ED_NONE : right - x;
         const int g = min(gl, gr);                       // <= 46340: one side has a seed
         out = g * g;
+        if (F) at = (int)(base + (gl <= gr ? left : right));   // the left seed on a tie: the smaller raster index; below 2^31 - 1
       }
       p.d2[base + x] = out;
+      if (F) p.idx[base + x] = at;
     }
     __syncthreads();                                     // the next row overwrites the tables
   }
@@ -135,12 +144,19 @@ struct ColParams {
   long long stride;            // between the entries of a column
   long long plane;             // inner pass (Y): Y X; a column is (z, x) = (c / X, c % X)
   int X, n, inner;
+  const int* idx_in;           // F: the pass before's nearest seed of every entry (-1 where f = INF) ...
+  int* idx_out;                // ... and this pass's: another buffer, so no entry is read after this pass has written it
 };
 
+// F: the feature transform -- the backward scan also writes the governing site's seed, idx_out[u] = idx_in[site].  The envelope keeps the
+// smaller site on every tie (a later site governs from 1 + Sep on: only where it is strictly better; the top is popped only when it is
+// strictly worse), so of equally near seeds the one in the smaller plane / row wins: the smallest raster index.
+template <bool F>
 __global__ __launch_bounds__(ED_THREADS) void column_kernel(ColParams p) {
   // trip count fixed at launch (no barrier in here: it need not be uniform)
   for (long long c = (long long)blockIdx.x * ED_THREADS + threadIdx.x; c < p.ncols; c += (long long)gridDim.x * ED_THREADS) {
-    int* col = p.d2 + (p.inner ? (c / p.X) * p.plane + c % p.X : c);
+    const long long first = p.inner ? (c / p.X) * p.plane + c % p.X : c;
+    int* col = p.d2 + first;
     uint2* mine = p.stack + c;                           // entry k of this column's stack: mine[k ncols]
     int q = -1, ts = 0, tt = 0;                          // the stack's height - 1 and its top, kept in registers
     unsigned int tf = 0;
@@ -176,13 +192,20 @@ __global__ __launch_bounds__(ED_THREADS) void column_kernel(ColParams p) {
         }
       }
     }
-    if (q < 0) continue;                                 // a column without a seed: INF already
+    if (q < 0) {                                         // a column without a seed: INF already
+      if (F) for (int u = 0; u < p.n; ++u) p.idx_out[first + (long long)u * p.stride] = -1;      // fixed trip count
+      continue;
+    }
+    int at = 0;
+    if (F) at = p.idx_in[first + (long long)ts * p.stride];
     for (int u = p.n - 1; u >= 0; --u) {                 // fixed trip count; the bottom entry begins at 0, so q >= 0 down to u == 0
       col[(long long)u * p.stride] = (u - ts) * (u - ts) + (int)tf;
+      if (F) p.idx_out[first + (long long)u * p.stride] = at;
       if (u == tt && q > 0) {
         --q;
         const uint2 e = mine[q * p.ncols];
         ts = (int)(e.x & 0xffffu); tt = (int)(e.x >> 16); tf = e.y;
+        if (F) at = p.idx_in[first + (long long)ts * p.stride];
       }
     }
   }
@@ -202,21 +225,29 @@ inline bool ed_volume_ok(int Z, int Y, int X) {
   return (long long)(Z - 1) * (Z - 1) + (long long)(Y - 1) * (Y - 1) + (long long)(X - 1) * (X - 1) <= ED_MAX_SQ;
 }
 
-// passes Y and Z in place on d2; an axis of one entry is its own envelope
-int ed_columns(int* d2, int Z, int Y, int X, void* ws, hipStream_t st) {
+// The feature transform's idx alternates between the caller's map and a spare one in the workspace, pass by pass; the row pass begins in
+// the one from which the column passes that will run (an axis of one entry has none) end in the caller's.
+inline int* ed_row_idx(int* idx, int* spare, int Z, int Y) { return ((Y > 1) != (Z > 1)) ? spare : idx; }
+
+// passes Y and Z in place on d2; an axis of one entry is its own envelope.  idx: NULL, or the feature transform's map (ed_row_idx)
+int ed_columns(int* d2, int Z, int Y, int X, void* ws, hipStream_t st, int* idx = nullptr, int* spare = nullptr) {
   ColParams c;
   c.d2 = d2;
   c.stack = (uint2*)ws;
   c.X = X;
   c.plane = (long long)Y * X;
+  c.idx_in = nullptr; c.idx_out = idx ? ed_row_idx(idx, spare, Z, Y) : nullptr;
+  void (*column)(ColParams) = idx ? column_kernel<true> : column_kernel<false>;
   if (Y > 1) {
     c.ncols = (long long)Z * X; c.stride = X; c.n = Y; c.inner = 1;
-    hipLaunchKernelGGL(column_kernel, dim3(volume_grid((c.ncols + ED_THREADS - 1) / ED_THREADS, ED_MAX_GRID)), dim3(ED_THREADS), 0, st, c);
+    c.idx_in = c.idx_out; c.idx_out = c.idx_in == idx ? spare : idx;
+    hipLaunchKernelGGL(column, dim3(volume_grid((c.ncols + ED_THREADS - 1) / ED_THREADS, ED_MAX_GRID)), dim3(ED_THREADS), 0, st, c);
     IUNET_CHECK_HIP(hipGetLastError());
   }
   if (Z > 1) {
     c.ncols = c.plane; c.stride = c.plane; c.n = Z; c.inner = 0;
-    hipLaunchKernelGGL(column_kernel, dim3(volume_grid((c.ncols + ED_THREADS - 1) / ED_THREADS, ED_MAX_GRID)), dim3(ED_THREADS), 0, st, c);
+    c.idx_in = c.idx_out; c.idx_out = c.idx_in == idx ? spare : idx;
+    hipLaunchKernelGGL(column, dim3(volume_grid((c.ncols + ED_THREADS - 1) / ED_THREADS, ED_MAX_GRID)), dim3(ED_THREADS), 0, st, c);
     IUNET_CHECK_HIP(hipGetLastError());
   }
   return IUNET_OK;
@@ -252,7 +283,8 @@ int iunet_edt_sq(const void* src, int Z, int Y, int X, int C, int target, int in
   p.X = X; p.C = C; p.target = target; p.invert = invert; p.r2 = 0; p.above = 0;
   p.words = (X + 63) / 64;
   p.rows = (long long)Z * Y;
-  void (*row[3])(RowParams) = {row_kernel<0>, row_kernel<1>, row_kernel<2>};
+  p.idx = nullptr;
+  void (*row[3])(RowParams) = {row_kernel<0, false>, row_kernel<1, false>, row_kernel<2, false>};
   hipLaunchKernelGGL(row[C <= 2 ? C : 0], dim3(volume_grid(p.rows, ED_MAX_GRID)), dim3(ED_THREADS), 0, st, p);
   IUNET_CHECK_HIP(hipGetLastError());
   return d2 ? ed_columns((int*)d2, Z, Y, X, ws, st) : IUNET_OK;
@@ -276,9 +308,73 @@ int iunet_edt_sq_mask(const void* prev, int Z, int Y, int X, int r2, int above,
   p.X = X; p.C = 1; p.target = 0; p.invert = 0; p.r2 = r2; p.above = above;
   p.words = (X + 63) / 64;
   p.rows = (long long)Z * Y;
-  hipLaunchKernelGGL(row_kernel<3>, dim3(volume_grid(p.rows, ED_MAX_GRID)), dim3(ED_THREADS), 0, st, p);
+  p.idx = nullptr;
+  hipLaunchKernelGGL((row_kernel<3, false>), dim3(volume_grid(p.rows, ED_MAX_GRID)), dim3(ED_THREADS), 0, st, p);
   IUNET_CHECK_HIP(hipGetLastError());
   return ed_columns((int*)d2, Z, Y, X, ws, st);
+}
+
+// the feature transform's workspace: the columns' stacks, then the spare idx map: 12 bytes per voxel, each part a multiple of 16 bytes
+long long iunet_edt_feature_ws_bytes(int Z, int Y, int X) {
+  if (!ed_volume_ok(Z, Y, X)) return 0;
+  const long long N = (long long)Z * Y * X;
+  return volume_align16(8 * N) + volume_align16(4 * N);
+}
+
+int iunet_edt_feature(const void* src, int Z, int Y, int X, int C, int target, int invert,
+                      void* d2, void* idx, void* cls, void* ws, long long ws_bytes, void* stream) {
+  IUNET_REQUIRE(src && d2 && idx && ws, "edt_feature: null pointer (src, d2, idx, ws)");
+  VOLUME_REQUIRE_DIMS("edt_feature", Z, Y, X);
+  IUNET_REQUIRE(ed_volume_ok(Z, Y, X), "edt_feature: volume %d x %d x %d: more than 2^31 - 1 voxels or a squared diagonal above 2^31 - 2", Z, Y, X);
+  IUNET_REQUIRE(C >= 1 && C <= 16, "edt_feature: %d classes outside 1..16", C);
+  IUNET_REQUIRE(target >= 0 && target <= 255, "edt_feature: target %d outside 0..255", target);
+  IUNET_REQUIRE(invert == 0 || invert == 1, "edt_feature: invert %d (0 or 1)", invert);
+  IUNET_REQUIRE(ws_bytes >= iunet_edt_feature_ws_bytes(Z, Y, X), "edt_feature: workspace of %lld bytes, %lld needed", ws_bytes,
+                iunet_edt_feature_ws_bytes(Z, Y, X));
+  IUNET_REQUIRE((((uintptr_t)d2 | (uintptr_t)idx | (uintptr_t)ws) & 3) == 0, "edt_feature: d2, idx and the workspace must be 4-byte aligned");
+  const long long N = (long long)Z * Y * X;
+  IUNET_REQUIRE((uintptr_t)idx + 4 * (uintptr_t)N <= (uintptr_t)d2 || (uintptr_t)d2 + 4 * (uintptr_t)N <= (uintptr_t)idx,
+                "edt_feature: d2 and idx overlap");
+  hipStream_t st = (hipStream_t)stream;
+  int* spare = (int*)((char*)ws + volume_align16(8 * N));
+  RowParams p;
+  p.src = (const unsigned char*)src; p.prev = nullptr; p.d2 = (int*)d2; p.cls = (unsigned char*)cls;
+  p.X = X; p.C = C; p.target = target; p.invert = invert; p.r2 = 0; p.above = 0;
+  p.words = (X + 63) / 64;
+  p.rows = (long long)Z * Y;
+  p.idx = ed_row_idx((int*)idx, spare, Z, Y);
+  void (*row[3])(RowParams) = {row_kernel<0, true>, row_kernel<1, true>, row_kernel<2, true>};
+  hipLaunchKernelGGL(row[C <= 2 ? C : 0], dim3(volume_grid(p.rows, ED_MAX_GRID)), dim3(ED_THREADS), 0, st, p);
+  IUNET_CHECK_HIP(hipGetLastError());
+  return ed_columns((int*)d2, Z, Y, X, ws, st, (int*)idx, spare);
+}
+
+int iunet_edt_feature_mask(const void* prev, int Z, int Y, int X, int r2, int above,
+                           void* d2, void* idx, void* ws, long long ws_bytes, void* stream) {
+  IUNET_REQUIRE(prev && d2 && idx && ws, "edt_feature_mask: null pointer (prev, d2, idx, ws)");
+  VOLUME_REQUIRE_DIMS("edt_feature_mask", Z, Y, X);
+  IUNET_REQUIRE(ed_volume_ok(Z, Y, X), "edt_feature_mask: volume %d x %d x %d: more than 2^31 - 1 voxels or a squared diagonal above 2^31 - 2", Z, Y, X);
+  IUNET_REQUIRE(r2 >= 0 && r2 <= ED_MAX_SQ, "edt_feature_mask: threshold r2 %d outside 0..2^31 - 2", r2);
+  IUNET_REQUIRE(above == 0 || above == 1, "edt_feature_mask: above %d (0 or 1)", above);
+  IUNET_REQUIRE(ws_bytes >= iunet_edt_feature_ws_bytes(Z, Y, X), "edt_feature_mask: workspace of %lld bytes, %lld needed", ws_bytes,
+                iunet_edt_feature_ws_bytes(Z, Y, X));
+  IUNET_REQUIRE((((uintptr_t)prev | (uintptr_t)d2 | (uintptr_t)idx | (uintptr_t)ws) & 3) == 0,
+                "edt_feature_mask: prev, d2, idx and the workspace must be 4-byte aligned");
+  const long long N = (long long)Z * Y * X;
+  const uintptr_t a = (uintptr_t)prev, b = (uintptr_t)d2, c = (uintptr_t)idx, len = 4 * (uintptr_t)N;
+  IUNET_REQUIRE((a + len <= b || b + len <= a) && (a + len <= c || c + len <= a) && (b + len <= c || c + len <= b),
+                "edt_feature_mask: prev, d2 and idx overlap");
+  hipStream_t st = (hipStream_t)stream;
+  int* spare = (int*)((char*)ws + volume_align16(8 * N));
+  RowParams p;
+  p.src = nullptr; p.prev = (const int*)prev; p.d2 = (int*)d2; p.cls = nullptr;
+  p.X = X; p.C = 1; p.target = 0; p.invert = 0; p.r2 = r2; p.above = above;
+  p.words = (X + 63) / 64;
+  p.rows = (long long)Z * Y;
+  p.idx = ed_row_idx((int*)idx, spare, Z, Y);
+  hipLaunchKernelGGL((row_kernel<3, true>), dim3(volume_grid(p.rows, ED_MAX_GRID)), dim3(ED_THREADS), 0, st, p);
+  IUNET_CHECK_HIP(hipGetLastError());
+  return ed_columns((int*)d2, Z, Y, X, ws, st, (int*)idx, spare);
 }
 
 int iunet_edt_select(const void* d2, const void* cls, int Z, int Y, int X, int r2, int above, int only, int value,
