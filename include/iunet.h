@@ -566,6 +566,33 @@ int iunet_edt_assign(const void* idx, const void* d2, const void* seed_labels, c
  * 0 .. K is left as it is.  One streaming pass. */
 int iunet_label_remap(void* labels, int Z, int Y, int X, int K, const void* map, void* stream);
 
+/* ---- geodesic seeded growth through a resident volume (defined bit for bit by tests/geodesic_ref.py) ----------- */
+/* Integer seed labels grow through a domain A along the shortest path inside A.  A: the voxels of class `target` of src (C, target and
+ * the class rule as above), or {dom > 0} of an int32 [Z][Y][X] map.  seeds: int32 [Z][Y][X]; the voxels of A with seeds[v] > 0 are the
+ * seeds and seeds[v] their label; an entry off A is ignored.  Metric: (w1, w2, w3), the weight of a step to a face, edge and vertex
+ * neighbour; 0: no such step; 1 <= w1 <= 255, 0 <= w2, w3 <= 255.  g[v]: the least weight of a path from a seed to v whose every voxel
+ * lies in A, 0 on a seed, INF = 2^31 - 1 off A and where no seed is reachable; label[v]: the SMALLEST label among the seeds at that
+ * distance (not section 26's smallest raster index), 0 where g[v] = INF.
+ * ws: iunet_geo_ws_bytes(Z, Y, X) bytes of device memory, 16-byte aligned: a 64-bit key per voxel (g in the high word, the label in the
+ * low one; all ones off A) and two int32 flags per tile of 8 x 8 x 64 voxels, each part a multiple of 16 bytes (0 = refused: a dimension
+ * < 1 or Z Y X > 2^31 - 1).  iunet_geo_init / iunet_geo_init_mask write the initial state and set every flag. */
+long long iunet_geo_ws_bytes(int Z, int Y, int X);
+int iunet_geo_init(const void* src, int Z, int Y, int X, int C, int target, const void* seeds,
+                   void* ws, long long ws_bytes, void* stream);
+int iunet_geo_init_mask(const void* dom, int Z, int Y, int X, const void* seeds,
+                        void* ws, long long ws_bytes, void* stream);
+/* 1 <= rounds <= 1024 rounds of relaxation, asynchronously; a round is one launch in which every tile whose own or neighbouring tiles
+ * changed in the round before relaxes its keys.  changed: one int32 on the device (outside ws): the number of tiles that changed in the
+ * last round; 0: ws holds the fixed point, and further rounds leave every byte as it is.  Refused: Z Y X max(w) > 2^31 - 2 (a distance
+ * could overflow).  The fixed point does not depend on the order of the relaxations: the same bytes on every launch. */
+int iunet_geo_relax(void* ws, long long ws_bytes, int Z, int Y, int X, int w1, int w2, int w3, int rounds,
+                    void* changed, void* stream);
+/* labels (int32 [Z][Y][X]) and, where g is not NULL, g (int32 [Z][Y][X]) of the state in ws.  fallback: NULL or int32 [Z][Y][X]; with it
+ * labels[v] = offset + fallback[v] on the voxels of A no seed reached (offset >= 0; the sum must fit int32).  labels and g overlap
+ * neither each other, ws nor fallback.  One streaming pass. */
+int iunet_geo_finish(const void* ws, long long ws_bytes, int Z, int Y, int X, void* labels, void* g, const void* fallback,
+                     int offset, void* stream);
+
 /* ---- multiscale pyramid (utils.py:29-77 resize_volume / add_multiscales; SURVEY 8f "Zarr block I/O ... 0.5x nearest
  * multiscale pyramid on device") ----------------------------------------------------------------------------------- */
 /* scipy.ndimage.zoom(x, zoom, order=0) index arithmetic for one axis (host only, no GPU): n_out = round-half-even(n_in *

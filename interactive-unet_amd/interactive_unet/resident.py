@@ -1,5 +1,5 @@
-"""What components.py, morphology.py and propose.py check and compute alike: a uint8 volume on the device (a CUDA tensor) or on the host (a
-numpy array), their small integer arguments, and the host path's class maps.  Every check raises ValueError before any GPU work."""
+"""What components.py, morphology.py, propose.py and geodesic.py check and compute alike: a uint8 volume or an int32 map on the device (a
+CUDA tensor) or on the host (a numpy array), their small integer arguments, and the host path's class maps.  Every check raises ValueError before any GPU work."""
 import numpy as np
 import torch
 
@@ -31,6 +31,30 @@ def check_volume(src, max_sq=None):
     if max_sq is not None and (Z - 1) ** 2 + (Y - 1) ** 2 + (X - 1) ** 2 > max_sq:
         raise ValueError(f'volume {Z} x {Y} x {X}: its squared diagonal passes 2^31 - 2')
     return dev, Z, Y, X, (1 if src.ndim == 3 else int(src.shape[3]))
+
+
+def check_map(m, name, beside=None):
+    """Validated (on_device, Z, Y, X) of an int32 map [Z, Y, X]; beside = (on_device, Z, Y, X): on that side (device or host) and of that
+    shape."""
+    dev = torch.is_tensor(m)
+    if not (dev or isinstance(m, np.ndarray)):
+        raise ValueError(f'{name} must be a CUDA int32 tensor or a numpy int32 array')
+    if dev and not m.is_cuda:
+        raise ValueError(f'resident {name} must be a CUDA tensor (a host map goes in as a numpy array)')
+    if beside is not None and dev != beside[0]:
+        raise ValueError(f'{name} must be a CUDA tensor beside a resident volume, a numpy array beside a host volume')
+    if m.dtype != (torch.int32 if dev else np.int32):
+        raise ValueError(f'{name} must be int32, got {m.dtype}')
+    if not (m.is_contiguous() if dev else m.flags['C_CONTIGUOUS']):
+        raise ValueError(f'{name} must be contiguous')
+    if m.ndim != 3 or min(m.shape) < 1:
+        raise ValueError(f'{name} must be [Z, Y, X], got {tuple(m.shape)}')
+    Z, Y, X = (int(n) for n in m.shape)
+    if beside is not None and (Z, Y, X) != tuple(beside[1:]):
+        raise ValueError(f'{name} must be {tuple(beside[1:])}, got {(Z, Y, X)}')
+    if Z * Y * X > MAX_VOXELS:
+        raise ValueError(f'volume {Z} x {Y} x {X}: more than 2^31 - 1 voxels')
+    return dev, Z, Y, X
 
 
 def is_int(value):
