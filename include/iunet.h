@@ -593,6 +593,31 @@ int iunet_geo_relax(void* ws, long long ws_bytes, int Z, int Y, int X, int w1, i
 int iunet_geo_finish(const void* ws, long long ws_bytes, int Z, int Y, int X, void* labels, void* g, const void* fallback,
                      int offset, void* stream);
 
+/* ---- grayscale reconstruction of a resident volume: h-maxima markers (defined bit for bit by
+ * tests/reconstruct_ref.py) ----------- */
+/* marker, mask, r: int32 [Z][Y][X] on the device, any values.  By dilation (erosion 0): r0[v] = min(sat(marker[v] - h), mask[v]), sat
+ * clamping the 64-bit difference to int32, and R the fixed point of r[v] = min(mask[v], max(r[v], max over the neighbours u inside the
+ * volume of r[u])) started at r0; by erosion (erosion 1) the dual: max and min exchanged, sat(marker[v] + h).  connectivity 6, 18 or 26.
+ * ws: iunet_rec_ws_bytes(Z, Y, X) bytes of device memory, 16-byte aligned: two int32 flags per tile of 8 x 8 x 64 voxels, each array a
+ * multiple of 16 bytes (0 = refused: a dimension < 1 or Z Y X > 2^31 - 1). */
+long long iunet_rec_ws_bytes(int Z, int Y, int X);
+/* f[v] (int32 [Z][Y][X]) = floor(sqrt(scale^2 d2[v])) where d2[v] > 0 (the product in 64 bits, the floor exact), `off` elsewhere; d2 int32
+ * [Z][Y][X]; 1 <= scale <= 256; f may be d2 itself, else they do not overlap.  One streaming pass. */
+int iunet_rec_landscape(const void* d2, int Z, int Y, int X, int scale, int off, void* f, void* stream);
+/* r = r0 and every tile flag set.  h >= 0; marker may be mask; r overlaps neither marker, mask nor ws.  One streaming pass. */
+int iunet_rec_init(const void* marker, const void* mask, int Z, int Y, int X, int h, int erosion, void* r, void* ws,
+                   long long ws_bytes, void* stream);
+/* 1 <= rounds <= 1024 rounds of relaxation of r under mask, asynchronously; a round is one launch in which every tile whose own or
+ * neighbouring tiles changed in the round before relaxes its voxels.  connectivity and erosion as iunet_rec_init was called.  changed: one
+ * int32 on the device (outside ws and r): the number of tiles that changed in the last round; 0: r holds R, and further rounds leave
+ * every byte as it is.  r overlaps neither mask nor ws.  The fixed point does not depend on the order of the updates: the same bytes on
+ * every launch. */
+int iunet_rec_relax(void* r, const void* mask, int Z, int Y, int X, int connectivity, int erosion, int rounds, void* changed,
+                    void* ws, long long ws_bytes, void* stream);
+/* out[v] (uint8 [Z][Y][X]) = value where a[v] - b[v] >= t (the difference in 64 bits), 0 elsewhere; a, b int32 [Z][Y][X]; value
+ * 0 .. 255; out overlaps neither a nor b.  One streaming pass. */
+int iunet_rec_select(const void* a, const void* b, int Z, int Y, int X, int t, int value, void* out, void* stream);
+
 /* ---- multiscale pyramid (utils.py:29-77 resize_volume / add_multiscales; SURVEY 8f "Zarr block I/O ... 0.5x nearest
  * multiscale pyramid on device") ----------------------------------------------------------------------------------- */
 /* scipy.ndimage.zoom(x, zoom, order=0) index arithmetic for one axis (host only, no GPU): n_out = round-half-even(n_in *

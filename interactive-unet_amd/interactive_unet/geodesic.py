@@ -6,6 +6,7 @@ integer seed labels grow through a domain along the shortest path INSIDE the dom
   split_touching(src, target, radius, conn, metric)
                                                (labels, count): instances.split_touching with geodesic cells -- every voxel of an object
                                                takes the core it reaches by the shortest path inside the class; no path leaves an object
+  split_from_seeds(a, seeds, count, ...)       the tail of such a split (grow, fallback, renumber), for reconstruction.py's markers too
 
 src is uint8 as in morphology.py: a class map [Z, Y, X] or a predicted volume [Z, Y, X, C].  seeds is an int32 [Z, Y, X] map: the voxels
 of the domain with seeds > 0 are the seeds, the value is their label; an entry off the domain is ignored.  metric: 6, 18, 26 (unit steps
@@ -161,6 +162,40 @@ def split_weights(metric, connectivity):
     return tuple(w if k < rank else 0 for k, w in enumerate(_weights(metric)))
 
 
+def split_from_seeds(a, seeds, count, connectivity, weights, max_rounds):
+    """(labels int32 [Z, Y, X], instances): the tail of a split, written once for split_touching here and in reconstruction.py.  a: A as
+    a resident uint8 map (1 on A) or a numpy bool map; seeds: a ONE-ELEMENT LIST holding the int32 map of labels 1 .. count on A
+    (validated by the caller, as weights and max_rounds) -- the list is emptied here and the map released once it has grown, so a caller
+    that keeps no other reference does not hold it through the table, sort and remap.  The seeds grow through A; the voxels of A none
+    reaches take count + the label of their object (a component of A under `connectivity`); the labels that occur are renumbered in
+    increasing order of their first voxels."""
+    Z, Y, X = (int(n) for n in a.shape)
+    seeds = seeds.pop()
+    if torch.is_tensor(a):
+        from . import _native as nv
+        la, ka = instances._label(a, Z, Y, X, connectivity)
+        raw, _ = _grow_device(a, None, seeds, Z, Y, X, 1, 1, weights, max_rounds, want_g=False, fallback=la, offset=count)
+        del seeds, la
+        K = min(count + ka, Z * Y * X)                                # instances.split_touching's bound: every label of raw is <= K
+        sizes, first = instances._table(raw, a, Z, Y, X, K)
+        # the K-entry plumbing: the labels that occur, in order of their first voxel
+        there = sizes[1:] > 0
+        order = torch.sort(torch.where(there, first[1:], torch.full_like(first[1:], INF)).to(torch.int64), stable=True).indices
+        found = int(there.sum().item())
+        number = torch.zeros(K + 1, dtype=torch.int32, device=a.device)
+        number[order[:found] + 1] = torch.arange(1, found + 1, dtype=torch.int32, device=a.device)
+        with torch.cuda.device(a.device):
+            nv.call('iunet_label_remap', nv.ptr(raw), Z, Y, X, K, nv.ptr(number), nv.stream())
+        return raw, found
+    la, ka, _ = components.label(a.astype(np.uint8), connectivity)
+    raw = _host_finish(_host_keys(a, seeds, weights, max_rounds), fallback=la, offset=count)[0]
+    _, first = instances.instance_table(raw, count + ka)
+    there = np.flatnonzero(first[1:] >= 0)
+    number = np.zeros(count + ka + 1, dtype=np.int32)
+    number[there[np.argsort(first[1:][there], kind='stable')] + 1] = np.arange(1, len(there) + 1, dtype=np.int32)
+    return number[raw], len(there)
+
+
 def split_touching(src, target, radius, connectivity=6, metric='chamfer', max_rounds=None):
     """(labels int32 [Z, Y, X], count): 0 off class `target`.  The cores are the components of the class eroded by the ball of `radius`
     (instances.split_touching's); every voxel of an object -- a component of the class -- takes the core nearest along paths inside the
@@ -174,33 +209,14 @@ def split_touching(src, target, radius, connectivity=6, metric='chamfer', max_ro
     _check_overflow(Z, Y, X, weights)
     max_rounds = _check_rounds(max_rounds, Z, Y, X)
     if dev:
-        from . import _native as nv
         d_out = morphology._edt(src, Z, Y, X, C, target, True, want_cls=False)[0]      # the distance to the outside of A: > 0 exactly on A
         a = (d_out > 0).to(torch.uint8)
-        la, ka = instances._label(a, Z, Y, X, connectivity)
         le, ke = instances._label((d_out > r2).to(torch.uint8), Z, Y, X, connectivity)
-        del d_out
-        raw, _ = _grow_device(a, None, le, Z, Y, X, 1, 1, weights, max_rounds, want_g=False, fallback=la, offset=ke)
-        del le, la
-        K = min(ke + ka, Z * Y * X)                                   # instances.split_touching's bound: every label of raw is <= K
-        sizes, first = instances._table(raw, a, Z, Y, X, K)
-        # the K-entry plumbing: the labels that occur, in order of their first voxel
-        there = sizes[1:] > 0
-        order = torch.sort(torch.where(there, first[1:], torch.full_like(first[1:], INF)).to(torch.int64), stable=True).indices
-        count = int(there.sum().item())
-        number = torch.zeros(K + 1, dtype=torch.int32, device=src.device)
-        number[order[:count] + 1] = torch.arange(1, count + 1, dtype=torch.int32, device=src.device)
-        with torch.cuda.device(src.device):
-            nv.call('iunet_label_remap', nv.ptr(raw), Z, Y, X, K, nv.ptr(number), nv.stream())
-        return raw, count
+        seeds = [le]
+        del d_out, le
+        return split_from_seeds(a, seeds, ke, connectivity, weights, max_rounds)
     cls, has = resident.host_maps(src)
     a = has & (cls == target)
     d_out = morphology._host_d2(~a)
-    la, ka, _ = components.label(a.astype(np.uint8), connectivity)
     le, ke, _ = components.label((d_out > r2).astype(np.uint8), connectivity)
-    raw = _host_finish(_host_keys(a, le, weights, max_rounds), fallback=la, offset=ke)[0]
-    _, first = instances.instance_table(raw, ke + ka)
-    there = np.flatnonzero(first[1:] >= 0)
-    number = np.zeros(ke + ka + 1, dtype=np.int32)
-    number[there[np.argsort(first[1:][there], kind='stable')] + 1] = np.arange(1, len(there) + 1, dtype=np.int32)
-    return number[raw], len(there)
+    return split_from_seeds(a, [le], ke, connectivity, weights, max_rounds)

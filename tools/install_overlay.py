@@ -18,7 +18,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.join(os.path.dirname(HERE), 'interactive-unet_amd')
 REPLACED = ['unet', 'trainer', 'predict', 'metrics', 'slicer', 'loader', 'suggestor']
-ADDED = ['_native', 'topology', 'engine', 'engine_f32', 'engine_x2', 'engine_auto', 'net_graph', 'train_engine', 'train_engine_f32', 'engine_nested', 'train_engine_nested', 'engine_linknet', 'train_engine_linknet', 'engine_deeplab', 'train_engine_deeplab', 'engine_segformer', 'train_engine_segformer', 'engine_upernet', 'train_engine_upernet', 'engine_manet', 'train_engine_manet', 'shard', 'dp', 'multiscale', 'zarr3', 'resident', 'propose', 'tta', 'components', 'morphology', 'instances', 'geodesic']
+ADDED = ['_native', 'topology', 'engine', 'engine_f32', 'engine_x2', 'engine_auto', 'net_graph', 'train_engine', 'train_engine_f32', 'engine_nested', 'train_engine_nested', 'engine_linknet', 'train_engine_linknet', 'engine_deeplab', 'train_engine_deeplab', 'engine_segformer', 'train_engine_segformer', 'engine_upernet', 'train_engine_upernet', 'engine_manet', 'train_engine_manet', 'shard', 'dp', 'multiscale', 'zarr3', 'resident', 'propose', 'tta', 'components', 'morphology', 'instances', 'geodesic', 'reconstruction']
 NOT_INSTALLED = ['utils', '__init__']          # the reference's own stay
 
 
